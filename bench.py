@@ -19,8 +19,12 @@ Weak scaling: every rank holds its own shard; only the small moment / member-sum
 Other workloads (--config): c4 = BASELINE config 4 (chignolin: xyz -> 45 C-alpha distances on the device every
 step -> k = 200 in the feature space -> lag scan 1..50 in one pass and one collective); c5 / c5t = BASELINE
 config 5 per GPU (1.25 M x 256 float32, k = 2000; clustering in the raw 256-d space / after TICA -> 10).
-Extra legs at N = 1 (reported beside the headline, never as it): the featurizer alone and in front of the c3
-chain, the operator API from host arrays, k-means quality against the CPU baseline, per-stage times.
+
+A plain run sets up, warms up, times the steps, writes the last step's outputs (--dump-outputs DIR) and prints the
+result line.  Everything else runs only with --full: the roofline and per-stage times (HIP events inside the timed
+steps), the parity of the run against the CPU oracle, the from-host pass, per-kernel rooflines, the CPU baselines
+and, at N = 1, the extra legs (reported beside the headline, never as it): the featurizer alone and in front of the c3
+chain, the operator API from host arrays, k-means quality against the CPU baseline.
 """
 
 from __future__ import annotations
@@ -283,6 +287,29 @@ def operator_api_leg(X: np.ndarray, c: dict) -> dict:
     return out
 
 
+DUMP_MAX_ELEMS = 1 << 20      # 8 MB of float64 per array: the at most six arrays stay under 64 MB
+
+
+def dump_outputs(out_dir: Path, msm, c: dict) -> None:
+    """What the last timed step hands its caller, as DIR/<name>.npy in float64 (this rank's shard for the per-frame
+    arrays).  An array of more than DUMP_MAX_ELEMS elements keeps a fixed, seeded sample of its rows, in row order."""
+    k, d = c["k"], msm.cfg.tica_dim
+    L = len(c["lags"]) if c.get("lags") else 1
+    arrays = {"centers": msm.buf["centers"], "labels": msm.labels,
+              "counts": msm.buf["counts"].view((L, k, k) if c.get("lags") else (k, k)),
+              "counted_pairs": msm.buf["counts"].view((L,), offset_elems=L * k * k), "transition_matrix": msm.T}
+    if d:
+        arrays["tica_eigenvalues"] = msm.eig.view((d,))
+        arrays["projected"] = msm.Y
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, dev in arrays.items():
+        a = dev.to_host().astype(np.float64)
+        if a.size > DUMP_MAX_ELEMS:
+            rows = np.random.default_rng(0).choice(a.shape[0], DUMP_MAX_ELEMS * a.shape[0] // a.size, replace=False)
+            a = a[np.sort(rows)]
+        np.save(out_dir / f"{name}.npy", a)
+
+
 def spawn_ranks(n_ranks: int, argv: list[str]) -> int:
     """`bench.py --gpus N` without a launcher: start N rank processes of this script (RANK / LOCAL_RANK / WORLD_SIZE /
     MASTER_* as torch.distributed.run sets them, one GPU each), relay rank 0's stdout, return non-zero if any rank
@@ -350,10 +377,17 @@ def main() -> None:
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", choices=sorted(CONFIGS), default="c3")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip the featurizer / operator-API / quality legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline, per-stage times, oracle parity, from-host pass, CPU baselines and extra legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extra-legs", action="store_true",
+                    help="with --full: skip the per-kernel / featurizer / operator-API / quality legs")
     ap.add_argument("--frames", type=int, default=0, help="frames per GPU (default: the config's)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
@@ -431,11 +465,13 @@ def main() -> None:
     for _ in range(max(0, args.warmup)):
         msm.step()
     barrier()
-    msm.time_accum = True
-    msm.time_stages = True
-    if multi and hasattr(comm, "events"):
-        comm.events.clear()
-        comm.timing = True
+    if args.full:
+        # HIP events inside the timed steps: per-stage times, the k-means pass of the roofline, the exchange times
+        msm.time_accum = True
+        msm.time_stages = True
+        if multi and hasattr(comm, "events"):
+            comm.events.clear()
+            comm.timing = True
     n_coll0 = comm.n_collectives if multi else 0
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -445,7 +481,7 @@ def main() -> None:
     msm.time_accum = False
     msm.time_stages = False
     exchange_ms = None
-    if multi and hasattr(comm, "events"):
+    if args.full and multi and hasattr(comm, "events"):
         comm.timing = False
         # device time between HIP events around the collectives of each exchange buffer, per step (the barrier's own
         # "timing" collective is outside the timed steps)
@@ -458,57 +494,60 @@ def main() -> None:
         comm.allreduce_max("timing")
         eng.sync()
         elapsed = float(shared["timing"].to_host()[0])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(Path(args.dump_outputs), msm, c)
 
-    # ---- per-stage device times (HIP events on the engine's stream, inside the timed steps)
-    names = [s for s in ("begin", "featurize", "moments", "tica_solve", "project", "kmeans", "counts") if s in msm.stage_events]
-    stages = {}
-    for a, b_ in zip(names[:-1], names[1:]):
-        stages[b_] = float(np.mean([x.elapsed_ms(y) for x, y in zip(msm.stage_events[a], msm.stage_events[b_])]))
+    if args.full:
+        # ---- per-stage device times (HIP events on the engine's stream, inside the timed steps)
+        names = [s for s in ("begin", "featurize", "moments", "tica_solve", "project", "kmeans", "counts") if s in msm.stage_events]
+        stages = {}
+        for a, b_ in zip(names[:-1], names[1:]):
+            stages[b_] = float(np.mean([x.elapsed_ms(y) for x, y in zip(msm.stage_events[a], msm.stage_events[b_])]))
 
-    # dominant kernel: the k-means assign + accumulate pass, measured with HIP events on the engine's stream
-    acc_ms = [a.elapsed_ms(b) for a, b in msm.accum_events]
-    acc_ms_avg = float(np.mean(acc_ms)) if acc_ms else float("nan")
-    dc = cfg.cluster_dim
-    flops_per_launch = 2.0 * k * dc * n            # 2 k d per frame
-    filtered = msm.km_image is not None
-    if filtered:
-        # the pass issues bf16 matrix instructions (an exact filter, labels bit-identical to the fp64 chain): the roof it
-        # runs under is the bf16 matrix peak for the instructions it executes, with the HBM fraction beside it
-        nm = 1 if 6 * dc + 4 <= 32 else 2
-        tiles = ((((k + 15) // 16) + 1) // 2) * 2
-        exec_flops = float(-(-n // 16)) * tiles * nm * 16384.0      # bf16 16x16x32 instructions issued x 16384 flop
-        img_b = eng.kmeans_image_bytes(n, dc) / n
-        alg_bytes = float((img_b + dc * msm.Y.dtype.itemsize + 8) * n)    # frame images + coordinates + the label in and out
-        achieved_tf = exec_flops / (acc_ms_avg * 1e-3) / 1e12
-        roofline = {
-            "bound": "mfma", "achieved": achieved_tf, "peak": BF16_MFMA_PEAK_TF, "unit": "TFLOP/s",
-            "frac": achieved_tf / BF16_MFMA_PEAK_TF, "traffic": None, "dtype_executed": "bf16",
-            "kernel": "kmeans_filter_kernel<double,2,4,true,false> (assign + accumulate: bf16x3 matrix-core filter, fp32 "
-                      "candidate pick, fp64 only for frames without a certificate)",
-            "launch_ms": acc_ms_avg, "launches_timed": len(acc_ms), "executed_flops_per_launch": exec_flops,
-            "algorithmic_flops_per_launch": flops_per_launch, "algorithmic_bytes_per_launch": alg_bytes,
-            "hbm": {"achieved": alg_bytes / (acc_ms_avg * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": alg_bytes / (acc_ms_avg * 1e-3) / 1e9 / HBM_PEAK_GBS},
-            "speedup_vs_fp64_bound": flops_per_launch / (acc_ms_avg * 1e-3) / 1e12 / FP64_MFMA_PEAK_TF,
-            "note": "achieved / peak / frac: bf16 matrix work EXECUTED per launch / launch time against the dense bf16 peak. "
-                    "speedup_vs_fp64_bound: the algorithmic 2 k d flop per frame / launch time over the fp64 matrix peak an "
-                    "all-fp64 pass is bounded by -- what the exact filter buys, not a fraction of any roof."}
-    else:
-        achieved_tf = flops_per_launch / (acc_ms_avg * 1e-3) / 1e12
-        roofline = {"bound": "mfma", "achieved": achieved_tf, "peak": FP64_MFMA_PEAK_TF, "unit": "TFLOP/s",
-                    "frac": achieved_tf / FP64_MFMA_PEAK_TF, "traffic": None,
-                    "kernel": "kmeans_mfma_kernel (assign + accumulate, fp64 MFMA)", "launch_ms": acc_ms_avg,
-                    "launches_timed": len(acc_ms), "algorithmic_flops_per_launch": flops_per_launch}
-    prof = ROOT / "profiles" / "r03_pmc_hbm.json"
-    if prof.exists() and args.config == "c3" and n == CONFIGS["c3"]["n"]:
-        try:
-            pj = json.loads(prof.read_text())
-            if pj.get("kernel_prefix", "x") in roofline["kernel"]:
-                roofline["traffic"] = pj.get("bytes_per_launch")
-                roofline["traffic_unit"] = ("bytes per launch, rocprofv3 PMC of an earlier run of this command kept in "
-                                            "profiles/r03_pmc_hbm.md (not re-measured by this run)")
-        except Exception:
-            pass
+        # dominant kernel: the k-means assign + accumulate pass, measured with HIP events on the engine's stream
+        acc_ms = [a.elapsed_ms(b) for a, b in msm.accum_events]
+        acc_ms_avg = float(np.mean(acc_ms)) if acc_ms else float("nan")
+        dc = cfg.cluster_dim
+        flops_per_launch = 2.0 * k * dc * n            # 2 k d per frame
+        filtered = msm.km_image is not None
+        if filtered:
+            # the pass issues bf16 matrix instructions (an exact filter, labels bit-identical to the fp64 chain): the roof it
+            # runs under is the bf16 matrix peak for the instructions it executes, with the HBM fraction beside it
+            nm = 1 if 6 * dc + 4 <= 32 else 2
+            tiles = ((((k + 15) // 16) + 1) // 2) * 2
+            exec_flops = float(-(-n // 16)) * tiles * nm * 16384.0      # bf16 16x16x32 instructions issued x 16384 flop
+            img_b = eng.kmeans_image_bytes(n, dc) / n
+            alg_bytes = float((img_b + dc * msm.Y.dtype.itemsize + 8) * n)    # frame images + coordinates + the label in and out
+            achieved_tf = exec_flops / (acc_ms_avg * 1e-3) / 1e12
+            roofline = {
+                "bound": "mfma", "achieved": achieved_tf, "peak": BF16_MFMA_PEAK_TF, "unit": "TFLOP/s",
+                "frac": achieved_tf / BF16_MFMA_PEAK_TF, "traffic": None, "dtype_executed": "bf16",
+                "kernel": "kmeans_filter_kernel<double,2,4,true,false> (assign + accumulate: bf16x3 matrix-core filter, fp32 "
+                          "candidate pick, fp64 only for frames without a certificate)",
+                "launch_ms": acc_ms_avg, "launches_timed": len(acc_ms), "executed_flops_per_launch": exec_flops,
+                "algorithmic_flops_per_launch": flops_per_launch, "algorithmic_bytes_per_launch": alg_bytes,
+                "hbm": {"achieved": alg_bytes / (acc_ms_avg * 1e-3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": alg_bytes / (acc_ms_avg * 1e-3) / 1e9 / HBM_PEAK_GBS},
+                "speedup_vs_fp64_bound": flops_per_launch / (acc_ms_avg * 1e-3) / 1e12 / FP64_MFMA_PEAK_TF,
+                "note": "achieved / peak / frac: bf16 matrix work EXECUTED per launch / launch time against the dense bf16 peak. "
+                        "speedup_vs_fp64_bound: the algorithmic 2 k d flop per frame / launch time over the fp64 matrix peak an "
+                        "all-fp64 pass is bounded by -- what the exact filter buys, not a fraction of any roof."}
+        else:
+            achieved_tf = flops_per_launch / (acc_ms_avg * 1e-3) / 1e12
+            roofline = {"bound": "mfma", "achieved": achieved_tf, "peak": FP64_MFMA_PEAK_TF, "unit": "TFLOP/s",
+                        "frac": achieved_tf / FP64_MFMA_PEAK_TF, "traffic": None,
+                        "kernel": "kmeans_mfma_kernel (assign + accumulate, fp64 MFMA)", "launch_ms": acc_ms_avg,
+                        "launches_timed": len(acc_ms), "algorithmic_flops_per_launch": flops_per_launch}
+        prof = ROOT / "profiles" / "r03_pmc_hbm.json"
+        if prof.exists() and args.config == "c3" and n == CONFIGS["c3"]["n"]:
+            try:
+                pj = json.loads(prof.read_text())
+                if pj.get("kernel_prefix", "x") in roofline["kernel"]:
+                    roofline["traffic"] = pj.get("bytes_per_launch")
+                    roofline["traffic_unit"] = ("bytes per launch, rocprofv3 PMC of an earlier run of this command kept in "
+                                                "profiles/r03_pmc_hbm.md (not re-measured by this run)")
+            except Exception:
+                pass
 
     if rank == 0:
         total_frames = float(n) * world * args.steps
@@ -535,131 +574,132 @@ def main() -> None:
                        "exchange": ({"rccl": "rccl (C ABI)", "torch": "torch.distributed " + os.environ.get("BENCH_BACKEND", "nccl")}
                                     [comm_kind] if multi else None),
                        "collectives_per_step": (n_coll / args.steps if multi else 0)},
-            "roofline": roofline,
-            "stages_ms": stages,
         }
-        if exchange_ms is not None:
-            out["exchange_ms"] = exchange_ms
-            out["config"]["exchange_note"] = ("RCCL defaults (no scaling curve has been measured for this path yet: the pool "
-                                              "offers one GPU per box)")
-        # ---- parity of this very run against the CPU oracle (outside the timed region) ----
-        parity = {}
-        try:
-            from oracle import cport, npport
+        if args.full:
+            out["roofline"] = roofline
+            out["stages_ms"] = stages
+            if exchange_ms is not None:
+                out["exchange_ms"] = exchange_ms
+                out["config"]["exchange_note"] = ("RCCL defaults (no scaling curve has been measured for this path "
+                                                  "yet)")
+            # ---- parity of this very run against the CPU oracle (outside the timed region) ----
+            parity = {}
+            try:
+                from oracle import cport, npport
 
-            L = len(c["lags"]) if c.get("lags") else 1
-            li = list(c["lags"]).index(lag) if c.get("lags") and lag in c["lags"] else 0
-            counts_all = msm.buf["counts"].view((L, k, k)).to_host()
-            pairs_all = msm.buf["counts"].view((L,), offset_elems=L * k * k).to_host()
-            counts = counts_all[li]
-            labels = msm.labels.to_host()
-            centers = msm.buf["centers"].to_host()
-            nchk = min(n, 250_000)      # the oracle's assignment is a scalar loop: a quarter of a million frames
-            Yh = (msm.Y.view((nchk, dc)) if True else msm.Y).to_host().astype(np.float64)
-            parity["labels_bit_exact_given_centres"] = bool(np.array_equal(labels[:nchk], cport.kmeans_assign(Yh, centers)))
-            parity["labels_checked"] = nchk
-            if world == 1:
-                ok = True
-                for i in range(L):
-                    want, pw = cport.count_transitions(labels, k, int(c["lags"][i]) if c.get("lags") else lag)
-                    ok = ok and bool(np.array_equal(counts_all[i], want)) and int(pairs_all[i]) == pw
-                parity["counts_bit_exact"] = ok
-            tm = eng.transition_matrix(eng.to_device(counts), mode=1)
-            spec = eng.spectrum(tm["T"], n=tm["n_active"], n_its=5, lags=[float(c["lags"][li] if c.get("lags") else lag)],
-                                allow_unconverged=True)
-            ev_ref, ts_ref = npport.its_from_counts(counts, int(c["lags"][li] if c.get("lags") else lag), 5)
-            okm = np.isfinite(ts_ref)
-            parity["its_rel_err"] = float(np.max(np.abs(spec["its_ts"][0][okm] - ts_ref[okm]) / ts_ref[okm]))
-            parity["its_timescales_frames"] = spec["its_ts"][0].tolist()
-            parity["its_residual"] = float(spec["residual"][0])
-            if d:
-                parity["tica_eigenvalues"] = msm.eig.to_host()[:d].tolist()
-                parity["tica_rank"] = int(msm.rank_d.to_host()[0])
-            if filtered:
-                parity["kmeans_filter_scanned_frames_per_pass"] = eng.kmeans_filter_scanned() / max(
-                    1, (args.steps + args.warmup) * (iters + 1))
-            if d and multi and n * world <= 2_000_000:
-                # rank 0 regenerates every shard (seeded) and checks the all-reduced TICA against the
-                # oracle on the list of shards (pairs never cross a shard)
-                allx = npport.preprocess(np.vstack([_gen.correlated_series(n, F, seed=1000 + r) for r in range(world)]),
-                                         scale=True)
-                ref = npport.tica_fit([allx[r * n:(r + 1) * n] for r in range(world)], lag, dim=d)
-                got = np.asarray(parity["tica_eigenvalues"])
-                m = min(2 * world, d)  # the resolved slow modes (2 per independently mixed shard)
-                parity["tica_eig_rel_err"] = float(np.max(np.abs(got[:m] - ref["eigenvalues"][:m])
-                                                          / np.abs(ref["eigenvalues"][:m])))
-                parity["tica_rank_oracle"] = int(ref["rank"])
-        except Exception as exc:  # parity reporting must not hide the throughput line
-            parity["error"] = repr(exc)
-        out["parity"] = parity
+                L = len(c["lags"]) if c.get("lags") else 1
+                li = list(c["lags"]).index(lag) if c.get("lags") and lag in c["lags"] else 0
+                counts_all = msm.buf["counts"].view((L, k, k)).to_host()
+                pairs_all = msm.buf["counts"].view((L,), offset_elems=L * k * k).to_host()
+                counts = counts_all[li]
+                labels = msm.labels.to_host()
+                centers = msm.buf["centers"].to_host()
+                nchk = min(n, 250_000)      # the oracle's assignment is a scalar loop: a quarter of a million frames
+                Yh = (msm.Y.view((nchk, dc)) if True else msm.Y).to_host().astype(np.float64)
+                parity["labels_bit_exact_given_centres"] = bool(np.array_equal(labels[:nchk], cport.kmeans_assign(Yh, centers)))
+                parity["labels_checked"] = nchk
+                if world == 1:
+                    ok = True
+                    for i in range(L):
+                        want, pw = cport.count_transitions(labels, k, int(c["lags"][i]) if c.get("lags") else lag)
+                        ok = ok and bool(np.array_equal(counts_all[i], want)) and int(pairs_all[i]) == pw
+                    parity["counts_bit_exact"] = ok
+                tm = eng.transition_matrix(eng.to_device(counts), mode=1)
+                spec = eng.spectrum(tm["T"], n=tm["n_active"], n_its=5, lags=[float(c["lags"][li] if c.get("lags") else lag)],
+                                    allow_unconverged=True)
+                ev_ref, ts_ref = npport.its_from_counts(counts, int(c["lags"][li] if c.get("lags") else lag), 5)
+                okm = np.isfinite(ts_ref)
+                parity["its_rel_err"] = float(np.max(np.abs(spec["its_ts"][0][okm] - ts_ref[okm]) / ts_ref[okm]))
+                parity["its_timescales_frames"] = spec["its_ts"][0].tolist()
+                parity["its_residual"] = float(spec["residual"][0])
+                if d:
+                    parity["tica_eigenvalues"] = msm.eig.to_host()[:d].tolist()
+                    parity["tica_rank"] = int(msm.rank_d.to_host()[0])
+                if filtered:
+                    parity["kmeans_filter_scanned_frames_per_pass"] = eng.kmeans_filter_scanned() / max(
+                        1, (args.steps + args.warmup) * (iters + 1))
+                if d and multi and n * world <= 2_000_000:
+                    # rank 0 regenerates every shard (seeded) and checks the all-reduced TICA against the
+                    # oracle on the list of shards (pairs never cross a shard)
+                    allx = npport.preprocess(np.vstack([_gen.correlated_series(n, F, seed=1000 + r) for r in range(world)]),
+                                             scale=True)
+                    ref = npport.tica_fit([allx[r * n:(r + 1) * n] for r in range(world)], lag, dim=d)
+                    got = np.asarray(parity["tica_eigenvalues"])
+                    m = min(2 * world, d)  # the resolved slow modes (2 per independently mixed shard)
+                    parity["tica_eig_rel_err"] = float(np.max(np.abs(got[:m] - ref["eigenvalues"][:m])
+                                                              / np.abs(ref["eigenvalues"][:m])))
+                    parity["tica_rank_oracle"] = int(ref["rank"])
+            except Exception as exc:  # parity reporting must not hide the throughput line
+                parity["error"] = repr(exc)
+            out["parity"] = parity
 
-        extra = (not multi) and (not args.no_extra_legs) and args.config == "c3" and X is not None
-        # from-host pass: the same step with the shard uploaded from pageable host
-        # memory inside the clock -- reported beside `value`, never as it
-        if not multi and X is not None:
-            eng.sync()
-            t1 = time.perf_counter()
-            xd2 = eng.to_device(X)
-            eng.sync()
-            h2d = time.perf_counter() - t1
-            msm.x = xd2
-            msm.step()
-            eng.sync()
-            tot = time.perf_counter() - t1
-            msm.x = xd
-            del xd2
-            out["from_host"] = {"value": n / tot, "unit": "frames/s", "h2d_ms": h2d * 1e3, "step_ms": (tot - h2d) * 1e3,
-                                "h2d_GBps": X.nbytes / h2d / 1e9, "note": "one pageable-memory upload + one step"}
-        if not multi and not args.no_extra_legs and X is not None:
-            try:
-                roofline["kernels"] = kernel_rooflines(eng, msm, c, n, acc_ms_avg)
-            except Exception as exc:
-                roofline["kernels"] = [{"error": repr(exc)}]
-        if not multi and not args.no_cpu_baseline and X is not None and d:
-            cb = cpu_baseline(X, c)
-            ref_eig = np.asarray(cb.pop("tica_eigenvalues"))
-            Yz = cb.pop("_Yz")
-            got = np.asarray(parity.get("tica_eigenvalues", ref_eig))
-            out["parity"]["tica_eig_rel_err"] = float(np.max(np.abs(got - ref_eig) / np.abs(ref_eig)))
-            out["cpu_baseline"] = cb
-            from threadpoolctl import threadpool_limits
+            extra = (not multi) and (not args.no_extra_legs) and args.config == "c3" and X is not None
+            # from-host pass: the same step with the shard uploaded from pageable host
+            # memory inside the clock -- reported beside `value`, never as it
+            if not multi and X is not None:
+                eng.sync()
+                t1 = time.perf_counter()
+                xd2 = eng.to_device(X)
+                eng.sync()
+                h2d = time.perf_counter() - t1
+                msm.x = xd2
+                msm.step()
+                eng.sync()
+                tot = time.perf_counter() - t1
+                msm.x = xd
+                del xd2
+                out["from_host"] = {"value": n / tot, "unit": "frames/s", "h2d_ms": h2d * 1e3, "step_ms": (tot - h2d) * 1e3,
+                                    "h2d_GBps": X.nbytes / h2d / 1e9, "note": "one pageable-memory upload + one step"}
+            if not multi and not args.no_extra_legs and X is not None:
+                try:
+                    roofline["kernels"] = kernel_rooflines(eng, msm, c, n, acc_ms_avg)
+                except Exception as exc:
+                    roofline["kernels"] = [{"error": repr(exc)}]
+            if not multi and not args.no_cpu_baseline and X is not None and d:
+                cb = cpu_baseline(X, c)
+                ref_eig = np.asarray(cb.pop("tica_eigenvalues"))
+                Yz = cb.pop("_Yz")
+                got = np.asarray(parity.get("tica_eigenvalues", ref_eig))
+                out["parity"]["tica_eig_rel_err"] = float(np.max(np.abs(got - ref_eig) / np.abs(ref_eig)))
+                out["cpu_baseline"] = cb
+                from threadpoolctl import threadpool_limits
 
-            with threadpool_limits(limits=1):
-                cb1 = cpu_baseline(X, c)
-            for key in ("tica_eigenvalues", "_Yz", "threadpool_info"):
-                cb1.pop(key, None)
-            cb1["cores"] = 1
-            out["cpu_baseline_1thread"] = cb1
-            # what the fast k-means buys: the device's 10 Lloyd iterations and the CPU branch (MiniBatchKMeans) on
-            # the SAME whitened coordinates, inertia = sum of squared distances to the assigned centre
-            try:
-                yz = eng.to_device(np.ascontiguousarray(Yz))
-                cen, st = eng.kmeans_fit(yz, k, seed=0, max_iter=iters, tol2=0.0)
-                md = eng.empty((n,), np.float64)
-                eng.kmeans_assign(yz, cen, mindist=md)
-                dev_inertia = float(eng.sum_f64(md).to_host()[0])
-                cen100, _ = eng.kmeans_fit(yz, k, seed=0, max_iter=100, tol2=1e-4 * dc)
-                eng.kmeans_assign(yz, cen100, mindist=md)
-                out["kmeans_quality"] = {
-                    "space": "TICA coordinates whitened as the reference's discretizer does (z-score, ddof = 1)",
-                    "inertia_device_10_lloyd": dev_inertia,
-                    "inertia_device_to_tolerance": float(eng.sum_f64(md).to_host()[0]),
-                    "inertia_cpu_baseline_minibatch": cb["inertia_whitened"],
-                    "ratio_device_over_cpu": dev_inertia / cb["inertia_whitened"]}
-                del yz, md
-            except Exception as exc:
-                out["kmeans_quality"] = {"error": repr(exc)}
-        elif rank == 0:
-            out["cpu_baseline"] = None
-        if extra:
-            try:
-                out["featurize"] = featurize_legs(eng, c)
-            except Exception as exc:
-                out["featurize"] = {"error": repr(exc)}
-            try:
-                out["operator_api"] = operator_api_leg(X, c)
-            except Exception as exc:
-                out["operator_api"] = {"error": repr(exc)}
+                with threadpool_limits(limits=1):
+                    cb1 = cpu_baseline(X, c)
+                for key in ("tica_eigenvalues", "_Yz", "threadpool_info"):
+                    cb1.pop(key, None)
+                cb1["cores"] = 1
+                out["cpu_baseline_1thread"] = cb1
+                # what the fast k-means buys: the device's 10 Lloyd iterations and the CPU branch (MiniBatchKMeans) on
+                # the SAME whitened coordinates, inertia = sum of squared distances to the assigned centre
+                try:
+                    yz = eng.to_device(np.ascontiguousarray(Yz))
+                    cen, st = eng.kmeans_fit(yz, k, seed=0, max_iter=iters, tol2=0.0)
+                    md = eng.empty((n,), np.float64)
+                    eng.kmeans_assign(yz, cen, mindist=md)
+                    dev_inertia = float(eng.sum_f64(md).to_host()[0])
+                    cen100, _ = eng.kmeans_fit(yz, k, seed=0, max_iter=100, tol2=1e-4 * dc)
+                    eng.kmeans_assign(yz, cen100, mindist=md)
+                    out["kmeans_quality"] = {
+                        "space": "TICA coordinates whitened as the reference's discretizer does (z-score, ddof = 1)",
+                        "inertia_device_10_lloyd": dev_inertia,
+                        "inertia_device_to_tolerance": float(eng.sum_f64(md).to_host()[0]),
+                        "inertia_cpu_baseline_minibatch": cb["inertia_whitened"],
+                        "ratio_device_over_cpu": dev_inertia / cb["inertia_whitened"]}
+                    del yz, md
+                except Exception as exc:
+                    out["kmeans_quality"] = {"error": repr(exc)}
+            elif rank == 0:
+                out["cpu_baseline"] = None
+            if extra:
+                try:
+                    out["featurize"] = featurize_legs(eng, c)
+                except Exception as exc:
+                    out["featurize"] = {"error": repr(exc)}
+                try:
+                    out["operator_api"] = operator_api_leg(X, c)
+                except Exception as exc:
+                    out["operator_api"] = {"error": repr(exc)}
         print(json.dumps(out), flush=True)
     if multi:
         barrier()
@@ -667,7 +707,6 @@ def main() -> None:
             dist.destroy_process_group()
         else:
             comm.close()
-
 
 if __name__ == "__main__":
     main()

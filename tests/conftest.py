@@ -2,6 +2,7 @@
 
 from __future__ import annotations
 
+import subprocess
 import sys
 from pathlib import Path
 
@@ -25,6 +26,16 @@ def golden():
         return np.load(GOLDEN / name, allow_pickle=False)
 
     return _load
+
+
+@pytest.fixture(scope="session")
+def gpu_present() -> bool:
+    """Whether torch sees a GPU, asked in a child process: torch ships its own HIP runtime, and bringing it up in the
+    test process next to the one the engine's library links leaves every later Engine(0) of the session failing."""
+    r = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.is_available())"], capture_output=True,
+                       text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    return r.stdout.split()[-1] == "True"
 
 
 @pytest.fixture(scope="session")

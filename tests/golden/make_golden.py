@@ -700,7 +700,52 @@ def golden_real_assets():
             bytes.fromhex(sha(res_index.astype(np.int64))), np.uint8))
 
 
+# the names the engine's feature objects carry (pmarlo_amd/features/builtins.py) and the specs a user would write
+REGISTRY_NAMES = ["phi_psi", "chi1", "distance", "angle", "dihedral", "Rg", "distance_pair", "contacts_pair", "sasa",
+                  "hbonds_count", "ssfrac"]
+REGISTRY_SPECS = ["phi_psi", "Rg", "chi1", "dist:AtomPair(3, 17)", "contacts:Pair(1, 2)", "contacts:Pair(1, 2, 0.8)",
+                  "sasa:all", "hbonds:x", "ssfrac:x", "distance([0, 5])", "angle([0, 1, 2])", "dihedral([0, 1, 2, 3])"]
+
+
+def golden_registry():
+    """pmarlo.features.base as the engine's adapter meets it: the key register_feature stores each engine name under,
+    the key get_feature resolves each spelling of it to, and what parse_feature_spec makes of each spec."""
+    import pmarlo.features.base as ref_base
+
+    saved = dict(ref_base.FEATURE_REGISTRY)
+    ref_base.FEATURE_REGISTRY.clear()
+    try:
+        stubs = {}
+        for name in REGISTRY_NAMES:
+            stubs[name] = SimpleNamespace(name=name)
+            ref_base.register_feature(stubs[name])
+        by_id = {id(v): k for k, v in ref_base.FEATURE_REGISTRY.items()}
+        register_keys = {name: by_id[id(stubs[name])] for name in REGISTRY_NAMES}
+        lookup_keys = {}
+        for name in REGISTRY_NAMES:
+            for spelling in (name, name.upper(), name.lower()):
+                lookup_keys[spelling] = by_id[id(ref_base.get_feature(spelling))]
+        # last registration wins: a second object under an existing name (any case) replaces the first
+        first, second = SimpleNamespace(name="rg"), SimpleNamespace(name="RG")
+        ref_base.register_feature(first)
+        ref_base.register_feature(second)
+        last_wins = ref_base.get_feature("Rg") is second
+        try:
+            ref_base.get_feature("not_a_feature")
+            unknown_raises = False
+        except KeyError:
+            unknown_raises = True
+        parse = [[spec, *ref_base.parse_feature_spec(spec)] for spec in REGISTRY_SPECS]
+    finally:
+        ref_base.FEATURE_REGISTRY.clear()
+        ref_base.FEATURE_REGISTRY.update(saved)
+    (OUT / "registry.json").write_text(json.dumps(
+        {"register_keys": register_keys, "lookup_keys": lookup_keys, "last_registration_wins": last_wins,
+         "unknown_name_raises_key_error": unknown_raises, "parse_feature_spec": parse}, indent=1) + "\n")
+
+
 if __name__ == "__main__":
+    golden_registry()
     golden_real_assets()
     golden_whitening()
     golden_fes_smoothing()

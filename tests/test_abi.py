@@ -44,11 +44,9 @@ def test_python_binding_covers_the_header():
     assert lib.msm_version().startswith(b"msmhip")
 
 
-def test_missing_gpu_fails_loudly():
+def test_missing_gpu_fails_loudly(gpu_present):
     """Without a HIP device the engine must raise, never fall back."""
-    import torch
-
-    if torch.cuda.is_available():
+    if gpu_present:
         pytest.skip("GPU present")
     from pmarlo_amd._lib import MsmError
     from pmarlo_amd.device import Engine

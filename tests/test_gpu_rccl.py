@@ -28,7 +28,7 @@ def _launch(nproc: int, extra_env: dict, args: list[str]) -> dict:
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0", **extra_env)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc),
            "--master-addr", "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", str(nproc), "--steps", "2",
-           "--warmup", "1", "--no-cpu-baseline", "--no-extra-legs"] + args
+           "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extra-legs"] + args
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]

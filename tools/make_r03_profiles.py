@@ -10,7 +10,7 @@ from pathlib import Path
 
 ROOT = Path(__file__).resolve().parents[1]
 P = ROOT / "profiles"
-CMD = "rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extra-legs"
+CMD = "rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-extra-legs"
 
 
 def main():
@@ -34,7 +34,7 @@ def main():
     u = {n: util(names[n]) for n in ("kmeans_filter_kernel", "cov_fused_kernel", "project_mfma_kernel") if n in names}
     head = ["# Round 3: PMC counters of the bench step (per launch means), end of round", "",
             "Command per counter set (`tools/run/prof_r03.sh`; counters only ever with `--kernel-trace`): `rocprofv3 --pmc <set> "
-            "--kernel-trace --output-format csv -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extra-legs`.",
+            "--kernel-trace --output-format csv -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extra-legs`.",
             "Sets: FETCH_SIZE | WRITE_SIZE | SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VALU "
             "SQ_ACTIVE_INST_LDS GRBM_GUI_ACTIVE | SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_ANY SQ_WAIT_INST_ANY "
             "SQ_ACTIVE_INST_ANY SQ_INSTS_VALU_MFMA_MOPS_* SQ_VALU_MFMA_COEXEC_CYCLES.",
@@ -51,7 +51,7 @@ def main():
             for k, v in d.items() if v.get("FETCH_SIZE") is not None and v.get("WRITE_SIZE") is not None]
     out = ["# Round 3: HBM-side traffic per launch (PMC), end of round", "",
            "Command (two passes, FETCH_SIZE needs 3 TCC slots and WRITE_SIZE 2): `rocprofv3 --pmc FETCH_SIZE --kernel-trace "
-           "--output-format csv -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extra-legs`, then the same with "
+           "--output-format csv -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extra-legs`, then the same with "
            "`--pmc WRITE_SIZE` (`tools/run/prof_r03.sh`).", "",
            "Counters are in KiB.  Correction per `MI355X_MICROARCH.md` (HBM section), calibrated in round 1 (`r01_pmc_hbm.md`): on "
            "gfx950 FETCH_SIZE tallies 128-B read requests at 64 B, so reads = 2 x FETCH_SIZE; WRITE_SIZE is taken as is.  "

@@ -1,7 +1,10 @@
 #!/bin/bash
-# GPU box: rocprofv3 kernel trace of the bench (outputs under gpurun_out/prof)
-mkdir -p gpurun_out && cd /tmp && export TMPDIR=/tmp
-rm -rf $GRAFT_REPO_ROOT/gpurun_out/prof
-rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/gpurun_out/prof -- python3 $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 2 --no-cpu-baseline > $GRAFT_REPO_ROOT/gpurun_out/prof_bench.log 2>&1
-tail -1 $GRAFT_REPO_ROOT/gpurun_out/prof_bench.log | cut -c1-300
-find $GRAFT_REPO_ROOT/gpurun_out/prof -name "*kernel_stats.csv" | head
+# GPU box: rocprofv3 kernel trace of the bench (outputs under $OUT/prof)
+R=$(cd "$(dirname "$0")/../.." && pwd)
+OUT=${OUT:-$R/out}          # where logs and traces go
+export OUT
+mkdir -p $OUT && cd /tmp && export TMPDIR=/tmp
+rm -rf $OUT/prof
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -- python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > $OUT/prof_bench.log 2>&1
+tail -1 $OUT/prof_bench.log | cut -c1-300
+find $OUT/prof -name "*kernel_stats.csv" | head
