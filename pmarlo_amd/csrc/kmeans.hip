@@ -902,7 +902,26 @@ __global__ void mfma_bf16_probe_kernel(const uint16_t* __restrict__ A, const uin
     for (int r = 0; r < 4; ++r) D[(4 * q + r) * 16 + i] = c[r];
 }
 
-// ---- certified bf16 filter path (kmeans_filter.h): d <= 10 and centres + images fit the LDS -------------
+// the same with one v_mfma_f32_16x16x32_f16 (msm_mfma_f16_probe): the instruction of the fp16 filter
+__global__ void mfma_f16_probe_kernel(const uint16_t* __restrict__ A, const uint16_t* __restrict__ B,
+                                      const float* __restrict__ C, float* __restrict__ D) {
+    const int l = threadIdx.x, i = l & 15, q = l >> 4;
+    A += (size_t)blockIdx.x * 512;
+    B += (size_t)blockIdx.x * 512;
+    C += (size_t)blockIdx.x * 256;
+    D += (size_t)blockIdx.x * 256;
+    v8h a, b;
+    for (int j = 0; j < 8; ++j) {
+        a[j] = __builtin_bit_cast(_Float16, A[i * 32 + 8 * q + j]);
+        b[j] = __builtin_bit_cast(_Float16, B[(8 * q + j) * 16 + i]);
+    }
+    v4f32 c;
+    for (int r = 0; r < 4; ++r) c[r] = C[(4 * q + r) * 16 + i];
+    c = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+    for (int r = 0; r < 4; ++r) D[(4 * q + r) * 16 + i] = c[r];
+}
+
+// ---- certified fp16 filter path (kmeans_filter.h): d <= 10 and centres + images fit the LDS -------------
 bool filter_enabled() {
     static const bool on = [] {
         const char* e = getenv("MSM_KMEANS_FILTER");   // MSM_KMEANS_FILTER=0: all-fp64 kernel everywhere (A/B timing)
@@ -911,18 +930,28 @@ bool filter_enabled() {
     return on;
 }
 
-// whole units of 64 rows (the filter kernel loads a unit without clamping)
-size_t filter_image_bytes(int64_t n, int d) { return (size_t)((n + 63) & ~(int64_t)63) * 16 * filter_rowq(filter_nm(d)); }
+// whole units of 64 rows (the filter kernel loads a unit without clamping), then one uint4: [max |x| bound | e_x | pad]
+size_t filter_image_bytes(int64_t n, int) { return (size_t)((n + 63) & ~(int64_t)63) * 16 * kFilterRowQ + 16; }
 
+// absmax: device pointer to a bound >= max |x| (whitened), or NULL: a pass of its own into the image's last word
 template <typename T>
 msm_status launch_pack(msm_ctx* ctx, const T* x, int64_t n, int d, int64_t ld, const double* mean, const double* stdv,
-                       uint4* image) {
+                       const double* absmax, uint4* image) {
     const unsigned grid = (unsigned)((n + 255) / 256);
+    if (!absmax) {
+        uint4* tail = image + (size_t)((n + 63) & ~(int64_t)63) * kFilterRowQ;
+        MSM_HIP(ctx, hipMemsetAsync(tail, 0, 8, ctx->stream));
+        const int g = (int)std::min<int64_t>((n * d + 256 * 8 - 1) / (256 * 8), (int64_t)ctx->n_cu * 8);
+        hipLaunchKernelGGL(filter_absmax_kernel<T>, dim3(g), dim3(256), 0, ctx->stream, x, n, d, ld, mean, stdv,
+                           (unsigned long long*)tail);
+        MSM_CHECK_LAUNCH(ctx);
+        absmax = (const double*)tail;
+    }
     const int dense = ld == d && ((uintptr_t)x & 15) == 0;
 #define MSM_PACK_CASE(D)                                                                                              \
     case D:                                                                                                           \
-        hipLaunchKernelGGL((kmeans_pack_kernel<T, D>), dim3(grid), dim3(256), 0, ctx->stream, x, n, ld, mean, stdv, image, \
-                           dense);                                                                                    \
+        hipLaunchKernelGGL((kmeans_pack_kernel<T, D>), dim3(grid), dim3(256), 0, ctx->stream, x, n, ld, mean, stdv, absmax, \
+                           image, dense);                                                                             \
         break
     switch (d) {
         MSM_PACK_CASE(1); MSM_PACK_CASE(2); MSM_PACK_CASE(3); MSM_PACK_CASE(4); MSM_PACK_CASE(5);
@@ -946,8 +975,8 @@ msm_status filter_stats_buffer(msm_ctx* ctx, unsigned long long** out) {
     return MSM_OK;
 }
 
-template <typename T, int NM, bool ACCUM>
-msm_status launch_filter_nm(msm_ctx* ctx, const T* x, int64_t n, int d, int64_t ld, const double* centers, int k,
+template <typename T, int DP, bool ACCUM>
+msm_status launch_filter_dp(msm_ctx* ctx, const T* x, int64_t n, int d, int64_t ld, const double* centers, int k,
                             const double* mean, const double* stdv, const uint4* image, int32_t* labels, double* mindist,
                             const FitState* st, unsigned long long* sums, unsigned long long* counts, double* upd_centers) {
     constexpr int NF = 4;
@@ -955,12 +984,12 @@ msm_status launch_filter_nm(msm_ctx* ctx, const T* x, int64_t n, int d, int64_t 
     // (the centre tables are built by every workgroup of the kernel for itself: no staging launch)
     msm_status rs;
     const int64_t n_units = (n + 16 * NF - 1) / (16 * NF);
-    constexpr int kWaves = filter_waves(NM);
+    const int kWaves = filter_waves(DP, ACCUM);
     const int grid = (int)std::min<int64_t>((n_units + kWaves - 1) / kWaves, (int64_t)ctx->n_cu);
     unsigned long long* stats = nullptr;
     rs = filter_stats_buffer(ctx, &stats);
     if (rs != MSM_OK) return rs;
-    auto kern = mean ? kmeans_filter_kernel<T, NM, NF, ACCUM, true> : kmeans_filter_kernel<T, NM, NF, ACCUM, false>;
+    auto kern = mean ? kmeans_filter_kernel<T, DP, NF, ACCUM, true> : kmeans_filter_kernel<T, DP, NF, ACCUM, false>;
     if (lds > 48 * 1024)
         MSM_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * kWaves), lds, ctx->stream, x, n, d, ld, k, mean, stdv, image, centers,
@@ -974,11 +1003,11 @@ template <typename T, bool ACCUM>
 msm_status launch_filter(msm_ctx* ctx, const T* x, int64_t n, int d, int64_t ld, const double* centers, int k,
                          const double* mean, const double* stdv, const uint4* image, int32_t* labels, double* mindist,
                          const FitState* st, unsigned long long* sums, unsigned long long* counts, double* upd_centers) {
-    if (filter_nm(d) == 1)
-        return launch_filter_nm<T, 1, ACCUM>(ctx, x, n, d, ld, centers, k, mean, stdv, image, labels, mindist, st, sums,
+    if (filter_dp(d) == 4)
+        return launch_filter_dp<T, 4, ACCUM>(ctx, x, n, d, ld, centers, k, mean, stdv, image, labels, mindist, st, sums,
                                              counts, upd_centers);
-    return launch_filter_nm<T, 2, ACCUM>(ctx, x, n, d, ld, centers, k, mean, stdv, image, labels, mindist, st, sums, counts,
-                                         upd_centers);
+    return launch_filter_dp<T, 10, ACCUM>(ctx, x, n, d, ld, centers, k, mean, stdv, image, labels, mindist, st, sums, counts,
+                                          upd_centers);
 }
 
 bool filter_fits(int k, int d, bool accum) { return filter_enabled() && d <= kFilterMaxD && filter_lds_bytes(k, d, accum) != 0; }
@@ -997,7 +1026,7 @@ msm_status dispatch_mfma(msm_ctx* ctx, const T* x, int64_t n, int d, int64_t ld,
         if (!image) {
             msm_status rs = msm_reserve_km_image(ctx, filter_image_bytes(n, d));
             if (rs != MSM_OK) return rs;
-            rs = launch_pack<T>(ctx, x, n, d, ld, mean, stdv, (uint4*)ctx->km_image);
+            rs = launch_pack<T>(ctx, x, n, d, ld, mean, stdv, nullptr, (uint4*)ctx->km_image);
             if (rs != MSM_OK) return rs;
             image = ctx->km_image;
         }
@@ -1023,6 +1052,32 @@ msm_status dispatch_mfma(msm_ctx* ctx, const T* x, int64_t n, int d, int64_t ld,
     MSM_MFMA_CASE(64);
 #undef MSM_MFMA_CASE
     return msm_fail(ctx, MSM_ERR_UNSUPPORTED, "k-means: d=%d > 256 not supported", d);
+}
+
+// msm_mfma_bf16_probe / msm_mfma_f16_probe: n_tiles independent instructions on host operands
+msm_status mfma_probe(msm_ctx* ctx, bool f16, const uint16_t* h_a, const uint16_t* h_b, const float* h_c, float* h_d,
+                      int n_tiles) {
+    if (!ctx) return MSM_ERR_INVALID;
+    MSM_REQUIRE(ctx, n_tiles >= 1 && h_a && h_b && h_c && h_d, "msm_mfma_probe: bad arguments");
+    const size_t na = (size_t)n_tiles * 512 * sizeof(uint16_t), nc = (size_t)n_tiles * 256 * sizeof(float);
+    msm_status rs = msm_reserve_scratch(ctx, 2 * na + 2 * nc);
+    if (rs != MSM_OK) return rs;
+    unsigned char* base = (unsigned char*)ctx->scratch;
+    uint16_t* d_a = (uint16_t*)base;
+    uint16_t* d_b = (uint16_t*)(base + na);
+    float* d_c = (float*)(base + 2 * na);
+    float* d_d = (float*)(base + 2 * na + nc);
+    MSM_HIP(ctx, hipMemcpyAsync(d_a, h_a, na, hipMemcpyHostToDevice, ctx->stream));
+    MSM_HIP(ctx, hipMemcpyAsync(d_b, h_b, na, hipMemcpyHostToDevice, ctx->stream));
+    MSM_HIP(ctx, hipMemcpyAsync(d_c, h_c, nc, hipMemcpyHostToDevice, ctx->stream));
+    if (f16)
+        hipLaunchKernelGGL(mfma_f16_probe_kernel, dim3((unsigned)n_tiles), dim3(64), 0, ctx->stream, d_a, d_b, d_c, d_d);
+    else
+        hipLaunchKernelGGL(mfma_bf16_probe_kernel, dim3((unsigned)n_tiles), dim3(64), 0, ctx->stream, d_a, d_b, d_c, d_d);
+    MSM_CHECK_LAUNCH(ctx);
+    MSM_HIP(ctx, hipMemcpyAsync(h_d, d_d, nc, hipMemcpyDeviceToHost, ctx->stream));
+    MSM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return MSM_OK;
 }
 
 }  // namespace
@@ -1067,6 +1122,11 @@ msm_status msm_kmeans_image_bytes(int64_t n, int d, size_t* out_bytes) {
 
 msm_status msm_kmeans_pack(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n, int d, int64_t ld,
                            const double* d_mean, const double* d_std, void* d_image) {
+    return msm_kmeans_pack_bounded(ctx, d_x, dtype, n, d, ld, d_mean, d_std, nullptr, d_image);
+}
+
+msm_status msm_kmeans_pack_bounded(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n, int d, int64_t ld,
+                                   const double* d_mean, const double* d_std, const double* d_absmax, void* d_image) {
     if (!ctx) return MSM_ERR_INVALID;
     MSM_REQUIRE(ctx, n >= 0 && d >= 1 && d <= kFilterMaxD && ld >= d, "msm_kmeans_pack: need 1 <= d <= %d, ld >= d",
                 kFilterMaxD);
@@ -1075,8 +1135,9 @@ msm_status msm_kmeans_pack(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64
     if (n == 0) return MSM_OK;
     MSM_REQUIRE(ctx, d_x && d_image, "msm_kmeans_pack: NULL pointer");
     MSM_REQUIRE(ctx, ((uintptr_t)d_image & 15) == 0, "msm_kmeans_pack: the image must be 16-byte aligned");
-    if (dtype == MSM_F32) return launch_pack<float>(ctx, (const float*)d_x, n, d, ld, d_mean, d_std, (uint4*)d_image);
-    return launch_pack<double>(ctx, (const double*)d_x, n, d, ld, d_mean, d_std, (uint4*)d_image);
+    if (dtype == MSM_F32)
+        return launch_pack<float>(ctx, (const float*)d_x, n, d, ld, d_mean, d_std, d_absmax, (uint4*)d_image);
+    return launch_pack<double>(ctx, (const double*)d_x, n, d, ld, d_mean, d_std, d_absmax, (uint4*)d_image);
 }
 
 msm_status msm_kmeans_filter_scanned(msm_ctx* ctx, uint64_t* h_out, int reset) {
@@ -1091,24 +1152,12 @@ msm_status msm_kmeans_filter_scanned(msm_ctx* ctx, uint64_t* h_out, int reset) {
 
 msm_status msm_mfma_bf16_probe(msm_ctx* ctx, const uint16_t* h_a, const uint16_t* h_b, const float* h_c, float* h_d,
                                int n_tiles) {
-    if (!ctx) return MSM_ERR_INVALID;
-    MSM_REQUIRE(ctx, n_tiles >= 1 && h_a && h_b && h_c && h_d, "msm_mfma_bf16_probe: bad arguments");
-    const size_t na = (size_t)n_tiles * 512 * sizeof(uint16_t), nc = (size_t)n_tiles * 256 * sizeof(float);
-    msm_status rs = msm_reserve_scratch(ctx, 2 * na + 2 * nc);
-    if (rs != MSM_OK) return rs;
-    unsigned char* base = (unsigned char*)ctx->scratch;
-    uint16_t* d_a = (uint16_t*)base;
-    uint16_t* d_b = (uint16_t*)(base + na);
-    float* d_c = (float*)(base + 2 * na);
-    float* d_d = (float*)(base + 2 * na + nc);
-    MSM_HIP(ctx, hipMemcpyAsync(d_a, h_a, na, hipMemcpyHostToDevice, ctx->stream));
-    MSM_HIP(ctx, hipMemcpyAsync(d_b, h_b, na, hipMemcpyHostToDevice, ctx->stream));
-    MSM_HIP(ctx, hipMemcpyAsync(d_c, h_c, nc, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(mfma_bf16_probe_kernel, dim3((unsigned)n_tiles), dim3(64), 0, ctx->stream, d_a, d_b, d_c, d_d);
-    MSM_CHECK_LAUNCH(ctx);
-    MSM_HIP(ctx, hipMemcpyAsync(h_d, d_d, nc, hipMemcpyDeviceToHost, ctx->stream));
-    MSM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return MSM_OK;
+    return mfma_probe(ctx, false, h_a, h_b, h_c, h_d, n_tiles);
+}
+
+msm_status msm_mfma_f16_probe(msm_ctx* ctx, const uint16_t* h_a, const uint16_t* h_b, const float* h_c, float* h_d,
+                              int n_tiles) {
+    return mfma_probe(ctx, true, h_a, h_b, h_c, h_d, n_tiles);
 }
 
 msm_status msm_kmeans_fit_begin(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n, int d, int64_t ld,
@@ -1258,7 +1307,7 @@ msm_status msm_kmeans_fit(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_
     int32_t* prev = (int32_t*)((char*)ctx->scratch + acc_bytes);
     MSM_HIP(ctx, hipMemsetAsync(sums, 0, acc_bytes, ctx->stream));
     MSM_HIP(ctx, hipMemsetAsync(prev, 0xFF, (size_t)n * sizeof(int32_t), ctx->stream));
-    // the frames' bf16 images are built once and serve every iteration (kmeans_filter.h)
+    // the frames' fp16 images are built once and serve every iteration (kmeans_filter.h)
     const void* image = nullptr;
     if (max_iter > 0 && filter_fits(k, d, true)) {
         rs = msm_reserve_km_image(ctx, filter_image_bytes(n, d));

@@ -1,48 +1,57 @@
-// Certified bf16 matrix-core FILTER + certified fp32 candidate pick for the k-means score table (d <= 10).
+// Certified fp16 matrix-core FILTER + certified fp32 candidate pick for the k-means score table (d <= 10).
 // Included by kmeans.hip inside its anonymous namespace (uses FitState, to_fixed, load_as_f64).
 //
 // The label of a frame is the arg-max over the k centres of the PINNED fp64 score
 //     m_j = fl(dot_j - h_j),  dot_j = ascending-feature fma chain of c_j[f] * z[f],  h_j = |c_j|^2 / 2
 // (strict '>' over ascending j; kmeans.hip states why this is sklearn's arg-min).  An all-fp64 scan costs
 // three v_mfma_f64_16x16x4 (64 cycles each) per 16 centres x 16 frames.  This kernel gets the same labels,
-// bit for bit, from bf16 matrix instructions at 1/6 of that matrix-pipe time:
+// bit for bit, from ONE v_mfma_f32_16x16x32_f16 (16 cycles) per 16 centres x 16 frames:
 //
-// 1. FILTER.  Every coordinate is split into three bf16 numbers (v = vh + vm + vl + r, |r| <= 2^-24 |v|:
-//    a bf16 triple holds an fp32 exactly).  One K = 32 instruction pair (v_mfma_f32_16x16x32_bf16 twice, 64
-//    product slots) evaluates, per centre and frame,
-//        u_j = sum_f (ch xh + cm xh + ch xm + cm xm + cl xh + ch xl)  -  (1 - kappa) h_j  +  kappa |c_j| |x|
-//    i.e. the score plus kappa (|x||c_j| + h_j) >= kappa S_j,  S_j = sum_f |x_f c_jf| + h_j.
-//    u_j is an UPPER BOUND of the pinned score m_j:
-//      dropped split terms   <= 4.01 x 2^-24 S_j
-//      accumulation          <= 68.7 x 2^-24 S_j: the instruction aligns its 32 products and C to the largest
-//                               exponent, keeps 24 bits below it, truncates, adds, and rounds once (measured on
-//                               MI355X, tools/probe/bf16_filter_probe.hip and tests/test_gpu_mfma_rule.py: terms
-//                               below 2^-24 of the largest one vanish, equal terms at 2^-24 survive; the last bits
-//                               depend on the order of the slots (groups of products are added), the bound holds
-//                               for every order; worst observed error 11.7 x 2^-24 of the largest term against
-//                               the bound 33)
-//      fp64 chain of m_j     <= 12 x 2^-53 S_j
-//    and kappa = 80 x 2^-24 covers their sum with 7 x 2^-24 S_j to spare.  With d <= 4 everything fits ONE
-//    instruction (28 slots): accumulation <= 34.3 x 2^-24 S_j, kappa = 44 x 2^-24.
+// 1. FILTER.  Frames are scaled by 2^e_x (one power of two per shard), centres by 2^e_c (one per launch), so that
+//    every scaled coordinate v' has |v'| < 2^13 (Scales, below).  v' is split into two fp16 numbers,
+//    v' = vh + vl + r with |r| <= 2^-22 |v'| (a part that would be subnormal is left out: Range).  One instruction
+//    (31 of its 32 product slots, filter_slot) evaluates, per centre and frame,
+//        u'_j = sum_f (ch xh + ch xl + cl xh)  +  C_j  +  kappa |c'_j| |x'|,   C_j >= -(1 - kappa) h'_j
+//    with h'_j = 2^(e_x + e_c) h_j and C_j the fp32 C operand, rounded up: the scaled score plus
+//    kappa (|x'||c'_j| + h'_j) >= kappa S'_j, S'_j = sum_f |x'_f c'_jf| + h'_j.  u_j = 2^-(e_x + e_c) u'_j is an
+//    UPPER BOUND of the pinned score m_j (the scales are powers of two: every relative bound carries over exactly):
+//      dropped split terms   <= 12.01 x 2^-24 S_j  (cl xl, and the residuals r of both sides)
+//      accumulation          <= 34.3 x 2^-24 S_j: the instruction sums its 32 products and C with an error of at
+//                               most 33 x 2^-24 of the largest term, in any slot order, plus the final rounding
+//                               (measured on MI355X, tests/test_gpu_mfma_rule_f16.py: worst observed 8.5 x 2^-24
+//                               of the largest term; a term of 2^-24 of the largest vanishes; the last bits depend
+//                               on the slot order; fp16 subnormal inputs are kept, not flushed -- the filter never
+//                               hands one over, so it does not depend on that)
+//      fp64 chain of m_j     <= 12 x 2^-53 S_j, fp64 rounding of (1 - kappa) h_j <= 2^-53 h_j
+//    and kappa = 52 x 2^-24 covers their sum with 5.6 x 2^-24 S_j to spare.  The C operand and both factors of the
+//    kappa slot are rounded up, which only raises u.  (The bf16 form this replaces split every coordinate three ways:
+//    6 d + 4 slots, two instructions per tile at d > 4, an 80-byte frame image and kappa = 80 x 2^-24.)
 // 2. Per lane (4 accumulator rows of a frame) only the largest PAIR maximum of u, the runner-up pair maximum and
 //    the pair index are tracked (max3 tree, med3, max, compare, select: 8 VALU per 8 scores).
 // 3. CANDIDATE PICK.  The 8 centres of the winning lane's winning pair are scored in fp32 from an fp32 copy of the
-//    centre table (s_j: the same chain in fp32; |s_j - exact_j| <= 14.1 x 2^-24 S_j, and S_j <= |z||c_j| + h_j),
-//    E = 20 x 2^-24 max_j (max(|z|, 1) |c_j| + h_j) + 1e-30.  With jw = arg-max s_j and R = the largest u outside the 8
-//    (runner-up pair of the winning lane, best pairs of the frame's other three lanes): if s_jw - E exceeds
-//    every other s_j + E AND R, then m_jw > m_j for every other centre: the label is jw, exactly as the
-//    all-fp64 scan gives it, and no fp64 arithmetic was needed.  (The pinned distance, when asked for, is the fp64
-//    chain of that one centre.)
+//    centre table (s_j: the same chain in fp32, unscaled; |s_j - exact_j| <= 14.1 x 2^-24 S_j, and
+//    S_j <= |z||c_j| + h_j), E = 20 x 2^-24 max_j (max(|z|, 1) |c_j| + h_j) + 1e-30.  With jw = arg-max s_j and
+//    R = the largest u outside the 8 (runner-up pair of the winning lane, best pairs of the frame's other three lanes,
+//    brought back to unscaled units): if s_jw - E exceeds every other s_j + E AND R, then m_jw > m_j for every other
+//    centre: the label is jw, exactly as the all-fp64 scan gives it, and no fp64 arithmetic was needed.  (The pinned
+//    distance, when asked for, is the fp64 chain of that one centre.)
 // 4. Otherwise (about 0.2 % of the frames: near-ties, duplicate centres, NaN / out-of-range input) the wave scores ALL
 //    centres for that frame in fp32 from the same LDS table, lane l rows l, l + 64, ...: no centre with
 //    s_j < max s - 2 E can hold the pinned maximum, so when one centre is left it is the label; else the pinned fp64
 //    scores of the few rows in that band decide (lowest index on ties, as the all-fp64 scan).  Only frames or tables
 //    that fail the range guard take the plain scan of all centres in fp64 (rows from global memory).
 //
-// Range: coordinates with 0 < |v| < 1e-14 are LEFT OUT of the bf16 images (their products could underflow inside
-// the matrix instruction) and the bound pays for them: a frame adds (sum of its tiny |x_f|) / kappa to its |x|
-// slot, a centre adds the sum of its tiny |c_jf| to its kappa |c_j| slot -- either covers the dropped products.
-// Frames or centres with |v| > 1e18, inf or NaN fail the guard: the frame (for a centre: every frame) takes step 4.
+// Scales.  e_x puts a bound on max |x| of the shard into [2^12, 2^13): msm_kmeans_pack_bounded takes the bound from
+// the caller (the bench chain hands over max |Y| of the projection, slot 2 of the fit state), msm_kmeans_pack finds
+// it with a pass of its own (filter_absmax_kernel, coordinates that pass the unscaled guard only); e_x travels in the
+// word after the image rows.  e_c does the same for max |c| of the centre table, per launch and workgroup.  A frame
+// is only ever compared across centres, so shards need no common e_x.
+// Range: scaled parts below 2^-14 (fp16 subnormal) are LEFT OUT of the operands and the bound pays for them: a frame
+// adds twice what it left out (a whole |v'| or a residual |v' - vh|, each < 2^-14), divided by kappa, to its |x'|
+// slot; a centre adds twice its left-out sum to its kappa |c'_j| slot -- either covers the dropped products with
+// room for the accumulation error of the slot itself.  Both slots are at least 2^-14.  Frames or centres with
+// |v| > 1e18, |v'| > 2^14, inf or NaN fail the guard: the frame (for a centre: every frame) takes step 4; so does
+// every frame when a centre's |C| would exceed 2^100.
 //
 // Schedule.  One workgroup of kFilterWaves waves per CU builds the centre tables in its LDS and then takes units of
 // 64 frames: tile loop (matrix pipe + top-two bookkeeping), the loads of the next unit's images and of this unit's
@@ -51,78 +60,89 @@
 // end of the workgroup's units alike: ~10 us of a wave per frame, and the slowest workgroup has 20 of them.  Scoring
 // the eight candidates in fp64 before step 4, one lane and one row at a time, halves the frames that reach step 4 and
 // still loses 6 us per pass: eight dependent trips to the L2 per occurrence.)  What the SIMD can do (tools/probe/bf16_mix_probe.hip): a matrix instruction keeps the
-// matrix pipe for 16 cycles and the VALU port for 8, a VALU instruction the port for 4; the tile loop (16 + 34 per
-// iteration) is balanced between the two.  Tried and dropped: scoring the candidates of unit i - 1 inside the tile
+// matrix pipe for 16 cycles and the VALU port for 8, a VALU instruction the port for 4; the bf16 tile loop (16 + 34 per
+// iteration) was balanced between the two; with one instruction per tile the VALU port bounds it.  Tried and dropped: scoring the candidates of unit i - 1 inside the tile
 // loop of unit i (same time: the port is the limit either way, and the state costs 12 of 16 waves).
 #pragma once
 
 typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
+typedef _Float16 v8h __attribute__((ext_vector_type(8)));
 typedef float v4f32 __attribute__((ext_vector_type(4)));
 
-// waves per workgroup (= per CU): the two-instruction shapes need ~150 VGPRs to keep the next unit's images in flight
-// without spilling (a kernel with ANY scratch memory ran 25 us longer per pass), the one-instruction shapes fit 128
+// waves per workgroup (= per CU): one instruction per tile and one 16-byte B operand per frame group keep the assign
+// passes within the 128 VGPRs of 16 waves; the d <= 10 accumulate passes (ten fp64 coordinates for the member sums)
+// need a few more and run 12 waves (a kernel with ANY scratch memory ran 25 us longer per pass)
 #ifdef MSM_KMF_WAVES
-__host__ __device__ constexpr int filter_waves(int) { return MSM_KMF_WAVES; }
+__host__ __device__ constexpr int filter_waves(int, bool) { return MSM_KMF_WAVES; }
 #else
-__host__ __device__ constexpr int filter_waves(int nm) { return nm == 1 ? 16 : 12; }
+__host__ __device__ constexpr int filter_waves(int dp, bool heavy) { return dp == 10 && heavy ? 12 : 16; }
 #endif
 constexpr int kFilterMaxD = 10;
-constexpr double kFilterTiny = 1e-14, kFilterHi = 1e18;
-constexpr float kPickEps = 20.0f * 5.9604644775390625e-08f;   // 20 x 2^-24
+constexpr int kFilterRowQ = 3;                                   // uint4 per frame image (48 bytes)
+constexpr double kFilterHi = 1e18;                               // unscaled range guard (the fp32 pick)
+constexpr double kFilterScaledHi = 16384.0;                      // 2^14: scaled range guard (fp16 operands)
+constexpr double kF16MinNormal = 6.103515625e-05;                // 2^-14
+constexpr int kFilterScaleTop = 13;                              // a scale puts the largest |v| into [2^12, 2^13)
+constexpr double kFilterKappa = 52.0 * 5.9604644775390625e-08;   // 52 x 2^-24
+constexpr float kPickEps = 20.0f * 5.9604644775390625e-08f;      // 20 x 2^-24
 constexpr float kPickFloor = 1e-30f;
-constexpr float kUp20 = 1.0f + 9.5367431640625e-07f;          // 1 + 2^-20
+constexpr float kUp20 = 1.0f + 9.5367431640625e-07f;             // 1 + 2^-20
+constexpr double kUp20d = 1.0 + 9.5367431640625e-07;
 
-__host__ __device__ constexpr int filter_nm(int d) { return 6 * d + 4 <= 32 ? 1 : 2; }   // K = 32 instructions per tile
-__host__ __device__ constexpr int filter_rowq(int nm) { return nm == 1 ? 4 : 5; }         // uint4 per frame image
-__host__ __device__ constexpr double filter_kappa(int nm) { return (nm == 1 ? 44.0 : 80.0) * 5.9604644775390625e-08; }
+// the exponent e of a power-of-two scale 2^e that puts amax into [2^12, 2^13) (0 for a zero or non-finite bound;
+// clamped to +-60 so that 2^-(e_x + e_c) stays a normal fp32 number)
+__host__ __device__ inline int filter_scale_exp(double amax) {
+    if (!(amax > 0.0) || !(amax <= 1.7976931348623157e308)) return 0;
+    const int q = ilogb(amax) + 1;   // amax = m 2^q, m in [0.5, 1) (frexp's out-parameter costs scratch memory)
+    const int e = kFilterScaleTop - q;
+    return e < -60 ? -60 : (e > 60 ? 60 : e);
+}
 
-__device__ __forceinline__ unsigned bf16_rn(float f) {            // round to nearest even, finite input
-    unsigned u = __float_as_uint(f);
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return u >> 16;
+// fp16 numbers of the normal range [2^-14, 65504] from fp64, without a detour through fp32 (two roundings):
+// v = m 2^q, m in [0.5, 1), keeps 11 significant bits, the last at 2^(q - 11)
+__device__ __forceinline__ double f16_round(double v) {
+    const int q = ilogb(v) + 1;
+    return ldexp(rint(ldexp(v, 11 - q)), q - 11);
 }
-__device__ __forceinline__ float bf16_f32(unsigned h) { return __uint_as_float(h << 16); }
-__device__ __forceinline__ unsigned bf16_up(float f) {            // smallest bf16 >= f, f >= 0 finite
-    unsigned h = bf16_rn(f);
-    if (bf16_f32(h) < f) ++h;
-    return h;
+__device__ __forceinline__ double f16_ceil(double v) {   // smallest fp16 >= v, v >= 2^-14
+    const int q = ilogb(v) + 1;
+    return ldexp(ceil(ldexp(v, 11 - q)), q - 11);
 }
-__device__ __forceinline__ void bf16_split3(double v, unsigned (&out)[3]) {
-    float r = (float)v;
-#pragma unroll
-    for (int t = 0; t < 3; ++t) {
-        out[t] = bf16_rn(r);
-        r -= bf16_f32(out[t]);
+__device__ __forceinline__ unsigned short f16_bits(double v) {   // v is an fp16 number: exact
+    return __builtin_bit_cast(unsigned short, (_Float16)(float)v);
+}
+// two-term fp16 split of a scaled coordinate |v| <= 2^14: v = hi + lo + r with |r| <= 2^-22 |v|.  A part that would
+// be subnormal is left out (zero) and what it leaves behind is added to `tiny` (the bound pays for it, header "Range")
+__device__ __forceinline__ void f16_split2(double v, unsigned short& hi, unsigned short& lo, double& tiny) {
+    hi = lo = 0;
+    if (!(fabs(v) >= kF16MinNormal)) {
+        tiny += fabs(v);
+        return;
     }
+    const double h = f16_round(v);
+    const double r = v - h;   // exact
+    hi = f16_bits(h);
+    if (!(fabs(r) >= kF16MinNormal)) {
+        tiny += fabs(r);
+        return;
+    }
+    lo = f16_bits(f16_round(r));
 }
-// product term t pairs these split parts (0 = high, 1 = middle, 2 = low)
-__device__ __forceinline__ int filter_part_c(int t) { return t == 1 || t == 3 ? 1 : (t == 4 ? 2 : 0); }
-__device__ __forceinline__ int filter_part_x(int t) { return t == 2 || t == 3 ? 1 : (t == 5 ? 2 : 0); }
+// smallest fp32 >= v, |v| < 2^127
+__device__ __forceinline__ float f32_up(double v) {
+    float f = (float)v;
+    if ((double)f < v) f = __uint_as_float(__float_as_uint(f) + (f >= 0.0f ? 1u : ~0u));
+    return f;
+}
 
-// K slot of product term t, feature f.  NM = 1: t d + f, then three slots for h and slot 31 for the norms.
-// NM = 2: the slots are ordered so that a lane's 8 slots (quarter q of instruction m) need ONE 16-byte piece of
-// a 80-byte frame image  [xh0..7 | xm0..7 | xl0..7 | xh8 xh9 xh8 xh9 xh8 xh9 xm8 xm9 | xm8 xm9 xl8 xl9 1 1 1 |x|]:
-//   m = 0: q0 = ch xh, q1 = cm xh, q2 = cl xh (all three read piece 0), q3 = ch xm (piece 1)
-//   m = 1: q0 = cm xm (piece 1), q1 = ch xl (piece 2), q2 = features 8, 9 of terms 0, 1, 4, 2 (piece 3),
-//          q3 = features 8, 9 of terms 3, 5, then -(1 - kappa) h_j in three parts and kappa |c_j| (piece 4)
-// (the expanded image was 128 bytes per frame and pass; the error bound of the instruction holds for any slot order).
-template <int NM>
-__host__ __device__ constexpr int filter_slot(int t, int f, int d) {
-    if (NM == 1) return t * d + f;
-    constexpr int lo8[6] = {0, 8, 24, 32, 16, 40};      // term -> first slot of features 0..7
-    constexpr int hi2[6] = {48, 50, 54, 56, 52, 58};    // term -> first slot of features 8, 9
-    return f < 8 ? lo8[t] + f : hi2[t] + (f - 8);
-}
-template <int NM>
-__host__ __device__ constexpr int filter_slot_h(int d) { return NM == 1 ? 6 * d : 60; }   // three slots, then ...
-template <int NM>
-__host__ __device__ constexpr int filter_slot_norm() { return 32 * NM - 1; }
-// piece of the frame image read by quarter q of instruction m
-template <int NM>
-__device__ __forceinline__ int filter_piece(int q, int m) {
-    if (NM == 1) return q;
-    return m == 0 ? (q < 3 ? 0 : 1) : q + 1;
-}
+// K slot of product term t (0 = ch xh, 1 = ch xl, 2 = cl xh), feature f.  Quarter q of the instruction (slots
+// 8 q .. 8 q + 7) reads piece filter_piece(q) of the 48-byte frame image
+//     [xh0..7 | xl0..7 | xh8 xh9 xl8 xl9 xh8 xh9 0 |x|]
+// so that quarters 0 and 2 share piece 0: q0 = ch xh, q1 = ch xl, q2 = cl xh (features 0..7), q3 = features 8, 9 of
+// the three terms, an empty slot and kappa |c_j| against |x| (slot 31).  -(1 - kappa) h_j is the C operand.
+__host__ __device__ constexpr int filter_slot(int t, int f) { return f < 8 ? 8 * t + f : 24 + 2 * t + (f - 8); }
+constexpr int kFilterSlotNorm = 31;
+__device__ __forceinline__ int filter_piece(int q) { return q == 3 ? 2 : (q & 1); }
 
 // max3 / med3 are written with compiler-visible builtins (hipcc then pads the MFMA -> VALU read hazard itself;
 // it does not inside inline asm).  fmaxf(fmaxf(a, b), c) becomes ONE v_max3_f32 with no canonicalising v_max x, x
@@ -138,9 +158,10 @@ __device__ __forceinline__ float hw_max_f32(float a, float b) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Frame images: row t = the B operands of frame t (filter_rowq uint4: 64 bytes for d <= 4, 80 bytes for d <= 10),
-// layout as filter_slot; the |x| slot is rounded up (it meets kappa |c_j|) and is +inf when the frame fails the
-// range guard.  One thread per frame.
+// Frame images: row t = the B operands of frame t (3 uint4, layout as filter_slot) in scaled units x' = 2^e_x x; the
+// |x| slot is rounded up (it meets kappa |c_j|) and is +inf when the frame fails the range guard.  The image holds
+// whole units of 64 rows and then one uint4 [max |x| bound (f64) | e_x (i32) | pad]: e_x follows from the bound
+// `absmax` (>= max |x| over the shard, whitened when mean / stdv are given), one scale per shard.  One thread per frame.
 // ---------------------------------------------------------------------------------------------------------
 // Both sides of the kernel go through the LDS so that the memory system only ever sees consecutive lanes on
 // consecutive 16-byte pieces: a lane reading its own 8 D-byte row or writing its own image row touched 64
@@ -148,11 +169,10 @@ __device__ __forceinline__ float hw_max_f32(float a, float b) {
 template <typename T, int D>
 __global__ __launch_bounds__(256) void kmeans_pack_kernel(const T* __restrict__ x, int64_t n, int64_t ld,
                                                          const double* __restrict__ mean,
-                                                         const double* __restrict__ stdv, uint4* __restrict__ image,
-                                                         int dense) {
-    constexpr int NM = filter_nm(D);
-    constexpr int RQ = filter_rowq(NM);
-    constexpr int kOutStride = 5;                       // uint4 per staged image row (odd: bank spread)
+                                                         const double* __restrict__ stdv, const double* absmax,
+                                                         uint4* __restrict__ image, int dense) {
+    constexpr int RQ = kFilterRowQ;
+    constexpr int kOutStride = RQ;                      // uint4 per staged image row (odd: bank spread)
     constexpr int kInBytes = 256 * D * (int)sizeof(T);  // a workgroup's rows, back to back
     constexpr int kOutBytes = 256 * kOutStride * 16;
     __shared__ __attribute__((aligned(16))) unsigned char stage[kOutBytes > kInBytes ? kOutBytes : kInBytes];
@@ -162,6 +182,8 @@ __global__ __launch_bounds__(256) void kmeans_pack_kernel(const T* __restrict__ 
     // the image is padded to whole units of 64 rows: rows beyond n are written as frames that fail the range guard
     const int64_t n_pad = (n + 63) & ~(int64_t)63;
     const int rows_out = (int)(n_pad - t0 < 256 ? n_pad - t0 : 256);
+    const int ex = filter_scale_exp(*absmax);
+    if (blockIdx.x == 0 && threadIdx.x == 0) reinterpret_cast<int*>(image + n_pad * RQ)[2] = ex;
     double v[D];
     if (dense) {
         // rows * D * sizeof(T) bytes from x + t0 * D, 16 bytes per lane and trip (the tail of the last workgroup by element)
@@ -183,57 +205,46 @@ __global__ __launch_bounds__(256) void kmeans_pack_kernel(const T* __restrict__ 
 #pragma unroll
         for (int f = 0; f < D; ++f) v[f] = load_as_f64(row + f);
     }
-    unsigned part[D][3];
-    double q = 0.0, tiny = 0.0;
     bool ok = t < n;
 #pragma unroll
     for (int f = 0; f < D; ++f) {
         if (mean) v[f] = (v[f] - mean[f]) / stdv[f];
-        ok = ok && fabs(v[f]) <= kFilterHi;   // false for NaN
+        ok = ok && fabs(v[f]) <= kFilterHi;           // false for NaN
+        v[f] = ldexp(v[f], ex);                       // exact
+        ok = ok && fabs(v[f]) <= kFilterScaledHi;
     }
+    unsigned short hi[D], lo[D];
+    double q = 0.0, tiny = 0.0;
 #pragma unroll
     for (int f = 0; f < D; ++f) {
-        const double a = fabs(v[f]);
-        const bool keep = ok && a >= kFilterTiny;
-        if (ok && !keep) tiny += a;            // left out of the image, paid for in the |x| slot
-        const double w = keep ? v[f] : 0.0;
-        q = fma(w, w, q);
-        bf16_split3(w, part[f]);
-    }
-    const unsigned xn = ok ? bf16_up((float)((sqrt(q) + tiny / filter_kappa(NM)) * (1.0 + 9.5367431640625e-07))) : 0x7F80u;
-    unsigned slots[8 * RQ];
-#pragma unroll
-    for (int s = 0; s < 8 * RQ; ++s) slots[s] = 0;
-    if constexpr (NM == 1) {
-#pragma unroll
-        for (int tt = 0; tt < 6; ++tt)
-#pragma unroll
-            for (int f = 0; f < D; ++f) slots[tt * D + f] = part[f][tt == 2 || tt == 3 ? 1 : (tt == 5 ? 2 : 0)];
-        slots[6 * D] = slots[6 * D + 1] = slots[6 * D + 2] = 0x3F80u;   // 1.0 against the three parts of -(1 - kappa) h_j
-        slots[31] = xn;                                                  // |x| rounded up against kappa |c_j|
-    } else {
-#pragma unroll
-        for (int f = 0; f < D; ++f) {
-            if (f < 8) {
-                slots[f] = part[f][0];
-                slots[8 + f] = part[f][1];
-                slots[16 + f] = part[f][2];
-            } else {
-                const int g = f - 8;
-                slots[24 + g] = slots[26 + g] = slots[28 + g] = part[f][0];
-                slots[30 + g] = part[f][1];
-                slots[32 + g] = part[f][1];
-                slots[34 + g] = part[f][2];
-            }
+        hi[f] = lo[f] = 0;
+        if (ok) {
+            q = fma(v[f], v[f], q);
+            f16_split2(v[f], hi[f], lo[f], tiny);
         }
-        slots[36] = slots[37] = slots[38] = 0x3F80u;
-        slots[39] = xn;
     }
+    // |x'| rounded up, plus twice what the left-out parts can contribute against kappa |c_j| (header, "Range")
+    const unsigned short xn =
+        ok ? f16_bits(f16_ceil(fmax((sqrt(q) + 2.0 * tiny / kFilterKappa) * kUp20d, kF16MinNormal))) : 0x7C00;
+    unsigned short s[8 * RQ];
+#pragma unroll
+    for (int i = 0; i < 8 * RQ; ++i) s[i] = 0;
+#pragma unroll
+    for (int f = 0; f < D; ++f) {
+        if (f < 8) {
+            s[f] = hi[f];
+            s[8 + f] = lo[f];
+        } else {
+            s[16 + f - 8] = s[20 + f - 8] = hi[f];
+            s[18 + f - 8] = lo[f];
+        }
+    }
+    s[23] = xn;
     uint4* mine = reinterpret_cast<uint4*>(stage) + threadIdx.x * kOutStride;
 #pragma unroll
     for (int c = 0; c < RQ; ++c)
-        mine[c] = make_uint4(slots[8 * c + 0] | (slots[8 * c + 1] << 16), slots[8 * c + 2] | (slots[8 * c + 3] << 16),
-                             slots[8 * c + 4] | (slots[8 * c + 5] << 16), slots[8 * c + 6] | (slots[8 * c + 7] << 16));
+        mine[c] = make_uint4(s[8 * c + 0] | ((unsigned)s[8 * c + 1] << 16), s[8 * c + 2] | ((unsigned)s[8 * c + 3] << 16),
+                             s[8 * c + 4] | ((unsigned)s[8 * c + 5] << 16), s[8 * c + 6] | ((unsigned)s[8 * c + 7] << 16));
     __syncthreads();
     uint4* dst = image + t0 * RQ;
     for (int c = threadIdx.x; c < rows_out * RQ; c += 256)
@@ -242,26 +253,27 @@ __global__ __launch_bounds__(256) void kmeans_pack_kernel(const T* __restrict__ 
 
 // ---------------------------------------------------------------------------------------------------------
 // Centre side, once per launch and workgroup (one wave per 16-centre tile) into the kernel's LDS:
-//   img   [n_tiles][NM][64] uint4       A operands, lane-major per instruction
+//   img   [n_tiles][64] uint4           A operands in scaled units c' = 2^e_c c, lane-major
 //   tab   [n_tiles * 16][RF] f32        fp32 centre coordinates zero-padded to DP features, then h_j, then |c_j|
 //                                       rounded up (padding rows: 0, 3e38, -3e38), rows 16-byte aligned: step 3
+//   cz    [n_tiles * 16] f32            C operand: -(1 - kappa) h_j 2^(e_x + e_c) rounded up (padding rows: -3e38)
 //   hs    [n_tiles * 16] f64            h_j (+inf for padding rows): step 4 and the pinned distance
 //   any_bad                             a centre failed the range guard: every frame takes the exhaustive scan
-// DP = 4 (NM = 1) or 10 (NM = 2).
+// DP = 4 (d <= 4) or 10 (d <= 10): the features of the fp32 table and of the frame coordinates.
 // ---------------------------------------------------------------------------------------------------------
-template <int NM>
+template <int DP>
 struct FilterShape {
-    static constexpr int DP = NM == 1 ? 4 : 10;
-    static constexpr int RF = NM == 1 ? 8 : 12;                          // floats per table row
-    static constexpr int kTileBytes = NM * 1024 + 16 * RF * 4 + 16 * 8;  // image + table rows + h of one 16-centre tile
+    static constexpr int RF = DP == 4 ? 8 : 12;                             // floats per table row
+    static constexpr int kTileBytes = 1024 + 16 * RF * 4 + 16 * 4 + 16 * 8;  // image + table rows + C + h of one tile
 };
+__host__ __device__ constexpr int filter_dp(int d) { return d <= 4 ? 4 : 10; }
 
 // One wave stages one 16-centre tile in two steps, so that a wave with several tiles has the global loads of all of
 // them in flight before it builds the first (the build is ~300 instructions; one load round trip under load is as long):
 //   filter_stage_fetch: the tile's 16 x d coordinates, one coalesced load per 64 elements (element e = row e / d,
 //                       feature e % d), at most kStageRegs per lane;
-//   filter_stage_build: bf16 triples into the A operands, fp32 coordinates into the table rows; the 16 row lanes then
-//                       fetch their row once more for h_j, the range guard and the kappa slots (the fp64 chain over
+//   filter_stage_build: fp16 pairs into the A operands, fp32 coordinates into the table rows; the 16 row lanes then
+//                       fetch their row once more for h_j, C, the range guard and the kappa slot (the fp64 chain over
 //                       ascending features: the bits of every other h_j in the library).
 constexpr int kStageRegs = (16 * kFilterMaxD + 63) / 64;
 // i / d for 0 <= i < 256, 1 <= d <= 10 without the integer-division sequence: (i + 0.5) / d is at least 0.05 away from
@@ -281,30 +293,31 @@ __device__ __forceinline__ void filter_stage_fetch(int tile, int lane, const dou
 #pragma unroll
     for (int f = 0; f < DP; ++f) rc[f] = (lane < 16 && jr < k && f < d) ? centers[(size_t)jr * d + f] : 0.0;
 }
-template <int NM>
+// ec: the centres' scale exponent; exc = e_x + e_c (the scale of the C operand)
+template <int DP>
 __device__ __forceinline__ void filter_stage_build(int tile, int lane, unsigned short* simg, const double (&c)[kStageRegs],
-                                                   const double (&rc)[FilterShape<NM>::DP], int k, int d,
-                                                   float* __restrict__ tab, double* __restrict__ hs, int* __restrict__ any_bad) {
-    using S = FilterShape<NM>;
-    constexpr double kappa = filter_kappa(NM);
-    for (int i = lane; i < NM * 64 * 4; i += 64) reinterpret_cast<unsigned*>(simg)[i] = 0u;
+                                                   const double (&rc)[DP], int k, int d, int ec, int exc,
+                                                   float* __restrict__ tab, float* __restrict__ cz, double* __restrict__ hs,
+                                                   int* __restrict__ any_bad) {
+    using S = FilterShape<DP>;
+    for (int i = lane; i < 64 * 4; i += 64) reinterpret_cast<unsigned*>(simg)[i] = 0u;
     for (int i = lane; i < 16 * S::RF; i += 64) tab[(size_t)tile * 16 * S::RF + i] = 0.0f;   // pads beyond d
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");   // one wave, LDS in order: only the compiler must not reorder
-    auto slot_addr = [&](int i, int sl) {      // bf16 element of tile row i, slot sl
-        const int m = sl >> 5, qq = (sl & 31) >> 3, e = sl & 7;
-        return ((m * 64) + qq * 16 + i) * 8 + e;
-    };
+    auto slot_addr = [&](int i, int sl) { return ((sl >> 3) * 16 + i) * 8 + (sl & 7); };   // fp16 element of row i, slot sl
 #pragma unroll
     for (int u = 0; u < kStageRegs; ++u) {
         const int i = lane + 64 * u;
         const int r = stage_row(i, d), f = i - r * d, j = tile * 16 + r;
         if (i < 16 * d && j < k) {
             tab[(size_t)j * S::RF + f] = (float)c[u];
-            if (fabs(c[u]) >= kFilterTiny) {            // tiny coordinates stay out of the image (see the header)
-                unsigned cp[3];
-                bf16_split3(c[u], cp);
-#pragma unroll
-                for (int t = 0; t < 6; ++t) simg[slot_addr(r, filter_slot<NM>(t, f, d))] = (unsigned short)cp[filter_part_c(t)];
+            const double w = ldexp(c[u], ec);
+            if (fabs(w) <= kFilterScaledHi) {            // (else the row lanes below fail the range guard)
+                unsigned short ch, cl;
+                double tiny = 0.0;                       // (the row lanes add it up for the kappa slot)
+                f16_split2(w, ch, cl, tiny);
+                simg[slot_addr(r, filter_slot(0, f))] = ch;
+                simg[slot_addr(r, filter_slot(1, f))] = ch;
+                simg[slot_addr(r, filter_slot(2, f))] = cl;
             }
         }
     }
@@ -315,33 +328,34 @@ __device__ __forceinline__ void filter_stage_build(int tile, int lane, unsigned 
         float* row = tab + (size_t)j * S::RF;
         double h = __builtin_inf();
         if (j < k) {
-            double a = 0.0, akeep = 0.0, tiny = 0.0;
+            double a = 0.0, aw = 0.0, tiny = 0.0;
             bool ok = true;
 #pragma unroll
-            for (int f = 0; f < S::DP; ++f) {
+            for (int f = 0; f < DP; ++f) {
                 const double cf = rc[f];   // zero beyond d
                 a = fma(cf, cf, a);
-                const double ac = fabs(cf);
-                ok = ok && ac <= kFilterHi;              // false for NaN
-                if (ac >= kFilterTiny) akeep = fma(cf, cf, akeep);
-                else tiny += ac;
+                const double w = ldexp(cf, ec);
+                ok = ok && fabs(cf) <= kFilterHi && fabs(w) <= kFilterScaledHi;   // false for NaN
+                if (ok) {   // what f16_split2 leaves out of this coordinate
+                    aw = fma(w, w, aw);
+                    const double r = fabs(w) >= kF16MinNormal ? fabs(w - f16_round(w)) : fabs(w);
+                    if (!(r >= kF16MinNormal) || !(fabs(w) >= kF16MinNormal)) tiny += r;
+                }
             }
             h = 0.5 * a;
+            const double cval = ldexp(-(h - kFilterKappa * h), exc);
+            ok = ok && fabs(cval) <= 0x1p100;
             if (!ok) bad_row = 1;
-            unsigned hsp[3];
-            bf16_split3(-(h - kappa * h), hsp);
-            const int sh = filter_slot_h<NM>(d);
-            simg[slot_addr(lane, sh)] = (unsigned short)hsp[0];
-            simg[slot_addr(lane, sh + 1)] = (unsigned short)hsp[1];
-            simg[slot_addr(lane, sh + 2)] = (unsigned short)hsp[2];
-            simg[slot_addr(lane, filter_slot_norm<NM>())] =
-                (unsigned short)bf16_up((float)((kappa * sqrt(akeep) + tiny) * (1.0 + 9.5367431640625e-07)));
-            row[S::DP] = (float)h;
-            row[S::DP + 1] = (float)(sqrt(a) * (1.0 + 9.5367431640625e-07));
+            cz[j] = ok ? f32_up(cval) : 0.0f;
+            if (ok)
+                simg[slot_addr(lane, kFilterSlotNorm)] =
+                    f16_bits(f16_ceil(fmax((kFilterKappa * sqrt(aw) + 2.0 * tiny) * kUp20d, kF16MinNormal)));
+            row[DP] = (float)h;
+            row[DP + 1] = (float)(sqrt(a) * kUp20d);
         } else {
-            simg[slot_addr(lane, filter_slot_h<NM>(d))] = 0xFF7F;   // -3.4e38 x 1.0: a padding centre never holds a maximum
-            row[S::DP] = 3.0e38f;        // score -3e38 ...
-            row[S::DP + 1] = -3.0e38f;   // ... and an S bound <= 0 (the pick multiplies this by max(|z|, 1))
+            cz[j] = -3.0e38f;            // a padding centre never holds a maximum
+            row[DP] = 3.0e38f;           // score -3e38 ...
+            row[DP + 1] = -3.0e38f;      // ... and an S bound <= 0 (the pick multiplies this by max(|z|, 1))
         }
         hs[j] = h;
     }
@@ -418,6 +432,30 @@ __device__ __forceinline__ double wave_max_f64(double x) {   // NaN operands los
                __longlong_as_double((long long)(((unsigned long long)rh[1] << 32) | rl[1])));
     }
     return x;
+}
+
+// max |v| over the coordinates that pass the unscaled range guard (whitened when mean / stdv are given) into *out_bits
+// (non-negative doubles order like their bits): the bound of the frames' scale when the caller has none to give
+template <typename T>
+__global__ __launch_bounds__(256) void filter_absmax_kernel(const T* __restrict__ x, int64_t n, int d, int64_t ld,
+                                                           const double* __restrict__ mean, const double* __restrict__ stdv,
+                                                           unsigned long long* __restrict__ out_bits) {
+    double m = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n * d; i += (int64_t)gridDim.x * 256) {
+        const int64_t r = i / d;
+        const int f = (int)(i - r * d);
+        double v = load_as_f64(x + r * ld + f);
+        if (mean) v = (v - mean[f]) / stdv[f];
+        if (fabs(v) <= kFilterHi) m = fmax(m, fabs(v));
+    }
+    m = wave_max_f64(m);
+    __shared__ double wm[4];
+    if ((threadIdx.x & 63) == 0) wm[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        m = fmax(fmax(wm[0], wm[1]), fmax(wm[2], wm[3]));
+        if (m > 0.0) atomicMax(out_bits, (unsigned long long)__double_as_longlong(m));
+    }
 }
 
 template <typename T, int DP, bool WHITEN>
@@ -505,17 +543,17 @@ __device__ __forceinline__ void filter_close_iteration(const unsigned long long*
 }
 
 // ---------------------------------------------------------------------------------------------------------
-template <typename T, int NM, int NF, bool ACCUM, bool WHITEN>
-__global__ __launch_bounds__(64 * filter_waves(NM)) void kmeans_filter_kernel(
+template <typename T, int DP, int NF, bool ACCUM, bool WHITEN>
+__global__ __launch_bounds__(64 * filter_waves(DP, ACCUM)) void kmeans_filter_kernel(
     const T* __restrict__ x, int64_t n, int d, int64_t ld, int k, const double* __restrict__ mean,
     const double* __restrict__ stdv, const uint4* __restrict__ image, const double* __restrict__ centers,
     int32_t* __restrict__ labels,
     double* __restrict__ mindist, const FitState* __restrict__ st, unsigned long long* __restrict__ sums,
     unsigned long long* __restrict__ counts, unsigned long long* __restrict__ n_scanned, double* upd_centers,
     unsigned int* __restrict__ ticket) {
-    using S = FilterShape<NM>;
-    constexpr int kFilterWaves = filter_waves(NM);
-    constexpr int kMT = 64 * kFilterWaves, DP = S::DP, RF = S::RF, RQ = filter_rowq(NM);
+    using S = FilterShape<DP>;
+    constexpr int kFilterWaves = filter_waves(DP, ACCUM);
+    constexpr int kMT = 64 * kFilterWaves, RF = S::RF, RQ = kFilterRowQ;
     static_assert(NF == 4, "one frame group per lane quarter: a unit is 64 frames, one per lane in the candidate pick");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     if constexpr (ACCUM) {
@@ -524,12 +562,14 @@ __global__ __launch_bounds__(64 * filter_waves(NM)) void kmeans_filter_kernel(
     const int k16 = (k + 15) & ~15;
     const int n_tiles = ((k16 / 16) + 1) & ~1;            // even: the loop takes tile pairs
     uint4* img = reinterpret_cast<uint4*>(smem_raw);
-    float* tab = reinterpret_cast<float*>(img + (size_t)n_tiles * NM * 64);
-    double* hs = reinterpret_cast<double*>(tab + (size_t)n_tiles * 16 * RF);
+    float* tab = reinterpret_cast<float*>(img + (size_t)n_tiles * 64);
+    float* cz = tab + (size_t)n_tiles * 16 * RF;
+    double* hs = reinterpret_cast<double*>(cz + (size_t)n_tiles * 16);
     unsigned long long* lsum = reinterpret_cast<unsigned long long*>(hs + (size_t)n_tiles * 16);
     unsigned long long* lcnt = lsum + (ACCUM ? (size_t)k * d : 0);
     __shared__ int unit_ctr;
     __shared__ int any_bad;
+    __shared__ unsigned long long cmax_bits;
     // (the wave number through readfirstlane: the compiler then knows that unit numbers are uniform and addresses the
     // image and coordinate loads as scalar base + lane offset + immediate, not with a 64-bit register pair per load)
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -538,6 +578,7 @@ __global__ __launch_bounds__(64 * filter_waves(NM)) void kmeans_filter_kernel(
     if (tid == 0) {
         unit_ctr = kFilterWaves;
         any_bad = 0;
+        cmax_bits = 0ull;
     }
     KSTAMP_INIT
     if constexpr (ACCUM) {
@@ -549,40 +590,53 @@ __global__ __launch_bounds__(64 * filter_waves(NM)) void kmeans_filter_kernel(
     const int64_t units_per_block = (n_units + gridDim.x - 1) / gridDim.x;
     const int64_t u_begin = (int64_t)blockIdx.x * units_per_block;
     const int64_t u_end = min(n_units, u_begin + units_per_block);
-    // image pieces of this lane: quarter q of instruction m reads piece filter_piece(q, m) of its frame's row
-    int voff[NM];
-#pragma unroll
-    for (int m = 0; m < NM; ++m) voff[m] = j16 * RQ + filter_piece<NM>(q, m);
+    // image piece of this lane: quarter q reads piece filter_piece(q) of its frame's row
+    const int voff = j16 * RQ + filter_piece(q);
+    // the frames' scale 2^e_x, in the word after the image rows (kmeans_pack_kernel)
+    const int ex = reinterpret_cast<const int*>(image + (size_t)((n + 63) & ~(int64_t)63) * RQ)[2];
 
     int64_t unit = u_begin + wave;
-    v8bf b[NF][NM];
+    v8h b[NF];
     // (the image holds whole units of rows, msm_kmeans_image_bytes: no clamping at the end of the shard, and the loads
     // are scalar base + lane offset + immediate)
     auto load_images = [&](int64_t un) {
         const uint4* ub = image + un * (kUnit * RQ);
 #pragma unroll
-        for (int u = 0; u < NF; ++u)
-#pragma unroll
-            for (int m = 0; m < NM; ++m) b[u][m] = __builtin_bit_cast(v8bf, ub[voff[m] + u * 16 * RQ]);
+        for (int u = 0; u < NF; ++u) b[u] = __builtin_bit_cast(v8h, ub[voff + u * 16 * RQ]);
     };
     if (unit < u_end) load_images(unit);   // the first unit's images travel while the tables are built
 
     // ---- centre tables, built by every workgroup for itself: wave w stages tiles w, w + W, ... straight into the
     // LDS (a separate staging launch + 113 KB of copies per workgroup did the same for 4.7 us more per pass);
-    // padding tiles too (their rows carry the -3.4e38 sentinel); two tiles per trip, both fetched before either is built
+    // padding tiles too (their rows carry the -3e38 sentinel); two tiles per trip, both fetched before either is built.
+    // The centres' scale 2^e_c comes first: max |c| over the table (non-negative doubles order like their bits; NaN
+    // loses, an infinite coordinate fails the range guard anyway).  (Taking it from the fetched tiles instead kept
+    // their registers alive across the barrier: scratch memory.)
+    {
+        double cm = 0.0;
+        for (int i = tid; i < k * d; i += kMT) cm = fmax(cm, fabs(centers[i]));
+        cm = wave_max_f64(cm);
+        if (lane == 0 && cm > 0.0) atomicMax(&cmax_bits, (unsigned long long)__double_as_longlong(cm));
+    }
+    __syncthreads();
+    // (uniform values through readfirstlane: scalar registers, not VGPRs, for the rest of the kernel)
+    const int ec = __builtin_amdgcn_readfirstlane(filter_scale_exp(__longlong_as_double((long long)cmax_bits)));
+    const int exc = ex + ec;
     for (int t = wave; t < n_tiles; t += 2 * kFilterWaves) {
         const int t2 = t + kFilterWaves;
         double c0[kStageRegs], c1[kStageRegs], r0[DP], r1[DP];
         filter_stage_fetch<DP>(t, lane, centers, k, d, c0, r0);
         if (t2 < n_tiles) filter_stage_fetch<DP>(t2, lane, centers, k, d, c1, r1);
-        filter_stage_build<NM>(t, lane, reinterpret_cast<unsigned short*>(img + (size_t)t * NM * 64), c0, r0, k, d, tab, hs,
-                               &any_bad);
+        filter_stage_build<DP>(t, lane, reinterpret_cast<unsigned short*>(img + (size_t)t * 64), c0, r0, k, d, ec, exc, tab, cz,
+                               hs, &any_bad);
         if (t2 < n_tiles)
-            filter_stage_build<NM>(t2, lane, reinterpret_cast<unsigned short*>(img + (size_t)t2 * NM * 64), c1, r1, k, d, tab, hs,
-                                   &any_bad);
+            filter_stage_build<DP>(t2, lane, reinterpret_cast<unsigned short*>(img + (size_t)t2 * 64), c1, r1, k, d, ec, exc, tab,
+                                   cz, hs, &any_bad);
     }
     __syncthreads();
-    const bool all_scan = any_bad != 0;
+    // the upper bounds come out in units of 2^-(e_x + e_c): R goes back to the units of the fp32 scores with this
+    const float inv_scale_u = __int_as_float((127 - exc) << 23);   // 2^-exc, |exc| <= 120: built in a scalar register
+    const bool all_scan = __builtin_amdgcn_readfirstlane(any_bad) != 0;
     KSTAMP(0);
 
     unsigned long long my_scans = 0;
@@ -681,24 +735,16 @@ __global__ __launch_bounds__(64 * filter_waves(NM)) void kmeans_filter_kernel(
         for (int it = 0; it < iters; ++it) {
 #endif
             const int jt = 2 * it;
-            v8bf aa[NM], ab[NM];
-#pragma unroll
-            for (int m = 0; m < NM; ++m) {
-                aa[m] = __builtin_bit_cast(v8bf, img[((jt + 0) * NM + m) * 64 + lane]);
-                ab[m] = __builtin_bit_cast(v8bf, img[((jt + 1) * NM + m) * 64 + lane]);
-            }
+            const v8h aa = __builtin_bit_cast(v8h, img[(jt + 0) * 64 + lane]);
+            const v8h ab = __builtin_bit_cast(v8h, img[(jt + 1) * 64 + lane]);
+            // C: -(1 - kappa) h of this lane's four centres (rows 4 q .. 4 q + 3 of the tile), shared by the frame groups
+            const v4f32 ca = *reinterpret_cast<const v4f32*>(cz + (jt + 0) * 16 + 4 * q);
+            const v4f32 cb = *reinterpret_cast<const v4f32*>(cz + (jt + 1) * 16 + 4 * q);
             v4f32 acca[NF], accb[NF];
 #pragma unroll
             for (int u = 0; u < NF; ++u) {
-                acca[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aa[0], b[u][0], (v4f32){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-                accb[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab[0], b[u][0], (v4f32){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-            }
-            if constexpr (NM == 2) {
-#pragma unroll
-                for (int u = 0; u < NF; ++u) {
-                    acca[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aa[1], b[u][1], acca[u], 0, 0, 0);
-                    accb[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ab[1], b[u][1], accb[u], 0, 0, 0);
-                }
+                acca[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(aa, b[u], ca, 0, 0, 0);
+                accb[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ab, b[u], cb, 0, 0, 0);
             }
 #pragma unroll
             for (int u = 0; u < NF; ++u) {
@@ -719,7 +765,7 @@ __global__ __launch_bounds__(64 * filter_waves(NM)) void kmeans_filter_kernel(
         // the images of the next unit replace them
         bool guard[NF];
 #pragma unroll
-        for (int u = 0; u < NF; ++u) guard[u] = q == 3 && __builtin_bit_cast(unsigned short, b[u][NM - 1][7]) == 0x7F80;
+        for (int u = 0; u < NF; ++u) guard[u] = q == 3 && __builtin_bit_cast(unsigned short, b[u][7]) == 0x7C00;
         // ---- the loads of the next round go out now: the next unit's images, this unit's coordinates (lane = frame:
         // lane (q, j16) takes frame j16 of group q)
         if (nxt < u_end) load_images(nxt);
@@ -755,6 +801,9 @@ __global__ __launch_bounds__(64 * filter_waves(NM)) void kmeans_filter_kernel(
             Ru = q == u ? R_u : Ru;
         }
 #endif
+        // R in the units of the fp32 scores: a power of two, exact unless the result is subnormal; the 2^-149 added
+        // before the one rounding keeps it an upper bound there too (infinities stay)
+        Ru = __builtin_fmaf(Ru, inv_scale_u, 1.40129846e-45f);
         KSTAMP(3);
         // ---- step 3, one frame per lane: its eight candidates (rows 4 gs .. 4 gs + 3 of both tiles of the winning
         // pair) scored in fp32 one after the other: best and second-best score, the index of the best, the largest S bound
@@ -778,7 +827,7 @@ __global__ __launch_bounds__(64 * filter_waves(NM)) void kmeans_filter_kernel(
         for (int c = 0; c < 8; ++c) {
             const float4* r4 = reinterpret_cast<const float4*>(p_row + ((c & 3) + 16 * (c >> 2)) * RF);
             float a = 0.f, h, cn;
-            if constexpr (NM == 1) {
+            if constexpr (DP == 4) {
                 const float4 r0 = r4[0], r1 = r4[1];
                 a = __builtin_fmaf(r0.x, pz[0], a);
                 a = __builtin_fmaf(r0.y, pz[1], a);
@@ -871,7 +920,7 @@ __global__ __launch_bounds__(64 * filter_waves(NM)) void kmeans_filter_kernel(
             for (int c = lane; c < n_tiles * 16; c += 64) {
                 const float4* r4 = reinterpret_cast<const float4*>(tab + (size_t)c * RF);
                 float a = 0.f, h, cn;
-                if constexpr (NM == 1) {
+                if constexpr (DP == 4) {
                     const float4 r0 = r4[0], r1 = r4[1];
                     a = __builtin_fmaf(r0.x, zf[0], a);
                     a = __builtin_fmaf(r0.y, zf[1], a);
@@ -1001,11 +1050,10 @@ __global__ __launch_bounds__(64 * filter_waves(NM)) void kmeans_filter_kernel(
 // sums of an accumulate pass must fit the LDS too.
 static inline size_t filter_lds_bytes(int k, int d, bool accum) {
     if (d > kFilterMaxD) return 0;
-    const int nm = filter_nm(d);
     const int k16 = (k + 15) & ~15;
     const int n_tiles = ((k16 / 16) + 1) & ~1;
-    const size_t tile_bytes = nm == 1 ? FilterShape<1>::kTileBytes : FilterShape<2>::kTileBytes;
+    const size_t tile_bytes = filter_dp(d) == 4 ? FilterShape<4>::kTileBytes : FilterShape<10>::kTileBytes;
     const size_t total = (size_t)n_tiles * tile_bytes + (accum ? (size_t)k * (d + 1) * sizeof(unsigned long long) : 0);
-    const size_t cap = 160 * 1024 - 64;   // static __shared__ words of the kernel (two ints)
+    const size_t cap = 160 * 1024 - 64;   // static __shared__ words of the kernel (two ints, one u64)
     return total <= cap ? total : 0;
 }

@@ -672,8 +672,9 @@ class Engine:
         return int(out.value)
 
     def kmeans_pack(self, x: DeviceArray, *, mean: DeviceArray | None = None, std: DeviceArray | None = None,
-                    image: DeviceArray | None = None) -> DeviceArray | None:
-        """Frame images for repeated k-means passes over the same frames; None when d is outside the filter's range."""
+                    image: DeviceArray | None = None, absmax: DeviceArray | None = None) -> DeviceArray | None:
+        """Frame images for repeated k-means passes over the same frames; None when d is outside the filter's range.
+        absmax: one device f64 >= max |x| (e.g. slot 2 of a fit state); without it the library finds the maximum."""
         n, d = x.shape
         nbytes = self.kmeans_image_bytes(n, d)
         if nbytes == 0:
@@ -681,9 +682,9 @@ class Engine:
         image = image if image is not None else self.empty((nbytes,), np.uint8)
         if image.nbytes < nbytes:
             raise ValueError(f"image buffer holds {image.nbytes} bytes, {nbytes} needed")
-        check(lib.msm_kmeans_pack(self.handle, x.ptr, _dtype_code(x.dtype), n, d, d,
-                                  mean.ptr if mean is not None else None, std.ptr if std is not None else None,
-                                  image.ptr), self.handle)
+        check(lib.msm_kmeans_pack_bounded(self.handle, x.ptr, _dtype_code(x.dtype), n, d, d,
+                                          mean.ptr if mean is not None else None, std.ptr if std is not None else None,
+                                          absmax.ptr if absmax is not None else None, image.ptr), self.handle)
         return image
 
     def kmeans_filter_scanned(self, reset: bool = False) -> int:
@@ -694,16 +695,23 @@ class Engine:
 
     def mfma_bf16_probe(self, a_bits: np.ndarray, b_bits: np.ndarray, c: np.ndarray) -> np.ndarray:
         """D = A B + C through one v_mfma_f32_16x16x32_bf16 per tile: a_bits [t, 16, 32], b_bits [t, 32, 16] uint16
-        (raw bf16 patterns), c [t, 16, 16] float32 (host arrays).  The hardware rule behind the k-means filter."""
+        (raw bf16 patterns), c [t, 16, 16] float32 (host arrays)."""
+        return self._mfma_probe(lib.msm_mfma_bf16_probe, a_bits, b_bits, c)
+
+    def mfma_f16_probe(self, a_bits: np.ndarray, b_bits: np.ndarray, c: np.ndarray) -> np.ndarray:
+        """The same through one v_mfma_f32_16x16x32_f16 per tile (raw fp16 patterns): the hardware rule behind the
+        k-means filter."""
+        return self._mfma_probe(lib.msm_mfma_f16_probe, a_bits, b_bits, c)
+
+    def _mfma_probe(self, fn, a_bits: np.ndarray, b_bits: np.ndarray, c: np.ndarray) -> np.ndarray:
         a = np.ascontiguousarray(a_bits, np.uint16)
         b = np.ascontiguousarray(b_bits, np.uint16)
         cc = np.ascontiguousarray(c, np.float32)
         t = a.shape[0]
         if a.shape != (t, 16, 32) or b.shape != (t, 32, 16) or cc.shape != (t, 16, 16):
-            raise ValueError("mfma_bf16_probe: shapes must be [t,16,32], [t,32,16], [t,16,16]")
+            raise ValueError("mfma probe: shapes must be [t,16,32], [t,32,16], [t,16,16]")
         out = np.empty((t, 16, 16), np.float32)
-        check(lib.msm_mfma_bf16_probe(self.handle, a.ctypes.data, b.ctypes.data, cc.ctypes.data, out.ctypes.data, t),
-              self.handle)
+        check(fn(self.handle, a.ctypes.data, b.ctypes.data, cc.ctypes.data, out.ctypes.data, t), self.handle)
         return out
 
     def kmeans_lloyd_pass(self, x: DeviceArray, centers: DeviceArray, state: DeviceArray, sums: DeviceArray,

@@ -462,7 +462,8 @@ class ShardedMSM:
         acc_sums, acc_counts = acc.view((k * d,), np.int64), acc.view((k,), np.int64, offset_elems=k * d)
         self.labels.fill_bytes_(0xFF)          # the centre each frame is booked under: none yet
         if self.km_image is not None:
-            eng.kmeans_pack(self.Y, image=self.km_image)
+            # the frames' scale from max |Y| in slot 2 of the fit state (left there by the projection or fit_begin)
+            eng.kmeans_pack(self.Y, image=self.km_image, absmax=b["fit_state"].view((1,), offset_elems=2))
         for _ in range(cfg.kmeans_iters):
             if self.time_accum:
                 e0, e1 = eng.event(), eng.event()
