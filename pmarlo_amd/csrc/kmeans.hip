@@ -875,6 +875,10 @@ msm_status launch_mfma(msm_ctx* ctx, const T* x, int64_t n, int d, int64_t ld, c
         chalf_g = (double*)ctx->aux;
         hipLaunchKernelGGL(chalf_kernel, dim3((k + 255) / 256), dim3(256), 0, ctx->stream, centers, k, d, chalf_g);
     }
+    if (getenv("MSM_KMEANS_DEBUG"))   // the instantiation and launch shape, one line per launch (see filter_enabled)
+        fprintf(stderr, "msm_kmeans: fp64 T=%s n=%lld d=%d k=%d KS=%d NF=%d MT=%d ACCUM=%d FOLD=%d MULTI=%d tile_k=%d lds_acc=%d grid=%d lds=%zu\n",
+                sizeof(T) == 4 ? "f32" : "f64", (long long)n, d, k, KS, NF, kMT, (int)ACCUM, (int)foldm, (int)multi, tile_k,
+                lds_acc, grid, lds);
     if (lds > 48 * 1024)
         MSM_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(kMT), lds, ctx->stream, x, n, d, ld, centers, k, mean, stdv, tile_k,
@@ -929,6 +933,9 @@ bool filter_enabled() {
     }();
     return on;
 }
+// MSM_KMEANS_DEBUG (any value, read at every launch): one line on stderr per assign / accumulate launch, either
+// "msm_kmeans: filter T= n= d= k= ACCUM=" or "msm_kmeans: fp64 T= n= d= k= KS= NF= MT= ACCUM= FOLD= MULTI= tile_k=
+// lds_acc= grid= lds=": the kernel instantiation that ran.  tests/_kmeans_ref.py restates the rule; the GPU tests compare.
 
 // whole units of 64 rows (the filter kernel loads a unit without clamping), then one uint4: [max |x| bound | e_x | pad]
 size_t filter_image_bytes(int64_t n, int) { return (size_t)((n + 63) & ~(int64_t)63) * 16 * kFilterRowQ + 16; }
@@ -1023,6 +1030,9 @@ msm_status dispatch_mfma(msm_ctx* ctx, const T* x, int64_t n, int d, int64_t ld,
     // launch is still due
     if (folded) *folded = false;
     if (filter_fits(k, d, ACCUM)) {
+        if (getenv("MSM_KMEANS_DEBUG"))
+            fprintf(stderr, "msm_kmeans: filter T=%s n=%lld d=%d k=%d ACCUM=%d\n", sizeof(T) == 4 ? "f32" : "f64", (long long)n,
+                    d, k, (int)ACCUM);
         if (!image) {
             msm_status rs = msm_reserve_km_image(ctx, filter_image_bytes(n, d));
             if (rs != MSM_OK) return rs;
