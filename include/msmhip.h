@@ -321,6 +321,37 @@ msm_status msm_project_finite(msm_ctx* ctx, const void* d_x, msm_dtype dtype, in
  * S/features/deeptica/core/trainer_api.py:646-651). d_sweeps int32 [1] may be NULL. */
 msm_status msm_eigh(msm_ctx* ctx, const double* d_a, int n, double* d_w, double* d_v, int* d_sweeps);
 
+/* Per-segment autocorrelation of the standardised columns at n_lag lags: the frame passes of
+ * _autocorrelation_curve (S/analysis/diagnostics.py:247-351), which walks the split once per segment and lag.
+ * For segment s = rows [start, stop) of length L, in fp64 whatever the input type:
+ *   mean_f = column mean over the segment, var_f = mean of (x - mean_f)^2 (ddof = 0);
+ *   column f is valid when var_f > var_floor (the reference passes 1e-8, an absolute number; a column that
+ *   holds a non-finite value has a NaN variance and is not valid); d_nvalid[s] = m = number of valid columns;
+ *   z = (x - mean_f) / sqrt(var_f) on the valid columns;
+ *   d_value[s][l] = sum_{valid f} sum_{t = start}^{stop - tau - 1} z[t][f] z[t + tau][f] / ((L - tau) m)
+ *   for 1 <= tau = h_lags[l] < L, and NaN when tau >= L, L <= 1 or m = 0.  Pairs never cross a segment.
+ * The weighting of the segments into one curve is left to the host (pmarlo_amd/analysis/diagnostics.py).
+ * Means and variances are formed first and the products from centred values, so a large common offset
+ * costs no digits.  Per-workgroup partial sums go through a slab and are added in a fixed order: two calls
+ * on the same input give the same bits.  The segments and lags travel through the context's device table,
+ * any number of each; the launch sequence has 4 + 2 ceil(n_lag / 32) kernels whatever n_seg is.
+ *
+ * d_x [n, ld] f32 / f64, 1 <= F <= 256 (MSM_ERR_UNSUPPORTED beyond), ld >= F, n <= 2^31.
+ * h_seg_start / h_seg_stop int64 [n_seg], n_seg >= 1, 0 <= start <= stop <= n (not clipped: anything else is
+ * MSM_ERR_INVALID); h_lags int32 [n_lag], every lag >= 1.
+ * d_value f64 [n_seg][n_lag] OVERWRITTEN; d_nvalid int32 [n_seg] OVERWRITTEN (may be NULL).
+ * Not under graph capture. */
+msm_status msm_autocorr_lagscan(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n, int F, int64_t ld,
+                                const int64_t* h_seg_start, const int64_t* h_seg_stop, int n_seg,
+                                const int32_t* h_lags, int n_lag, double var_floor, double* d_value,
+                                int32_t* d_nvalid);
+
+/* d_out [n, pa + pb] f64 = [A | B]: the two column blocks side by side, so that ONE msm_lagged_moments(lag = 0)
+ * pass over d_out gives the joint second moments the canonical correlations are made of
+ * (_canonical_correlations, S/analysis/diagnostics.py:173-221).  A is [n, lda], B is [n, ldb], f32 or f64 each. */
+msm_status msm_hstack_f64(msm_ctx* ctx, const void* d_a, msm_dtype dtype_a, int pa, int64_t lda, const void* d_b,
+                          msm_dtype dtype_b, int pb, int64_t ldb, int64_t n, double* d_out);
+
 /* ------------------------------------------------------------------ */
 /* k-means                                                              */
 /* ------------------------------------------------------------------ */

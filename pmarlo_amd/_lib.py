@@ -78,6 +78,8 @@ _PROTOTYPES: dict[str, tuple] = {
     "msm_project": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _i64, _vp]),
     "msm_project_finite": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _i64, _vp]),
     "msm_eigh": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp]),
+    "msm_autocorr_lagscan": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _vp, _i32, _vp, _i32, _f64, _vp, _vp]),
+    "msm_hstack_f64": (_i32, [_vp, _vp, _i32, _i32, _i64, _vp, _i32, _i32, _i64, _i64, _vp]),
     "msm_kmeans_assign": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _i32, _vp, _vp, _vp, _vp]),
     "msm_kmeans_fit": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _vp, _i32, C.c_uint64, _i32, _i32, _f64, _vp, _vp]),
     "msm_kmeans_fit_begin": (

@@ -98,6 +98,11 @@ msm_status msm_build_segtab(msm_ctx* ctx, int64_t n, const int64_t* h_start,
                             const int64_t* h_stop, int n_seg, int lag, int stride,
                             SegTab* out, int table_slot);
 
+// Copies `bytes` of host data into the context's device table (through its pinned staging buffer, on the
+// context's stream) and returns the device address.  The table is shared: it holds one caller's data at a
+// time, until the next msm_build_segtab / msm_upload_table on the same context.  Not under graph capture.
+msm_status msm_upload_table(msm_ctx* ctx, const void* h_src, size_t bytes, const void** d_out);
+
 __device__ __forceinline__ int64_t seg_pair_to_frame(const SegTab& st, int64_t p) {
     if (!st.use_table) {
         int s = 0;

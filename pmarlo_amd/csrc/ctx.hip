@@ -71,6 +71,19 @@ static msm_status reserve_tables(msm_ctx* ctx, size_t bytes) {
     return MSM_OK;
 }
 
+msm_status msm_upload_table(msm_ctx* ctx, const void* h_src, size_t bytes, const void** d_out) {
+    if (ctx->capturing)
+        return msm_fail(ctx, MSM_ERR_UNSUPPORTED, "a device table cannot be uploaded under graph capture");
+    msm_status rs = reserve_tables(ctx, bytes);
+    if (rs != MSM_OK) return rs;
+    // the staging buffer may still feed an earlier async copy
+    MSM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    memcpy(ctx->pinned, h_src, bytes);
+    MSM_HIP(ctx, hipMemcpyAsync(ctx->dtab, ctx->pinned, bytes, hipMemcpyHostToDevice, ctx->stream));
+    *d_out = ctx->dtab;
+    return MSM_OK;
+}
+
 msm_status msm_build_segtab(msm_ctx* ctx, int64_t n, const int64_t* h_start,
                             const int64_t* h_stop, int n_seg, int lag, int stride,
                             SegTab* out, int table_slot) {

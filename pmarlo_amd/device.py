@@ -485,6 +485,36 @@ class Engine:
                  int(lag), shift.ptr, int(bool(assume_finite)), out.ptr), self.handle)
         return out
 
+    def autocorr_lagscan(self, x: DeviceArray, lags: Sequence[int], *, starts=None, stops=None,
+                         var_floor: float = 1e-8, ld: int | None = None):
+        """Per-segment autocorrelation of the standardised columns of x [n, F] at every lag ->
+        (values f64 [n_seg, n_lag], valid columns int32 [n_seg]) device arrays (msm_autocorr_lagscan).
+        Any number of segments and lags; ``ld``: row stride in elements when x is a wider buffer's left block."""
+        n, F = x.shape
+        lags_arr = np.ascontiguousarray(lags, np.int64).reshape(-1)
+        if lags_arr.size and (lags_arr.min() < 1 or lags_arr.max() > np.iinfo(np.int32).max):
+            raise ValueError("lags must be integers in [1, 2^31)")
+        lags_arr = lags_arr.astype(np.int32)
+        if starts is None:
+            starts, stops = segments_to_bounds(None, n)
+        starts, stops = self._seg_ptrs(starts, stops)
+        value = self.empty((len(starts), len(lags_arr)), np.float64)
+        nvalid = self.empty((len(starts),), np.int32)
+        check(lib.msm_autocorr_lagscan(self.handle, x.ptr, _dtype_code(x.dtype), n, F, int(F if ld is None else ld),
+                                       starts.ctypes.data, stops.ctypes.data, len(starts), lags_arr.ctypes.data,
+                                       len(lags_arr), float(var_floor), value.ptr, nvalid.ptr), self.handle)
+        return value, nvalid
+
+    def hstack(self, a: DeviceArray, b: DeviceArray) -> DeviceArray:
+        """[a | b] as one float64 device array [n, pa + pb]; both [n, *], float32 or float64."""
+        (n, pa), (nb, pb) = a.shape, b.shape
+        if n != nb:
+            raise ValueError(f"hstack: row counts differ ({n} vs {nb})")
+        out = self.empty((n, pa + pb), np.float64)
+        check(lib.msm_hstack_f64(self.handle, a.ptr, _dtype_code(a.dtype), pa, pa, b.ptr, _dtype_code(b.dtype), pb, pb,
+                                 n, out.ptr), self.handle)
+        return out
+
     def onesided_tica_eigenvalues(self, moments: DeviceArray, F: int, clip: float = 1e-12) -> DeviceArray:
         """Descending eigenvalues of the reference's in-repo estimator from one-sided moments."""
         out = self.empty((F,), np.float64)
