@@ -14,6 +14,7 @@
 // partner row lies inside the tile is served from there, every other partner is read from global memory,
 // so the traffic is about (3 + number of lags longer than the tile) * n * F * sizeof(T).
 #include "common.h"
+#include "wave.h"
 
 #include <algorithm>
 #include <cstring>
@@ -209,7 +210,7 @@ __global__ __launch_bounds__(kThreads) void autocorr_lag_kernel(
                         if (f >= F) { f -= F; ++row; }
                     }
                 }
-                for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+                acc = wave_sum_down(acc);
                 if ((tid & 63) == 0) s_acc[l][wave] += acc;  // a slot belongs to one wave: tiles add in order
             }
         }

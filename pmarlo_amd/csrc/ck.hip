@@ -6,6 +6,7 @@
 // v_mfma_f64_16x16x4_f64 per 16 x 16 output tile and 4 inner indices, i.e. every output element is
 // the plain ascending-k FMA chain (bit-reproducible, restated in oracle/msm_oracle.c).
 #include "common.h"
+#include "wave.h"
 
 namespace {
 
@@ -56,18 +57,6 @@ __global__ __launch_bounds__(256) void gemm_f64_kernel(const double* __restrict_
     }
 }
 
-// fixed-order block reduction (same tree for every launch)
-__device__ double block_sum_1024(double v, double* red) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = 0.0;
-    if (threadIdx.x == 0)
-        for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += red[i];
-    return t;  // valid in thread 0
-}
-
 // out[0] = mean((P - Q)^2)
 __global__ __launch_bounds__(1024) void mse_kernel(const double* __restrict__ P, int64_t ldp, const double* __restrict__ Q,
                                                    int64_t ldq, int n, double* __restrict__ out) {
@@ -78,7 +67,7 @@ __global__ __launch_bounds__(1024) void mse_kernel(const double* __restrict__ P,
         const double d = P[(size_t)i * ldp + j] - Q[(size_t)i * ldq + j];
         acc = fma(d, d, acc);
     }
-    const double t = block_sum_1024(acc, red);
+    const double t = block_sum_lane0(acc, red);
     if (threadIdx.x == 0) out[0] = t / ((double)n * (double)n);
 }
 
@@ -96,11 +85,11 @@ __global__ __launch_bounds__(1024) void diff_norms_kernel(const double* __restri
         ref += fabs(q);
         l2 = fma(d, d, l2);
     }
-    l1 = block_sum_1024(l1, red);
+    l1 = block_sum_lane0(l1, red);
     __syncthreads();
-    ref = block_sum_1024(ref, red);
+    ref = block_sum_lane0(ref, red);
     __syncthreads();
-    l2 = block_sum_1024(l2, red);
+    l2 = block_sum_lane0(l2, red);
     if (threadIdx.x == 0) { out[0] = l1; out[1] = ref; out[2] = l2; }
 }
 
@@ -117,7 +106,7 @@ __global__ __launch_bounds__(1024) void multinomial_se_kernel(const double* __re
         const double p = P[(size_t)i * ldp + j];
         acc += p * (1.0 - p) / Ni;
     }
-    const double t = block_sum_1024(acc, red);
+    const double t = block_sum_lane0(acc, red);
     if (threadIdx.x == 0) out[0] = sqrt(t / ((double)n * (double)n));
 }
 

@@ -12,6 +12,7 @@
 // at least as many pairs as bins (the bench shape) take the two-pass bucket path
 // further down instead: no global atomics at all.
 #include "common.h"
+#include "wave.h"
 
 #include <cstdlib>
 
@@ -27,17 +28,11 @@ struct BinT { using lds_t = unsigned int; using out_t = unsigned long long; };
 template <>
 struct BinT<true> { using lds_t = double; using out_t = double; };
 
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
 // One same-address global atomic per WORKGROUP: thousands of per-wave atomics on one counter
 // serialise in L2 and used to cost more than the whole binning pass.
 __device__ __forceinline__ void block_add_u64(unsigned long long v, unsigned long long* dst) {
     __shared__ unsigned long long wave_part[kThreads / 64];
-    v = wave_sum_u64(v);
+    v = wave_sum_down(v);
     if ((threadIdx.x & 63) == 0) wave_part[threadIdx.x >> 6] = v;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -308,7 +303,7 @@ __global__ __launch_bounds__(kThreads) void count_bucket_bin_kernel(const unsign
         unsigned long long v = 0;
         for (int w = tid; w < chunks; w += kThreads) v += valid[w];
         __shared__ unsigned long long wave_part[kThreads / 64];
-        v = wave_sum_u64(v);
+        v = wave_sum_down(v);
         if ((tid & 63) == 0) wave_part[tid >> 6] = v;
         __syncthreads();
         if (tid == 0) {

@@ -10,6 +10,7 @@
 // V.  A and V live in LDS (odd row stride, conflict-free column walks) whenever
 // 2 n (n+1) doubles fit; otherwise in global scratch.
 #include "common.h"
+#include "wave.h"
 
 // Diagnostic build only (tools/probe/jacobi_probe.hip): per-phase cycle stamps.
 #ifdef MSM_JACOBI_STAMPS
@@ -47,20 +48,6 @@ struct JacobiShared {
     double bc[4];
     int ibc[4];
 };
-
-__device__ __forceinline__ double block_sum(double v, JacobiShared* sh) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh->red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += sh->red[i];
-        sh->bc[0] = t;
-    }
-    __syncthreads();
-    return sh->bc[0];
-}
 
 // Short-latency fp64 reciprocal / reciprocal square root: hardware seed plus two
 // Newton steps (the IEEE division / sqrt expansions are 3-4x longer dependent chains,
@@ -149,8 +136,8 @@ __device__ __forceinline__ int jacobi_eigh(double* A, double* V, int n, int ld, 
             const double v = A[r * ld + c];
             if (r == c) dia = fma(v, v, dia); else off = fma(v, v, off);
         }
-        off = block_sum(off, sh);
-        dia = block_sum(dia, sh);
+        off = block_sum_bcast(off, sh->red, sh->bc);
+        dia = block_sum_bcast(dia, sh->red, sh->bc);
         // converged when ||off||_F <= n*eps*||A||_F: rounding of the rotations themselves
         // re-pollutes the zeroed entries at that level, and the eigenvalue error left
         // is second order in it.
@@ -366,8 +353,8 @@ __device__ __forceinline__ int jacobi_eigh_pipelined(double* A, double* V, int n
             const double v = A[r * ld + c];
             if (r == c) dia = fma(v, v, dia); else off = fma(v, v, off);
         }
-        off = block_sum(off, sh);
-        dia = block_sum(dia, sh);
+        off = block_sum_bcast(off, sh->red, sh->bc);
+        dia = block_sum_bcast(dia, sh->red, sh->bc);
         const double tol = (double)n * 2.220446049250313e-16;  // see jacobi_eigh
         if (off <= tol * tol * (dia + off) || off == 0.0) break;
         for (int rr = 0; rr < ring; ++rr) {
@@ -539,52 +526,6 @@ struct TriShared {
 
 typedef double tri_v4f64 __attribute__((ext_vector_type(4)));
 
-// 64-lane sum on the VALU (row DPP moves, then the two row swaps of gfx950): every lane gets the total, bit for
-// bit the same in every wave that feeds it the same numbers
-template <int CTRL>
-__device__ __forceinline__ double mov_dpp64(double x) {
-    const long long b = __double_as_longlong(x);
-    const int lo = __builtin_amdgcn_update_dpp(0, (int)b, CTRL, 0xf, 0xf, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, 0xf, 0xf, true);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
-}
-// the bare v_max_f64 / v_min_f64 (operands never NaN where these are used): fmax() on a value that came through a DPP
-// move costs an extra canonicalising v_max_f64 per call
-__device__ __forceinline__ double hw_max_f64(double a, double b) {
-    double r;
-    asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ double hw_min_f64(double a, double b) {
-    double r;
-    asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-typedef unsigned tri_v2u32 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ double sum8_dpp(double x) {   // sum over aligned groups of 8 lanes
-    x += mov_dpp64<0xB1>(x);    // quad_perm [1,0,3,2]
-    x += mov_dpp64<0x4E>(x);    // quad_perm [2,3,0,1]
-    x += mov_dpp64<0x141>(x);   // row_half_mirror
-    return x;
-}
-__device__ __forceinline__ double wave_sum_all(double x) {
-    x = sum8_dpp(x);
-    x += mov_dpp64<0x140>(x);   // row_mirror: all 16 lanes of a row hold the row sum
-    {
-        const long long b = __double_as_longlong(x);
-        const tri_v2u32 rl = __builtin_amdgcn_permlane16_swap((unsigned)b, (unsigned)b, false, false);
-        const tri_v2u32 rh = __builtin_amdgcn_permlane16_swap((unsigned)(b >> 32), (unsigned)(b >> 32), false, false);
-        x = __longlong_as_double(((long long)rh[0] << 32) | rl[0]) + __longlong_as_double(((long long)rh[1] << 32) | rl[1]);
-    }
-    {
-        const long long b = __double_as_longlong(x);
-        const tri_v2u32 rl = __builtin_amdgcn_permlane32_swap((unsigned)b, (unsigned)b, false, false);
-        const tri_v2u32 rh = __builtin_amdgcn_permlane32_swap((unsigned)(b >> 32), (unsigned)(b >> 32), false, false);
-        x = __longlong_as_double(((long long)rh[0] << 32) | rl[0]) + __longlong_as_double(((long long)rh[1] << 32) | rl[1]);
-    }
-    return x;
-}
-
 // C[i][j] = sum_k opA(i,k) opB(k,j) on the matrix cores (v_mfma_f64_16x16x4_f64; one 16 x 16 tile of C per wave
 // and trip), i < rows, j < cols, k < inner; opA = A or A', opB = B or B'.  bscale (optional) multiplies column j of
 // opB.  C must not alias A or B.  A 64^3 product costs what it costs on the VALU (the fp64 rates are equal) but
@@ -683,11 +624,6 @@ __device__ __forceinline__ int sturm_count(const TriShared* ts, int nblocks, dou
 //   write their partial u = Q v; between barrier 2 and barrier 1 of the next column they sum the partials and apply
 //   q_j -= tau v_j u.  They add nothing to the A waves' chain, which is what a column costs.
 // Rows up to k carry v_j = w_j = 0; groups of four own rows that lie entirely there are skipped.
-__device__ __forceinline__ double bcast_lane(double x, int j) {   // lane j's value to everybody; j uniform
-    const long long b = __double_as_longlong(x);
-    const int lo = __builtin_amdgcn_readlane((int)b, j), hi = __builtin_amdgcn_readlane((int)(b >> 32), j);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
-}
 template <typename F>
 __device__ __forceinline__ void hh_for_groups(int sub, int k, F&& body) {
     // own rows sub + 8 t, t = 4 g + u; group g is dead once its last row sub + 32 g + 24 <= k
@@ -892,7 +828,7 @@ __device__ __forceinline__ bool ldl_whiten_registers(const double* C, double* W,
             // row j of the matrix the multipliers come from and of the matrix this wave updates
             const double rowM = ts->part[par + src][lane];
             const double row = what == 1 ? ts->part[par + 1][lane] : rowM;
-            const double d = bcast_lane(rowM, j);
+            const double d = readlane_f64(rowM, j);
             LSTAMP(13);
             if (!(d > 0.0)) return false;   // uniform over the workgroup (see below for the idle waves)
             {
@@ -966,6 +902,8 @@ __device__ __forceinline__ bool tridiag_eigh(double* A, double* Q, double* X, in
     {   // scale to |T| <= 1 by a power of two (exact), Gershgorin bounds of the scaled matrix: wave-parallel
         const double dl = lane < n ? ts->d[lane] : 0.0, el = lane < n ? ts->e[lane] : 0.0;
         double an = fmax(fabs(dl), fabs(el));
+        // wave_max_xor (wave.h) written out, here and for `worst` below: as a call it changes the code of the index
+        // divisions around it, and the solve is one latency-bound chain
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) an = fmax(an, __shfl_xor(an, off, 64));
         double sc = 1.0;
@@ -974,11 +912,7 @@ __device__ __forceinline__ bool tridiag_eigh(double* A, double* Q, double* X, in
         const double em = lane > 0 && lane < n ? ts->e[lane - 1] * sc : 0.0;
         const double rad = fabs(em) + (lane + 1 < n ? fabs(es) : 0.0);
         double gl = lane < n ? ds - rad : 1e300, gu = lane < n ? ds + rad : -1e300;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            gl = fmin(gl, __shfl_xor(gl, off, 64));
-            gu = fmax(gu, __shfl_xor(gu, off, 64));
-        }
+        wave_minmax_xor(gl, gu);
         __syncthreads();   // every wave has read the unscaled d, e
         if (wave == 0) {
             if (lane < n) { ts->d[lane] = ds; ts->e[lane] = es; ts->de[lane] = make_double2(ds, em * em); }
@@ -1009,11 +943,8 @@ __device__ __forceinline__ bool tridiag_eigh(double* A, double* Q, double* X, in
             const double x = fma(hi - lo, frac, lo);
             const int c = sturm_count(ts, nblocks, x);
             double nlo = c <= i ? x : lo, nhi = c > i ? x : hi;
-            nlo = hw_max_f64(nlo, mov_dpp64<0xB1>(nlo)); nhi = hw_min_f64(nhi, mov_dpp64<0xB1>(nhi));
-            nlo = hw_max_f64(nlo, mov_dpp64<0x4E>(nlo)); nhi = hw_min_f64(nhi, mov_dpp64<0x4E>(nhi));
-            nlo = hw_max_f64(nlo, mov_dpp64<0x141>(nlo)); nhi = hw_min_f64(nhi, mov_dpp64<0x141>(nhi));
-            lo = nlo;
-            hi = nhi;
+            lo = row8_reduce(nlo, hw_max_f64);   // the 8 lanes of eigenvalue i agree on the tightest bracket
+            hi = row8_reduce(nhi, hw_min_f64);
         }
         if (i < n && t == 0) ts->lam[i] = 0.5 * (lo + hi);
     }
@@ -1178,7 +1109,7 @@ __device__ __forceinline__ bool tridiag_eigh(double* A, double* Q, double* X, in
             }
         }
         if (bad) worst = 1e300;
-#pragma unroll
+#pragma unroll   // written out like `an` in the bracket set-up above: see the comment there
         for (int off = 32; off > 0; off >>= 1) worst = fmax(worst, __shfl_xor(worst, off, 64));
         if (lane == 0) ts->red[wave] = worst;
         __syncthreads();
@@ -1274,7 +1205,7 @@ __global__ __launch_bounds__(kEigThreads) void tica_solve_kernel(
                 const double wv = B2[(e / n) * ld + (e % n)];
                 s = fma(wv, wv, s);
             }
-            s = block_sum(s, &sh);
+            s = block_sum_bcast(s, sh.red, sh.bc);
             if (!(s * epsilon * (1.0 + 1e-9) <= 1.0)) full_rank = ldl_whiten_registers(A, nullptr, n, epsilon, &ts, 2);
         }
     } else {
@@ -1394,12 +1325,7 @@ __global__ __launch_bounds__(kEigThreads) void tica_solve_kernel(
                 double best = lane < n ? fabs(B1[lane * ld + j]) : -1.0;
                 int bi = lane;
                 double val = lane < n ? B1[lane * ld + j] : 0.0;
-#pragma unroll
-                for (int off = 1; off < 64; off <<= 1) {
-                    const double ob = __shfl_xor(best, off, 64), ov = __shfl_xor(val, off, 64);
-                    const int oi = __shfl_xor(bi, off, 64);
-                    if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; val = ov; }
-                }
+                wave_argmax_xor(best, bi, val);
                 if (lane == 0) sgn[j] = val < 0.0 ? -1.0 : 1.0;
             }
         }

@@ -8,6 +8,7 @@
 // 423-500, no PBC): d = sqrt(max(|v|^2, eps)); angle = acos(clamp(v1.v2/(|v1||v2|)));
 // dihedral = atan2((c0 x c1).b1/|b1|, c0.c1) with c0 = b0 x b1, c1 = b1 x b2 normalised.
 #include "common.h"
+#include "wave.h"
 
 namespace {
 
@@ -114,16 +115,16 @@ __global__ __launch_bounds__(kThreads) void rg_kernel(const float* __restrict__ 
         const float* fr = xyz + t * A * 3;
         double sx = 0.0, sy = 0.0, sz = 0.0;
         for (int a = lane; a < A; a += 64) { sx += fr[3 * a]; sy += fr[3 * a + 1]; sz += fr[3 * a + 2]; }
-        for (int off = 32; off > 0; off >>= 1) {
-            sx += __shfl_xor(sx, off, 64); sy += __shfl_xor(sy, off, 64); sz += __shfl_xor(sz, off, 64);
-        }
+        sx = wave_sum_xor(sx);
+        sy = wave_sum_xor(sy);
+        sz = wave_sum_xor(sz);
         const double mx = sx / A, my = sy / A, mz = sz / A;
         double q = 0.0;
         for (int a = lane; a < A; a += 64) {
             const double dx = fr[3 * a] - mx, dy = fr[3 * a + 1] - my, dz = fr[3 * a + 2] - mz;
             q += dx * dx + dy * dy + dz * dz;
         }
-        for (int off = 32; off > 0; off >>= 1) q += __shfl_xor(q, off, 64);
+        q = wave_sum_xor(q);
         if (lane == 0) out[t * ld + col_off] = (float)sqrt(q / A);
     }
 }

@@ -14,22 +14,12 @@
 //    frame: v_mfma_f64_16x16x4_f64 with the Gaussian factors evaluated on the fly (8 exps feed 16
 //    matrix instructions per 4 frames and lane); per-workgroup slabs, fixed-order reduction.
 #include "common.h"
+#include "wave.h"
 
 namespace {
 
 constexpr int kT = 256;
 typedef double v4f64 __attribute__((ext_vector_type(4)));
-
-__device__ double block_sum(double v, double* red) {  // valid in thread 0; blockDim.x <= 1024
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = 0.0;
-    if (threadIdx.x == 0)
-        for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += red[i];
-    return t;
-}
 
 // ---------------------------------------------------------------------------------------------
 // weighted statistics of one strided coordinate.  partial[b] = {sw, sw2, swx, min, max} then a
@@ -50,11 +40,9 @@ __global__ __launch_bounds__(1024) void wstats_pass1(const double* __restrict__ 
         mn = fmin(mn, v);
         mx = fmax(mx, v);
     }
-    const double a = block_sum(sw, red), b = block_sum(sw2, red), c = block_sum(swx, red);
-    for (int off = 32; off > 0; off >>= 1) {
-        mn = fmin(mn, __shfl_down(mn, off, 64));
-        mx = fmax(mx, __shfl_down(mx, off, 64));
-    }
+    const double a = block_sum_lane0(sw, red), b = block_sum_lane0(sw2, red), c = block_sum_lane0(swx, red);
+    mn = wave_min_down(mn);
+    mx = wave_max_down(mx);
     __shared__ double rmn[16], rmx[16];
     __syncthreads();
     if ((threadIdx.x & 63) == 0) { rmn[threadIdx.x >> 6] = mn; rmx[threadIdx.x >> 6] = mx; }
@@ -89,7 +77,7 @@ __global__ __launch_bounds__(1024) void wstats_pass2(const double* __restrict__ 
         const double d = x[i * stride] - mean;
         acc = fma(w ? w[i] : 1.0, d * d, acc);
     }
-    const double t = block_sum(acc, red);
+    const double t = block_sum_lane0(acc, red);
     if (threadIdx.x == 0) partial[blockIdx.x] = t;
 }
 
@@ -175,7 +163,7 @@ __global__ __launch_bounds__(1024) void scale_to_total(double* __restrict__ h, i
     __shared__ double f;
     double acc = 0.0;
     for (int i = threadIdx.x; i < n; i += blockDim.x) acc += h[i];
-    const double t = block_sum(acc, red);
+    const double t = block_sum_lane0(acc, red);
     if (threadIdx.x == 0) f = t > 0.0 ? want_total / t : 1.0;
     __syncthreads();
     for (int i = threadIdx.x; i < n; i += blockDim.x) h[i] *= f;
@@ -197,7 +185,7 @@ __global__ __launch_bounds__(1024) void fes_finalize_kernel(const double* __rest
         if (v <= 0.0) bad |= 4;
         acc += v;
     }
-    const double t = block_sum(acc, red);
+    const double t = block_sum_lane0(acc, red);
     if (bad) atomicOr(&st, bad);
     if (threadIdx.x == 0) total = t;
     __syncthreads();
@@ -213,7 +201,7 @@ __global__ __launch_bounds__(1024) void fes_finalize_kernel(const double* __rest
         F[i] = f;
         mn = fmin(mn, f);
     }
-    for (int off = 32; off > 0; off >>= 1) mn = fmin(mn, __shfl_down(mn, off, 64));
+    mn = wave_min_down(mn);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mn;
     __syncthreads();

@@ -13,6 +13,7 @@
 //   dist = fma(-2.0, dot, csq)      csq = fma chain of c[f]*c[f]
 //   argmin with strict '<' over ascending centre index.
 #include "common.h"
+#include "wave.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -89,7 +90,7 @@ __global__ __launch_bounds__(kThreads) void absmax_kernel(const T* __restrict__ 
             m = fmax(m, fabs(v));
         }
     }
-    for (int off = 32; off > 0; off >>= 1) m = fmax(m, __shfl_down(m, off, 64));
+    m = wave_max_down(m);
     // one atomic per workgroup, and only when it can raise the running maximum: thousands of
     // same-address atomics would otherwise serialise in L2 and dominate the pass.
     // Non-negative doubles order like their bit patterns.
@@ -183,7 +184,7 @@ __global__ __launch_bounds__(1024) void kmeans_update_kernel(unsigned long long*
                 centers[i0 + c * 1024] = c_new;
             }
     }
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    acc = wave_sum_down(acc);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (clear) {
@@ -224,7 +225,7 @@ __global__ __launch_bounds__(1024) void kmeans_update_wide_kernel(unsigned long 
             centers[i] = c_new;
         }
     }
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    acc = wave_sum_down(acc);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (clear) {
@@ -254,7 +255,7 @@ __global__ __launch_bounds__(1024) void sum_partial_kernel(const double* __restr
     const int64_t chunk = (n + gridDim.x - 1) / gridDim.x;
     const int64_t a = (int64_t)blockIdx.x * chunk, b = min(a + chunk, n);
     for (int64_t i = a + threadIdx.x; i < b; i += blockDim.x) acc += v[i];
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    acc = wave_sum_down(acc);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -301,14 +302,6 @@ typedef double v4f64 __attribute__((ext_vector_type(4)));
 // workgroup size of the matrix-core kernel: 16 waves (4 per SIMD, <= 128 VGPRs, two frame groups
 // per wave) while the frame fits 16 features, 8 waves (<= 256 VGPRs) for wider frames
 constexpr int kMTNarrow = 1024, kMTWide = 512;
-
-// one v_max_f64: fmax() would first canonicalise both operands (two more VALU ops each);
-// NaNs lose against numbers here too.  The caller pads the MFMA -> VALU hazard itself.
-__device__ __forceinline__ double max_f64(double a, double b) {
-    double r;
-    asm volatile("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
 
 // Diagnostic build only (tools/probe/kmeans_stamp_probe.hip): per-phase cycle stamps of wave 0.
 #ifdef MSM_KM_STAMPS
@@ -639,13 +632,13 @@ __global__ __launch_bounds__(kMT, kMT == 1024 ? 4 : 2) void kmeans_mfma_kernel(
                 if constexpr (KS > 4) asm volatile("s_nop 15\n\ts_nop 3" ::: "memory");  // both tiles just issued
                 double ma[NF], mb[NF];
 #pragma unroll
-                for (int u = 0; u < NF; ++u) ma[u] = max_f64(max_f64(acca[u][0], acca[u][1]), max_f64(acca[u][2], acca[u][3]));
+                for (int u = 0; u < NF; ++u) ma[u] = hw_max_f64_pin(hw_max_f64_pin(acca[u][0], acca[u][1]), hw_max_f64_pin(acca[u][2], acca[u][3]));
                 asm volatile("s_nop 7" ::: "memory");
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int u = 0; u < NF; ++u) {
-                    mb[u] = max_f64(max_f64(accb[u][0], accb[u][1]), max_f64(accb[u][2], accb[u][3]));
-                    const double m = max_f64(ma[u], mb[u]);
+                    mb[u] = hw_max_f64_pin(hw_max_f64_pin(accb[u][0], accb[u][1]), hw_max_f64_pin(accb[u][2], accb[u][3]));
+                    const double m = hw_max_f64_pin(ma[u], mb[u]);
                     const bool better = m > best[u];  // strict: the first pair keeps ties
                     best[u] = better ? m : best[u];
                     const int code = kGlobalRecovery ? (((k0 >> 4) + jt) << 1) | (jb == jt ? 1 : 0) : jt;

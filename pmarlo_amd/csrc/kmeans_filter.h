@@ -149,13 +149,8 @@ __device__ __forceinline__ int filter_piece(int q) { return q == 3 ? 2 : (q & 1)
 // when `a` is already the result of a VALU maximum, which is why the pair maximum below starts from b2.
 __device__ __forceinline__ float max3_f32(float a, float b, float c) { return __builtin_fmaxf(__builtin_fmaxf(a, b), c); }
 __device__ __forceinline__ float med3_f32(float a, float b, float c) { return __builtin_amdgcn_fmed3f(a, b, c); }
-// the bare v_max_f32 (operands are never NaN where this is used): fmaxf() on a loop-carried value costs an extra
-// canonicalising v_max per call, and med3(a, b, +inf) is folded back into it
-__device__ __forceinline__ float hw_max_f32(float a, float b) {
-    float r;
-    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
+// hw_max_f32 (wave.h) where a maximum is loop-carried: fmaxf() costs an extra canonicalising v_max per call, and
+// med3(a, b, +inf) is folded back into it
 
 // ---------------------------------------------------------------------------------------------------------
 // Frame images: row t = the B operands of frame t (3 uint4, layout as filter_slot) in scaled units x' = 2^e_x x; the
@@ -363,76 +358,8 @@ __device__ __forceinline__ void filter_stage_build(int tile, int lane, unsigned 
     if (bad && lane == 0) atomicOr(any_bad, 1);
 }
 
-// cross-row butterflies over the 4 lanes (j, j + 16, j + 32, j + 48) that share a frame: v_permlane16_swap /
-// v_permlane32_swap exchange whole rows of 16 lanes on the VALU (no LDS round trip as ds_bpermute would take)
-typedef unsigned v2u32 __attribute__((ext_vector_type(2)));
-template <typename Op>
-__device__ __forceinline__ unsigned xrow_reduce_u32(unsigned x, Op op) {
-    v2u32 r = __builtin_amdgcn_permlane16_swap(x, x, false, false);
-    x = op(r[0], r[1]);
-    r = __builtin_amdgcn_permlane32_swap(x, x, false, false);
-    return op(r[0], r[1]);
-}
-__device__ __forceinline__ float xrow_max_f32(float x) {   // operands are never NaN here
-    return __uint_as_float(xrow_reduce_u32(__float_as_uint(x), [](unsigned a, unsigned b) {
-        return __float_as_uint(hw_max_f32(__uint_as_float(a), __uint_as_float(b)));
-    }));
-}
-__device__ __forceinline__ int xrow_min_i32(int x) {
-    return (int)xrow_reduce_u32((unsigned)x, [](unsigned a, unsigned b) { return (unsigned)min((int)a, (int)b); });
-}
-// reductions over the whole wave on the VALU: four DPP steps inside the rows of 16 lanes (quad_perm [1,0,3,2],
-// quad_perm [2,3,0,1], row_half_mirror, row_mirror), then the two row swaps -- every lane ends with the result
-// (a butterfly of __shfl_xor is six dependent trips through the LDS crossbar, ~1 us)
-template <typename Op>
-__device__ __forceinline__ unsigned row_reduce_u32(unsigned x, Op op) {
-    x = op(x, (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0xB1, 0xF, 0xF, false));
-    x = op(x, (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0x4E, 0xF, 0xF, false));
-    x = op(x, (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0x141, 0xF, 0xF, false));
-    x = op(x, (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0x140, 0xF, 0xF, false));
-    return x;
-}
-__device__ __forceinline__ float wave_max_f32(float x) {   // operands are never NaN here
-    const unsigned r = row_reduce_u32(__float_as_uint(x), [](unsigned a, unsigned b) {
-        return __float_as_uint(hw_max_f32(__uint_as_float(a), __uint_as_float(b)));
-    });
-    return xrow_max_f32(__uint_as_float(r));
-}
-__device__ __forceinline__ int wave_min_i32(int x) {
-    return xrow_min_i32((int)row_reduce_u32((unsigned)x, [](unsigned a, unsigned b) { return (unsigned)min((int)a, (int)b); }));
-}
-__device__ __forceinline__ double wave_max_f64(double x) {   // NaN operands lose (v_max_f64)
-    auto mx = [](double a, double b) {
-        double r;
-        asm volatile("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-        return r;
-    };
-    auto dpp = [&](double v, auto ctrl) {
-        const long long bits = __double_as_longlong(v);
-        const int lo = __builtin_amdgcn_update_dpp(0, (int)bits, decltype(ctrl)::value, 0xF, 0xF, false);
-        const int hi = __builtin_amdgcn_update_dpp(0, (int)(bits >> 32), decltype(ctrl)::value, 0xF, 0xF, false);
-        return __longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo));
-    };
-    x = mx(x, dpp(x, std::integral_constant<int, 0xB1>{}));
-    x = mx(x, dpp(x, std::integral_constant<int, 0x4E>{}));
-    x = mx(x, dpp(x, std::integral_constant<int, 0x141>{}));
-    x = mx(x, dpp(x, std::integral_constant<int, 0x140>{}));
-#pragma unroll
-    for (int step = 0; step < 2; ++step) {
-        const unsigned lo = (unsigned)__double_as_longlong(x), hi = (unsigned)(__double_as_longlong(x) >> 32);
-        v2u32 rl, rh;
-        if (step == 0) {
-            rl = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-            rh = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-        } else {
-            rl = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-            rh = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-        }
-        x = mx(__longlong_as_double((long long)(((unsigned long long)rh[0] << 32) | rl[0])),
-               __longlong_as_double((long long)(((unsigned long long)rh[1] << 32) | rl[1])));
-    }
-    return x;
-}
+// The filter's cross-lane steps are on the VALU (wave.h): xrow_* over the 4 lanes (j, j + 16, j + 32, j + 48) that share
+// a frame, wave_* over the whole wave.  A butterfly of __shfl_xor would be six trips through the LDS crossbar, ~1 us.
 
 // max |v| over the coordinates that pass the unscaled range guard (whitened when mean / stdv are given) into *out_bits
 // (non-negative doubles order like their bits): the bound of the frames' scale when the caller has none to give
@@ -528,6 +455,7 @@ __device__ __forceinline__ void filter_close_iteration(const unsigned long long*
                         centers[i0 + c * 1024] = c_new;
                     }
             }
+            // wave_sum_down (wave.h) written out: the call moves the red[] address ahead of the last shuffle and adds an s_waitcnt
             for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
             if ((v & 63) == 0) red[v >> 6] = acc;
         }
@@ -700,6 +628,7 @@ __global__ __launch_bounds__(64 * filter_waves(DP, ACCUM)) void kmeans_filter_ke
             const double sc = score64(centers + (size_t)c * d, c, zz);
             if (sc > sbest) { sbest = sc; sbi = c; }   // ascending c per lane: the first maximum stays
         }
+        // wave_argmax_xor (wave.h) written out: as a call, every specialisation of the kernel gets a different branch layout
 #pragma unroll
         for (int off = 1; off < 64; off <<= 1) {
             const double ob = __shfl_xor(sbest, off, 64);
@@ -901,6 +830,7 @@ __global__ __launch_bounds__(64 * filter_waves(DP, ACCUM)) void kmeans_filter_ke
         while (todo) {
             const int jf = __builtin_ctzll(todo);
             todo &= todo - 1;
+            // the 64-bit readlane pairs (readlane_f64 of wave.h) written out, here and below: calls change the SGPR spills of this loop
             const int64_t t = ((int64_t)__builtin_amdgcn_readlane((int)(f0 >> 32), jf) << 32) |
                               (unsigned)__builtin_amdgcn_readlane((int)f0, jf);
             const bool plain = all_scan || __builtin_amdgcn_readlane((int)(z_bad || !(Ru < __builtin_inff())), jf) != 0;

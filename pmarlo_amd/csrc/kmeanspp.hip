@@ -19,6 +19,7 @@
 // the frame).  C3 (1 M x 10, k = 500): ~1000 launches, 48 GB of traffic, ~15 ms -- a start-up cost of the operator
 // API's fit, not of the bench step (which keeps its seeded stratified draw, as round 1 defined the workload).
 #include "common.h"
+#include "wave.h"
 
 namespace {
 
@@ -83,7 +84,7 @@ __global__ __launch_bounds__(kBlock) void kpp_update_kernel(const T* __restrict_
         mind[t] = m;
         w = __double2ll_rn(m * scale);
     }
-    for (int off = 32; off > 0; off >>= 1) w += __shfl_down(w, off, 64);
+    w = wave_sum_down(w);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = w;
     __syncthreads();
     if (threadIdx.x == 0) {

@@ -7,6 +7,7 @@
 // run of the row-major matrix.  Reductions are two-stage (per-workgroup slab in
 // scratch, then one fixed-order pass), so results are run-to-run reproducible.
 #include "common.h"
+#include "wave.h"
 
 namespace {
 
@@ -158,7 +159,7 @@ constexpr int kProjFT = 64;  // feature chunk
 // the maximum.  Feeds the fixed-point scale of the k-means fit without a second pass over Y.
 __device__ __forceinline__ void publish_absmax(double m, unsigned long long* __restrict__ bits, double* red) {
     if (!bits) return;
-    for (int off = 32; off > 0; off >>= 1) m = fmax(m, __shfl_down(m, off, 64));
+    m = wave_max_down(m);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
     __syncthreads();
@@ -458,10 +459,7 @@ __global__ __launch_bounds__(256) void column_minmax_kernel(const T* __restrict_
         }
         good_rows += all_ok ? 1 : 0;
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        bad_entries += __shfl_down(bad_entries, off, 64);
-        good_rows += __shfl_down(good_rows, off, 64);
-    }
+    wave_sum_down_each(bad_entries, good_rows);
     if ((threadIdx.x & 63) == 0) {
         if (bad_entries) atomicAdd(&counters[0], bad_entries);
         if (good_rows) atomicAdd(&counters[1], good_rows);

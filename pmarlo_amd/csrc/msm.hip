@@ -11,6 +11,7 @@
 // non-symmetric eigenproblem is solved by elmhes/hqr (small_eig.h).  The Ritz
 // vector of the eigenvalue nearest 1 gives the stationary distribution.
 #include "common.h"
+#include "wave.h"
 #include "small_eig.h"
 
 #include <algorithm>
@@ -39,7 +40,7 @@ __global__ __launch_bounds__(kThreads) void rowcol_sums_kernel(const CT* __restr
         r += cnt_as_f64(C[(size_t)i * k + j]);
         c += cnt_as_f64(C[(size_t)j * k + i]);
     }
-    for (int off = 32; off > 0; off >>= 1) { r += __shfl_down(r, off, 64); c += __shfl_down(c, off, 64); }
+    wave_sum_down_each(r, c);
     __shared__ double red2[kThreads / 64];
     if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = r; red2[threadIdx.x >> 6] = c; }
     __syncthreads();
@@ -109,7 +110,7 @@ __global__ __launch_bounds__(1024) void diag_mass_kernel(const double* __restric
     __shared__ double red[16];
     double t = 0.0;
     for (int i = threadIdx.x; i < k; i += 1024) t += T[(size_t)i * k + i];
-    for (int off = 32; off > 0; off >>= 1) t += __shfl_down(t, off, 64);
+    t = wave_sum_down(t);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = t;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -134,7 +135,7 @@ __global__ __launch_bounds__(kThreads) void row_normalise_kernel(const CT* __res
     const int i = blockIdx.x;
     double r = 0.0;
     for (int j = threadIdx.x; j < k; j += kThreads) r += cnt_as_f64(C[(size_t)i * k + j]);
-    for (int off = 32; off > 0; off >>= 1) r += __shfl_down(r, off, 64);
+    r = wave_sum_down(r);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = r;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -162,7 +163,7 @@ __global__ __launch_bounds__(kThreads) void row_normalise_kernel(const CT* __res
         const int v = v0 + threadIdx.x;
         double t = 0.0;
         for (int q = v; q < k; q += 1024) t += __hip_atomic_load(&tdiag[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        for (int off = 32; off > 0; off >>= 1) t += __shfl_down(t, off, 64);
+        t = wave_sum_down(t);
         if ((v & 63) == 0) red[v >> 6] = t;
     }
     __syncthreads();
@@ -245,34 +246,6 @@ struct SpecShared {
     int order[kMaxP];
     int status;
 };
-
-__device__ double spec_block_sum(double v, SpecShared* sh) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh->red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += sh->red[i];
-        sh->bc = t;
-    }
-    __syncthreads();
-    return sh->bc;
-}
-
-__device__ double spec_block_max(double v, SpecShared* sh) {
-    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off, 64));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh->red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = -INFINITY;
-        for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t = fmax(t, sh->red[i]);
-        sh->bc = t;
-    }
-    __syncthreads();
-    return sh->bc;
-}
 
 // Gram matrix M = A'B (p x p, operands n x p with row stride p) on the fp64 matrix cores.  The scalar version (a thread
 // per entry walking all rows) read every operand element p times from the LDS: 8 us at n = 200, p = 32, LDS-bandwidth
@@ -432,12 +405,6 @@ constexpr int kStepFinish = 8;   // Rayleigh-Ritz, residuals, pi, implied timesc
 // arrays in scratch memory), the pivot-row elements come by v_readlane, and the dependent chain holds only the
 // multiply-adds, the square root and the division: 13 instead of 21 us at p = 32, 3.7 instead of 5.5 us at p = 12
 // (tools/run/spec_stamps.sh).  Same operations in the same order as the LDS walk it replaces: the same bits.
-__device__ __forceinline__ double readlane_f64(double v, int lane) {
-    const long long b = __double_as_longlong(v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)b, lane);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(b >> 32), lane);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
 template <int C>
 __device__ __forceinline__ void chol_step(double (&r)[kMaxP], const double* G, double* R, int p, int j) {
     if constexpr (C < kMaxP) {
@@ -959,8 +926,8 @@ __global__ __launch_bounds__(kSolveThreads) void spec_step_kernel(SpecArgs ar, i
                         rn = fma(rr, rr, fma(ri, ri, rn));
                         xn = fma(xr, xr, fma(xi, xi, xn));
                     }
-                    rn = spec_block_sum(rn, &sh);
-                    xn = spec_block_sum(xn, &sh);
+                    rn = block_sum_bcast(rn, sh.red, &sh.bc);
+                    xn = block_sum_bcast(xn, sh.red, &sh.bc);
                     // (the plane comes from the SQUARED shifted matrix: with another eigenvalue very close to the pair
                     // its residual floors near eps / gap^2; the change between launches then still decides)
                     double res = sqrt(rn / fmax(xn, 1e-300));
@@ -994,8 +961,8 @@ __global__ __launch_bounds__(kSolveThreads) void spec_step_kernel(SpecArgs ar, i
                 rn = fma(r, r, rn);
                 xn = fma(xv, xv, xn);
             }
-            rn = spec_block_sum(rn, &sh);
-            xn = spec_block_sum(xn, &sh);
+            rn = block_sum_bcast(rn, sh.red, &sh.bc);
+            xn = block_sum_bcast(xn, sh.red, &sh.bc);
             worst = fmax(worst, sqrt(rn / fmax(xn, 1e-300)));
         }
         if (tid == 0) ar.change[b] = worst;
@@ -1017,7 +984,7 @@ __global__ __launch_bounds__(kSolveThreads) void spec_step_kernel(SpecArgs ar, i
             pi[i] = v;
             part += v;
         }
-        const double tot = spec_block_sum(part, &sh);
+        const double tot = block_sum_bcast(part, sh.red, &sh.bc);
         for (int i = tid; i < n; i += blockDim.x) pi[i] = pi[i] / tot;
     }
     __syncthreads();
@@ -1055,12 +1022,12 @@ __global__ __launch_bounds__(kSolveThreads) void spec_step_kernel(SpecArgs ar, i
                 nn = fma(v, v, nn);
                 big = fmax(big, fabs(v));
             }
-            nn = spec_block_sum(nn, &sh);
-            big = spec_block_max(big, &sh);
+            nn = block_sum_bcast(nn, sh.red, &sh.bc);
+            big = block_max_bcast(big, sh.red, &sh.bc);
             double first = -(double)n;                       // -(lowest index that attains the maximum)
             for (int i = tid; i < n; i += blockDim.x)
                 if (fabs(out[i]) == big) { first = -(double)i; break; }
-            first = spec_block_max(first, &sh);
+            first = block_max_bcast(first, sh.red, &sh.bc);
             const int lead = min(n - 1, max(0, (int)(-first)));
             const double scale = (out[lead] < 0.0 ? -1.0 : 1.0) / sqrt(fmax(nn, 1e-300));
             __syncthreads();                                 // every thread has read out[lead]

@@ -15,17 +15,12 @@
 // normalisation of the previous iterate in a fixed order (bit-identical across workgroups) and
 // produces the unnormalised new row sums of its rows, one wave per row.
 #include "common.h"
+#include "wave.h"
 
 namespace {
 
 constexpr int kRT = 256;
 constexpr int kRowsPerBlock = kRT / 64;
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 // fixed-order sum of x[0..n) by one workgroup (identical in every workgroup)
 __device__ double block_total(const double* __restrict__ x, int n, double* sh) {
@@ -58,8 +53,8 @@ __global__ __launch_bounds__(kRT) void symmetrise_kernel(const double* __restric
         a += cij;
         b += s;
     }
-    a = wave_sum(a);
-    b = wave_sum(b);
+    a = wave_sum_xor(a);
+    b = wave_sum_xor(b);
     if (lane == 0) { c[i] = a; x0[i] = b; }
 }
 
@@ -85,7 +80,7 @@ __global__ __launch_bounds__(kRT) void iterate_kernel(const double* __restrict__
         const double den = vi + v[j];
         if (c2 > 0.0 && den > 0.0) acc += c2 / den;
     }
-    acc = wave_sum(acc);
+    acc = wave_sum_xor(acc);
     if (lane == 0) x_new[i] = acc;
 }
 
@@ -133,7 +128,7 @@ __global__ __launch_bounds__(kRT) void finish_kernel(const double* __restrict__ 
         T[(size_t)i * ldt + j] = f;
         acc += f;
     }
-    acc = wave_sum(acc);
+    acc = wave_sum_xor(acc);
     for (int j = lane; j < n; j += 64) {
         // a state without any flux keeps a self-loop (cannot happen on a connected count matrix)
         T[(size_t)i * ldt + j] = acc > 0.0 ? T[(size_t)i * ldt + j] / acc : (j == i ? 1.0 : 0.0);

@@ -9,6 +9,7 @@
 // query point and walks the clusters in order, so the per-cluster distance sums sit in registers with
 // static indices; the reference points stream through LDS tiles shared by the workgroup.
 #include "common.h"
+#include "wave.h"
 
 namespace {
 
@@ -76,7 +77,7 @@ __global__ __launch_bounds__(1024) void mean_kernel(const double* __restrict__ v
     __shared__ double red[16];
     double acc = 0.0;
     for (int64_t i = threadIdx.x; i < n; i += blockDim.x) acc += v[i];
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    acc = wave_sum_down(acc);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) {

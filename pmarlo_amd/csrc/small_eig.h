@@ -7,6 +7,7 @@
 #include <math.h>
 
 #ifdef __HIPCC__
+#include "wave.h"
 #define SE_HD __host__ __device__
 #else
 #define SE_HD
@@ -170,7 +171,7 @@ __device__ inline int eigenvalues_wave(volatile double* a, int n, int ld, double
         // pivot: the first row j >= m with the largest |A(j, m-1)| (lane = candidate row)
         double x = (lane >= m && lane < n) ? A_(lane, m - 1) : 0.0;
         double big = fabs(x);
-        for (int off = 32; off > 0; off >>= 1) big = fmax(big, __shfl_xor(big, off, 64));
+        big = wave_max_xor(big);
         int i = m;
         if (big > 0.0) {
             const unsigned long long hits = __ballot(lane >= m && lane < n && fabs(x) == big);
@@ -207,7 +208,7 @@ __device__ inline int eigenvalues_wave(volatile double* a, int n, int ld, double
     double anorm = 0.0;   // only a fall-back scale for the deflation test: summation order is free
     if (lane < n)
         for (int i = 0; i <= (lane + 1 < n ? lane + 1 : n - 1); ++i) anorm += fabs(A_(i, lane));
-    for (int off = 32; off > 0; off >>= 1) anorm += __shfl_xor(anorm, off, 64);
+    anorm = wave_sum_xor(anorm);
     int nn = n - 1;
     double t = 0.0, p = 0.0, q = 0.0, r = 0.0;
     while (nn >= 0) {
@@ -432,13 +433,13 @@ __device__ inline void eigenvector_wave(const double* h, int n, int ld, double t
         }
         scale = fmax(scale, fabs(v));
     }
-    for (int off = 32; off > 0; off >>= 1) scale = fmax(scale, __shfl_xor(scale, off, 64));
+    scale = wave_max_xor(scale);
     const double tiny = 2.3e-16 * (scale > 0.0 ? scale : 1.0);
     SE_SYNC();
     for (int c = 0; c < n; ++c) {
         const double mine = (lane >= c && lane < n) ? fabs(m[lane * n + c]) : -1.0;
         double big = mine;
-        for (int off = 32; off > 0; off >>= 1) big = fmax(big, __shfl_xor(big, off, 64));
+        big = wave_max_xor(big);
         const int pr = __builtin_ctzll(__ballot(mine == big));     // first row attaining the maximum
         if (lane == 0) piv[c] = (double)pr;
         if (pr != c && lane < n) { const double t = m[c * n + lane]; m[c * n + lane] = m[pr * n + lane]; m[pr * n + lane] = t; }
@@ -471,7 +472,7 @@ __device__ inline void eigenvector_wave(const double* h, int n, int ld, double t
             SE_SYNC();
         }
         double nrm = lane < n ? fabs(y[lane]) : 0.0;
-        for (int off = 32; off > 0; off >>= 1) nrm = fmax(nrm, __shfl_xor(nrm, off, 64));
+        nrm = wave_max_xor(nrm);
         if (nrm > 0.0 && lane < n) y[lane] /= nrm;
         SE_SYNC();
     }

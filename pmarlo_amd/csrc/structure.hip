@@ -5,6 +5,7 @@
 // geometry/src/sasa.cpp, geometry/hbond.py, geometry/src/dssp.cpp) in their operation order; the oracle
 // (oracle/npport.py) restates them once more in numpy.
 #include "common.h"
+#include "wave.h"
 
 namespace {
 
@@ -77,7 +78,7 @@ __global__ __launch_bounds__(kSThreads) void sasa_kernel(const float* __restrict
             }
             acc += open ? 1 : 0;
         }
-        for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+        acc = wave_sum_xor(acc);
         if (lane == 0) out[it] = constant * Ri * Ri * (float)acc;
     }
 }

@@ -11,6 +11,7 @@
 // per column a pivot search, a row swap, a scaling and a rank-1 update of the trailing block and
 // of the right-hand sides, each fully parallel); fixed arithmetic order -> reproducible.
 #include "common.h"
+#include "wave.h"
 
 namespace {
 
@@ -38,11 +39,7 @@ __global__ __launch_bounds__(kLT) void solve_kernel(double* __restrict__ A, int6
             const double v = fabs(A[(size_t)i * lda + k]);
             if (v > best) { best = v; bi = i; }
         }
-        for (int off = 32; off > 0; off >>= 1) {
-            const double ov = __shfl_down(best, off, 64);
-            const int oi = __shfl_down(bi, off, 64);
-            if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-        }
+        wave_argmax_down(best, bi);
         if ((tid & 63) == 0) { sh.val[tid >> 6] = best; sh.idx[tid >> 6] = bi; }
         __syncthreads();
         if (tid == 0) {
@@ -143,7 +140,7 @@ __global__ __launch_bounds__(1024) void flux_totals_kernel(const double* __restr
     for (int i = threadIdx.x; i < n; i += blockDim.x) z = fma(pi[i], qm[i], z);
     for (int which = 0; which < 2; ++which) {
         double v = which == 0 ? f : z;
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+        v = wave_sum_down(v);
         __syncthreads();
         if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
         __syncthreads();
@@ -177,7 +174,7 @@ __global__ __launch_bounds__(256) void lump_rows_kernel(const double* __restrict
         double acc = 0.0;
         for (int j = wave * 64 + lane; j < n; j += waves * 64)
             if (macro[j] == B) acc += T[(size_t)i * ldt + j];
-        for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+        acc = wave_sum_down(acc);
         if (lane == 0) part[wave * n_macro + B] = acc;
     }
     __syncthreads();
