@@ -601,6 +601,34 @@ msm_status msm_sample_transition_matrices(msm_ctx* ctx, const void* d_counts, in
                                           uint64_t seed, int first_sample, int n_samples, double* d_T,
                                           int64_t t_stride, int ld);
 
+/* Posterior samples of the REVERSIBLE estimate for the same confidence intervals: the law of deeptime's
+ * BayesianMSM(lagtime, n_samples) with its default reversible=True, which ITSMixin._its_compute_for_single_lag
+ * fits (S/markov_state_model/_its.py:289-312) and _summarize_its_stats (:543-668) summarises.  deeptime is absent
+ * (parity unpinned); the law is the published one, Trendelkamp-Schroer, Wu, Paul and Noe, J. Chem. Phys. 143,
+ * 174101 (2015): symmetric X >= 0 with T_ij = x_ij / x_i, pi_i = x_i / sum x and
+ *   p(X | C) ~ prod_i x_ii^(C_ii - 1) prod_{i<j} x_ij^(C_ij + C_ji - 1) prod_i x_i^(-c_i),   c_i = sum_j C_ij;
+ * cells with C_ij + C_ji == 0 are exactly 0 in every sample.  One independent Gibbs / Metropolis chain per sample
+ * (csrc/revposterior.hip describes the updates, the scan and the 1e-280 floor), started from X0 = diag(pi0) T0
+ * and run for n_sweeps sweeps.
+ * d_counts f64 [n, ld]: non-negative counts with the caller's prior already added (e.g. ensure_connected_counts'
+ * result); d_T0 f64 [n, ld] and d_pi0 f64 [n]: the reversible maximum-likelihood estimate of the same counts
+ * (msm_reversible_mle).  Sample s (numbered first_sample + s) is written at d_T + s*t_stride with row stride ldt,
+ * the layout msm_spectrum's batch takes, and satisfies pi_i T_ij = pi_j T_ji with its own pi, written to
+ * d_pi f64 [n_samples, n] (may be NULL).  Variates are Philox4x32-10 keyed by `seed` with counter (cell, sample
+ * number, sweep, attempt): a sample does not depend on the batch it is drawn in.  Plain launches on the context's
+ * stream, capturable.  n * 8 bytes must fit the 96 KB LDS table (MSM_ERR_UNSUPPORTED above);
+ * n_samples <= 65535 per call. */
+msm_status msm_sample_reversible_transition_matrices(msm_ctx* ctx, const double* d_counts, int n, int ld,
+                                                     const double* d_T0, const double* d_pi0, uint64_t seed,
+                                                     int first_sample, int n_samples, int n_sweeps, double* d_T,
+                                                     int64_t t_stride, int ldt, double* d_pi);
+
+/* The regularised active-set counts of ensure_connected_counts (S/utils/msm_utils.py:129-167) from the outputs of
+ * msm_transition_matrix mode 1: d_out f64 [n_active, n_active] contiguous,
+ * d_out[a, b] = counts[active[a], active[b]] + alpha.  Feeds msm_reversible_mle and the sampler above. */
+msm_status msm_active_counts(msm_ctx* ctx, const void* d_counts, int counts_are_f64, int k, const int32_t* d_active,
+                             const int32_t* d_n_active, double alpha, double* d_out);
+
 /* One Philox4x32-10 block (known-answer test of the generator): d_out uint32 [4]. */
 msm_status msm_philox4x32(msm_ctx* ctx, uint64_t key, const uint32_t counter[4], uint32_t* d_out);
 

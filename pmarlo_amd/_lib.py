@@ -121,6 +121,9 @@ _PROTOTYPES: dict[str, tuple] = {
                                     _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _f64, _vp, _i32]),
     "msm_sample_transition_matrices": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _f64, C.c_uint64, _i32, _i32, _vp, _i64,
                                               _i32]),
+    "msm_sample_reversible_transition_matrices": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, C.c_uint64, _i32, _i32, _i32,
+                                                         _vp, _i64, _i32, _vp]),
+    "msm_active_counts": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _f64, _vp]),
     "msm_reversible_mle": (_i32, [_vp, _vp, _i32, _i32, _f64, _i32, _vp, _i32, _vp, _vp, _vp]),
     "msm_philox4x32": (_i32, [_vp, C.c_uint64, _vp, _vp]),
     "msm_gemm_f64": (_i32, [_vp, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _i64]),

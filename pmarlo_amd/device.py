@@ -1160,6 +1160,44 @@ class Engine:
                                      pi.ptr, ctypes.byref(it), ctypes.byref(err)), self.handle)
         return {"T": T, "pi": pi, "iterations": it.value, "err": err.value}
 
+    def active_counts(self, counts: DeviceArray, active: DeviceArray, n_active: DeviceArray, n: int, *,
+                      alpha: float) -> DeviceArray:
+        """counts[active, active] + alpha as a contiguous f64 [n, n] (n = the host copy of n_active): the regularised
+        active-set counts of ensure_connected_counts, built on the device from msm_transition_matrix mode 1's outputs."""
+        out = self.empty((int(n), int(n)), np.float64)
+        check(lib.msm_active_counts(self.handle, counts.ptr, int(counts.dtype == np.float64), counts.shape[-1],
+                                    active.ptr, n_active.ptr, float(alpha), out.ptr), self.handle)
+        return out
+
+    def sample_reversible_transition_matrices(self, counts: DeviceArray, *, seed: int, n_samples: int,
+                                              n_sweeps: int | None = None, first_sample: int = 0,
+                                              out: DeviceArray | None = None, want_pi: bool = False):
+        """n_samples draws [n_samples, n, n] of the reversible posterior of a connected f64 count matrix [n, n]
+        (prior already added), one independent chain per sample started from reversible_mle(counts), which this runs
+        itself.  n_sweeps=None takes 2 * ceil(sqrt(n)) + 10 sweeps per chain: this engine's own choice (the chains start
+        at the posterior mode and every off-diagonal update is a mode-fitted independence proposal, so the burn-in is
+        short; tests/test_gpu_revposterior.py checks it against four times as many).  want_pi: returns (T, pi) with
+        the stationary vectors [n_samples, n] of the samples.  out [n_samples, m, m] with m >= n receives the samples
+        packed in the top-left n x n corners (the layout spectrum() takes with `n`)."""
+        n = counts.shape[0]
+        if n_sweeps is None:
+            n_sweeps = 2 * int(np.ceil(np.sqrt(n))) + 10
+        if out is None:
+            out = self.empty((int(n_samples), n, n), np.float64)
+        ldt = out.shape[-1]                           # a wider `out` takes the samples packed in its top-left corner
+        stride = out.shape[-2] * ldt
+        pi = self.empty((int(n_samples), n), np.float64) if want_pi else None
+        mle = self.reversible_mle(counts)
+        done = 0
+        while done < n_samples:                       # per-launch limit, as sample_transition_matrices
+            m = min(65535, n_samples - done)
+            check(lib.msm_sample_reversible_transition_matrices(
+                self.handle, counts.ptr, n, counts.shape[1], mle["T"].ptr, mle["pi"].ptr, int(seed) & (2 ** 64 - 1),
+                int(first_sample + done), m, int(n_sweeps), out.ptr + done * stride * 8, stride, ldt,
+                pi.ptr + done * n * 8 if pi is not None else None), self.handle)
+            done += m
+        return (out, pi) if want_pi else out
+
     def diff_norms(self, P: DeviceArray, Q: DeviceArray) -> np.ndarray:
         """[sum |P - Q|, sum |Q|, sum (P - Q)^2] of two f64 matrices of one shape."""
         n, m = P.shape

@@ -9,7 +9,10 @@ deeptime (SURVEY.md hard part 4).  This engine keeps the definition and replaces
   T(tau) = rownorm(C(tau) + alpha) on the active set (deterministic; zero-width intervals);
 * n_samples > 1: the same statistics over n_samples draws of the closed-form posterior of that
   estimator (independent Dirichlet rows, msm_sample_transition_matrices), all lags and samples
-  in one batched spectrum solve; median and percentile band as _summarize_its_stats :606-625."""
+  in one batched spectrum solve; median and percentile band as _summarize_its_stats :606-625;
+* reversible=True: the reference's default semantics.  The point estimate is the reversible
+  maximum-likelihood matrix and the samples come from the reversible posterior
+  (msm_sample_reversible_transition_matrices: every sample obeys detailed balance)."""
 
 from __future__ import annotations
 
@@ -216,7 +219,8 @@ def compute_implied_timescales(dtrajs: Sequence[np.ndarray], n_states: int, lag_
                                dirichlet_alpha: float = 1e-3, plateau_m: int | None = None,
                                plateau_epsilon: float = 0.1, time_per_frame_ps: float | None = None,
                                random_state: int | None = None, return_samples: bool = False,
-                               effective_frames: int | None = None) -> ITSResult:
+                               effective_frames: int | None = None, reversible: bool = False,
+                               n_sweeps: int | None = None) -> ITSResult:
     """Lag scan on the device (ITSMixin.compute_implied_timescales, S/markov_state_model/_its.py:137-192):
     batched counts for all lags, one packed transition matrix per lag, n_samples posterior matrices
     per lag, one batched spectrum solve over lags x samples, median / percentile band on the host.
@@ -224,9 +228,16 @@ def compute_implied_timescales(dtrajs: Sequence[np.ndarray], n_states: int, lag_
     Input rules of _validate_its_inputs (:453-524): no trajectories, or a shortest trajectory with fewer than two
     frames (an EMPTY trajectory counts: it makes max_valid_lag = -1), give the empty result; lags above
     min(len) - 1 are dropped; a largest lag >= `effective_frames` (the mixin's attribute of that name) raises.
-    The confidence bands come from independent Dirichlet rows on C_active + alpha (the closed-form posterior of the
-    non-reversible estimator this engine fits), not from deeptime's reversible BayesianMSM sampler: medians and
-    bands differ from the reference's systematically where detailed balance matters."""
+    reversible=False (default): the confidence bands come from independent Dirichlet rows on C_active + alpha, the
+    closed-form posterior of the non-reversible estimator; a sample need not obey detailed balance.
+    reversible=True: the semantics of the reference's BayesianMSM (reversible by default).  Per lag the regularised
+    active-set counts ensure_connected_counts(C, alpha=dirichlet_alpha).counts are built on the device, n_samples
+    matrices are drawn from the reversible posterior of Trendelkamp-Schroer et al. (2015), one independent chain of
+    n_sweeps sweeps per sample (None: the engine's default 2 * ceil(sqrt(n)) + 10) started from the reversible
+    maximum-likelihood estimate, and summarised as above; n_samples <= 1 is the deterministic spectrum of that
+    estimate.  deeptime is not available, so parity with its sampler stays unpinned: what is tested is the law the
+    samples are drawn from (closed-form Beta marginals, a numpy chain, detailed balance of every sample; DESIGN.md
+    section 7)."""
     n = int(n_timescales)
     empty = ITSResult(lag_times=np.array([], dtype=int), eigenvalues=np.empty((0, n)),
                       eigenvalues_ci=np.empty((0, n, 2)), timescales=np.empty((0, n)),
@@ -264,6 +275,22 @@ def compute_implied_timescales(dtrajs: Sequence[np.ndarray], n_states: int, lag_
         check(lib.msm_transition_matrix(eng.handle, counts.ptr + i * k * k * 8, 0, k, 1, float(dirichlet_alpha), 1e-12,
                                         Tb.ptr + i * k * k * 8, act.ptr + i * k * 4, inv.ptr, nb.ptr + 4 * i, rows.ptr,
                                         None), eng.handle)
+    rev_counts = None
+    if reversible:
+        # the regularised active-set counts of every lag, as fit_reversible_msm builds them
+        nb_h = nb.to_host()
+        rev_counts = [eng.active_counts(counts.view((k, k), offset_elems=i * k * k), act.view((k,), offset_elems=i * k),
+                                        nb.view((1,), offset_elems=i), int(nb_h[i]), alpha=float(dirichlet_alpha))
+                      if nb_h[i] > 0 else None for i in range(L)]
+    if not S and reversible:
+        import ctypes
+
+        for i in range(L):                     # the reversible estimate over the packed non-reversible one
+            if rev_counts[i] is not None:
+                ni = int(nb_h[i])
+                check(lib.msm_reversible_mle(eng.handle, rev_counts[i].ptr, ni, ni, 1e-8, 1_000_000, Tb.ptr + i * k * k * 8,
+                                             k, None, ctypes.byref(ctypes.c_int(0)), ctypes.byref(ctypes.c_double(0.0))),
+                      eng.handle)
     if not S:
         spec = eng.spectrum(Tb, n=nb, n_its=n, lags=[float(v) for v in lags], want_pi=False)
         ev, ts = spec["its_eig"], spec["its_ts"]
@@ -282,6 +309,12 @@ def compute_implied_timescales(dtrajs: Sequence[np.ndarray], n_states: int, lag_
             batch = eng.empty(((b - a) * S, k, k), np.float64)
             for i in range(a, b):
                 # every lag has its own stream: sample numbers i*S .. i*S + S - 1
+                if reversible:
+                    if rev_counts[i] is not None:
+                        eng.sample_reversible_transition_matrices(
+                            rev_counts[i], seed=seed, n_samples=S, n_sweeps=n_sweeps, first_sample=i * S,
+                            out=batch.view((S, k, k), offset_elems=(i - a) * S * k * k))
+                    continue
                 eng.sample_transition_matrices(
                     counts.view((k, k), offset_elems=i * k * k), act.view((k,), offset_elems=i * k),
                     nb.view((1,), offset_elems=i), alpha=float(dirichlet_alpha), seed=seed, n_samples=S,
