@@ -468,10 +468,11 @@ class Engine:
 
     def lagged_moments(self, x: DeviceArray, lag: int, shift: DeviceArray, *, starts=None, stops=None,
                        assume_finite: bool = False, out: DeviceArray | None = None,
-                       one_sided: bool = False, symmetric: bool = False) -> DeviceArray:
+                       one_sided: bool = False, symmetric: bool = False, ld: int | None = None) -> DeviceArray:
         """Raw lagged moments [M00 | M0t | sx | sy | T] (2F^2+2F+1 f64): the reversible estimator's
         (M00 over X0 and Yt) or, with one_sided, M00 over X0 only.  symmetric: the M0t block holds
-        (M0t + M0t') / 2 -- all a reversible TICA reads of it -- from the cheaper symmetric accumulation."""
+        (M0t + M0t') / 2 -- all a reversible TICA reads of it -- from the cheaper symmetric accumulation.
+        ``ld``: row stride in elements when x is a wider buffer's left block."""
         if one_sided and symmetric:
             raise ValueError("one_sided and symmetric moments exclude each other")
         n, F = x.shape
@@ -481,8 +482,8 @@ class Engine:
         out = out if out is not None else self.empty((2 * F * F + 2 * F + 1,), np.float64)
         fn = (lib.msm_lagged_moments_onesided if one_sided
               else lib.msm_lagged_moments_reversible if symmetric else lib.msm_lagged_moments)
-        check(fn(self.handle, x.ptr, _dtype_code(x.dtype), n, F, F, starts.ctypes.data, stops.ctypes.data, len(starts),
-                 int(lag), shift.ptr, int(bool(assume_finite)), out.ptr), self.handle)
+        check(fn(self.handle, x.ptr, _dtype_code(x.dtype), n, F, int(F if ld is None else ld), starts.ctypes.data,
+                 stops.ctypes.data, len(starts), int(lag), shift.ptr, int(bool(assume_finite)), out.ptr), self.handle)
         return out
 
     def autocorr_lagscan(self, x: DeviceArray, lags: Sequence[int], *, starts=None, stops=None,
@@ -522,16 +523,17 @@ class Engine:
         return out
 
     def moments_from_lagged(self, x: DeviceArray, lag: int, shift: DeviceArray, moments: DeviceArray, *, starts=None,
-                            stops=None, out: DeviceArray | None = None) -> DeviceArray:
-        """[cnt | S1 | S2] over all frames from lagged moments of the same shift (finite data only)."""
+                            stops=None, out: DeviceArray | None = None, ld: int | None = None) -> DeviceArray:
+        """[cnt | S1 | S2] over all frames from lagged moments of the same shift (finite data only).
+        ``ld``: row stride in elements when x is a wider buffer's left block."""
         n, F = x.shape
         if starts is None:
             starts, stops = segments_to_bounds(None, n)
         starts, stops = self._seg_ptrs(starts, stops)
         out = out if out is not None else self.empty((3 * F,), np.float64)
-        check(lib.msm_moments_from_lagged(self.handle, x.ptr, _dtype_code(x.dtype), n, F, F, starts.ctypes.data,
-                                          stops.ctypes.data, len(starts), int(lag), shift.ptr, moments.ptr, out.ptr),
-              self.handle)
+        check(lib.msm_moments_from_lagged(self.handle, x.ptr, _dtype_code(x.dtype), n, F, int(F if ld is None else ld),
+                                          starts.ctypes.data, stops.ctypes.data, len(starts), int(lag), shift.ptr,
+                                          moments.ptr, out.ptr), self.handle)
         return out
 
     def tica_solve(self, moments: DeviceArray, F: int, *, scale: DeviceArray | None = None,
