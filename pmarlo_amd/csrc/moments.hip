@@ -523,6 +523,8 @@ msm_status msm_column_minmax(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int
                              double* d_max, int64_t* d_counts) {
     if (!ctx) return MSM_ERR_INVALID;
     MSM_REQUIRE(ctx, n >= 0 && F >= 1 && ld >= F, "msm_column_minmax: bad shape");
+    // the per-workgroup minima and maxima take 16 F bytes of LDS, and 64 KiB is all a launch gets without opting in
+    MSM_REQUIRE(ctx, F <= 4096, "msm_column_minmax: at most 4096 columns per call (F = %d)", F);
     MSM_REQUIRE(ctx, dtype == MSM_F32 || dtype == MSM_F64, "msm_column_minmax: bad dtype");
     MSM_REQUIRE(ctx, d_min && d_max && d_counts && (d_x || n == 0), "msm_column_minmax: NULL pointer");
     msm_status rs = msm_reserve_scratch(ctx, (size_t)2 * F * sizeof(unsigned long long));

@@ -426,28 +426,32 @@ class Engine:
         return stats.to_host(), rs.to_host()[:r], rl.to_host()[:r]
 
     # -- moments / covariance / TICA -------------------------------------------
-    def column_moments(self, x: DeviceArray, ddof: int = 0):
-        """-> (mean, std, count) device arrays [F] f64 (NaN entries skipped)."""
+    def column_moments(self, x: DeviceArray, ddof: int = 0, ld: int | None = None):
+        """-> (mean, std, count) device arrays [F] f64 (NaN entries skipped).
+        ``ld``: row stride in elements when x is a wider buffer's left block."""
         n, F = x.shape
         mean, std, cnt = (self.empty((F,), np.float64) for _ in range(3))
-        check(lib.msm_column_moments(self.handle, x.ptr, _dtype_code(x.dtype), n, F, F, int(ddof), mean.ptr,
-                                     std.ptr, cnt.ptr), self.handle)
+        check(lib.msm_column_moments(self.handle, x.ptr, _dtype_code(x.dtype), n, F, int(F if ld is None else ld),
+                                     int(ddof), mean.ptr, std.ptr, cnt.ptr), self.handle)
         return mean, std, cnt
 
-    def column_minmax(self, x: DeviceArray):
-        """(min [F], max [F] over the finite entries, int64 [2] = non-finite entries, fully finite rows)."""
+    def column_minmax(self, x: DeviceArray, ld: int | None = None):
+        """(min [F], max [F] over the finite entries, int64 [2] = non-finite entries, fully finite rows).
+        ``ld``: row stride in elements when x is a wider buffer's left block."""
         n, F = x.shape
         mn, mx, cnt = self.empty((F,), np.float64), self.empty((F,), np.float64), self.empty((2,), np.int64)
-        check(lib.msm_column_minmax(self.handle, x.ptr, _dtype_code(x.dtype), n, F, F, mn.ptr, mx.ptr, cnt.ptr), self.handle)
+        check(lib.msm_column_minmax(self.handle, x.ptr, _dtype_code(x.dtype), n, F, int(F if ld is None else ld), mn.ptr,
+                                    mx.ptr, cnt.ptr), self.handle)
         return mn, mx, cnt
 
     def column_moments_partial(self, x: DeviceArray, shift: DeviceArray | None = None,
-                               sums: DeviceArray | None = None):
-        """Raw sums [cnt | S1 | S2] (3F f64) about `shift` (default: row 0) -> (sums, shift)."""
+                               sums: DeviceArray | None = None, ld: int | None = None):
+        """Raw sums [cnt | S1 | S2] (3F f64) about `shift` (default: row 0) -> (sums, shift).
+        ``ld``: row stride in elements when x is a wider buffer's left block."""
         n, F = x.shape
         sums = sums if sums is not None else self.empty((3 * F,), np.float64)
         shift_out = self.empty((F,), np.float64) if shift is None else None  # no allocation in steady state
-        check(lib.msm_column_moments_partial(self.handle, x.ptr, _dtype_code(x.dtype), n, F, F,
+        check(lib.msm_column_moments_partial(self.handle, x.ptr, _dtype_code(x.dtype), n, F, int(F if ld is None else ld),
                                              shift.ptr if shift is not None else None, sums.ptr,
                                              shift_out.ptr if shift_out is not None else None), self.handle)
         return sums, (shift_out if shift_out is not None else shift)
@@ -553,14 +557,15 @@ class Engine:
 
     def project(self, x: DeviceArray, mu: DeviceArray, inv_sigma: DeviceArray, W: DeviceArray, d: int, *,
                 mean2: DeviceArray | None = None, out: DeviceArray | None = None,
-                absmax: DeviceArray | None = None, assume_finite: bool = False) -> DeviceArray:
+                absmax: DeviceArray | None = None, assume_finite: bool = False, ld: int | None = None) -> DeviceArray:
         """`absmax` (one f64, e.g. slot 2 of a k-means fit state) receives max |Y| from the same pass.
-        assume_finite: X holds no NaN (column_moments' count tells); the per-element NaN test is left out."""
+        assume_finite: X holds no NaN (column_moments' count tells); the per-element NaN test is left out.
+        ``ld``: row stride in elements when x is a wider buffer's left block."""
         n, F = x.shape
         ldw = W.shape[1]
         out = out if out is not None else self.empty((n, d), np.float64)
         fn = lib.msm_project_finite if assume_finite else lib.msm_project
-        check(fn(self.handle, x.ptr, _dtype_code(x.dtype), n, F, F, mu.ptr, inv_sigma.ptr,
+        check(fn(self.handle, x.ptr, _dtype_code(x.dtype), n, F, int(F if ld is None else ld), mu.ptr, inv_sigma.ptr,
                  mean2.ptr if mean2 is not None else None, W.ptr, int(d), ldw, out.ptr,
                  out.shape[1], absmax.ptr if absmax is not None else None), self.handle)
         return out
