@@ -133,6 +133,35 @@ msm_status msm_hbond_presence(msm_ctx* ctx, const float* d_xyz, int64_t n, int A
 msm_status msm_dssp(msm_ctx* ctx, const float* d_xyz, int64_t n, int A, const int32_t* d_backbone,
                     const int32_t* d_chain, const uint8_t* d_proline, int R, uint8_t* d_codes);
 
+/* Rigid-body superposition onto a reference (mdtraj Trajectory.superpose as align_trajectory calls it,
+ * S/api/features.py:110-135) and the RMSD to it (the CV "RMSD_ref", S/api/feature_profiles.py:41-45).
+ *   d_sel int32 [S]: the atoms the fit uses, indices into [0, A) (the caller checks the range);
+ *   d_ref float32 [S, 3]: reference positions of those atoms, not centred;
+ *   d_out float32 [n, A, 3] or NULL; it may equal d_xyz (in place) but must not overlap it otherwise;
+ *   d_rmsd float32 [n] or NULL; at least one of the two.
+ * Per frame, with x_i the selected atoms, c their mean and c_ref the mean of d_ref: R is the PROPER rotation
+ * (det +1) minimising sum_i |R (x_i - c) - (r_i - c_ref)|^2;  out_a = R (x_a - c) + c_ref for all A atoms;
+ * rmsd = sqrt(max(0, (G_x + G_r - 2 lambda) / S)), G the sums of squared centred coordinates, lambda the optimal
+ * overlap.  Centroids, G and the 3 x 3 correlation matrix are fp64 sums of the fp32 inputs; R is the eigenvector of
+ * the largest eigenvalue of Horn's 4 x 4 quaternion matrix by cyclic Jacobi in fp64 (at most 16 sweeps); R is
+ * applied in fp32.  A zero correlation matrix (S = 1, coinciding atoms) gives R = identity; a degenerate largest
+ * eigenvalue (collinear atoms, S = 2) gives one of the minimisers; a frame with a non-finite selected coordinate
+ * gets NaN in all its outputs and disturbs no other frame.  Parity with mdtraj's fp32 QCP code is unpinned.
+ * The launch is picked by shape alone:
+ *   d_out given, A <= LDS_ATOMS: a workgroup holds min(TILE_FRAMES, TILE_FLOATS / (3 A)) frames in LDS between
+ *       the accumulate and the apply pass (xyz read once, written once; 16-byte accesses where d_out has d_xyz's
+ *       offset modulo 16 bytes, 4-byte stores otherwise);
+ *   d_out given, A >  LDS_ATOMS: a workgroup per frame, which reads the frame twice;
+ *   d_out NULL: only the S selected atoms of a frame are read;
+ *   the accumulate pass uses 8 lanes per frame for S <= NARROW_SEL and a wave above; for given (S, inputs) the
+ *   RMSD and the rotation have the same bits on every path. */
+#define MSM_SUPERPOSE_TILE_FRAMES 64      /* most frames of one LDS tile */
+#define MSM_SUPERPOSE_TILE_FLOATS 12288   /* coordinates of one LDS tile: 48 KiB; with the per-frame sums 28-60 KiB a workgroup */
+#define MSM_SUPERPOSE_LDS_ATOMS 4096      /* TILE_FLOATS / 3: the largest frame that fits the tile */
+#define MSM_SUPERPOSE_NARROW_SEL 64       /* largest S accumulated on 8 lanes per frame */
+msm_status msm_superpose(msm_ctx* ctx, const float* d_xyz, int64_t n, int A, const int32_t* d_sel, int S,
+                         const float* d_ref, float* d_out, float* d_rmsd);
+
 /* ------------------------------------------------------------------ */
 /* lag-tau transition counts                                            */
 /* ------------------------------------------------------------------ */

@@ -16,6 +16,8 @@ LIB_PATH = Path(__file__).resolve().parent / "csrc" / "libmsmhip.so"
 
 MSM_OK, MSM_ERR_INVALID, MSM_ERR_HIP, MSM_ERR_NOMEM, MSM_ERR_UNSUPPORTED, MSM_ERR_NOCONV = range(6)
 MSM_F32, MSM_F64 = 0, 1
+# launch thresholds of msm_superpose (MSM_SUPERPOSE_* in include/msmhip.h)
+SUPERPOSE_TILE_FRAMES, SUPERPOSE_TILE_FLOATS, SUPERPOSE_LDS_ATOMS, SUPERPOSE_NARROW_SEL = 64, 12288, 4096, 64
 
 
 class MsmError(RuntimeError):
@@ -59,6 +61,7 @@ _PROTOTYPES: dict[str, tuple] = {
     "msm_featurize_sasa": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _i32, _vp]),
     "msm_hbond_presence": (_i32, [_vp, _vp, _i64, _i32, _vp, _i32, C.c_float, C.c_float, _vp]),
     "msm_dssp": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _vp]),
+    "msm_superpose": (_i32, [_vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp]),
     "msm_count_transitions": (_i32, [_vp, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "msm_count_transitions_weighted": (
         _i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),

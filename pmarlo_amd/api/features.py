@@ -1,5 +1,6 @@
-"""compute_features with the on-disk feature cache: mirror of pmarlo.api.features
-(S/api/features.py:27-107 cache file, :192-208 compute_features, :319-342 block assembly).
+"""compute_features with the on-disk feature cache, trajectory alignment and the universal metric: mirror of
+pmarlo.api.features (S/api/features.py:27-107 cache file, :110-135 align_trajectory, :192-208 compute_features,
+:319-342 block assembly, :345-465 compute_universal_metric / compute_universal_embedding).
 
 The cache is the only on-disk format on the path.  File name and
 payload follow the reference, so caches written by either implementation are picked up by the
@@ -17,14 +18,18 @@ import hashlib
 import json
 import logging
 from pathlib import Path
-from typing import List, Optional, Sequence, Tuple
+from typing import Any, Dict, List, Literal, Optional, Sequence, Tuple
 
 import numpy as np
 
 from ..features import get_feature, parse_feature_spec
 from ..features.featurize import trig_expand_periodic
+from ..markov_state_model.reduction import pca_reduce, tica_reduce, vamp_reduce
 
-__all__ = ["compute_features", "feature_cache_file", "trig_expand_periodic"]
+__all__ = ["compute_features", "feature_cache_file", "trig_expand_periodic", "align_trajectory",
+           "compute_universal_metric", "compute_universal_embedding"]
+
+_DEFAULT_UNIVERSAL_SPECS = ["phi_psi", "chi1", "Rg", "sasa", "hbonds_count", "ssfrac"]
 
 logger = logging.getLogger("pmarlo")
 
@@ -142,3 +147,112 @@ def compute_features(traj, feature_specs: Sequence[str], cache_path: Optional[st
     if cache_file is not None:
         np.savez_compressed(cache_file, X=X, columns=np.array(columns, dtype=np.str_), periodic=periodic)
     return X, columns, periodic
+
+
+def align_trajectory(traj, atom_selection: str | Sequence[int] | None = "name CA"):
+    """Superpose all frames onto the first frame on the selected atoms (C-alpha by default; a selection string, None
+    for "name CA", or a sequence of atom indices) and return the trajectory.  As in the reference
+    (S/api/features.py:110-135) the alignment is ``traj.superpose(traj[0], atom_indices=...)``: it acts on ``traj``
+    itself, and an empty selection raises instead of returning the unaligned trajectory."""
+    top = traj.topology
+    if isinstance(atom_selection, str):
+        atom_indices = top.select(atom_selection)
+    elif atom_selection is None:
+        atom_indices = top.select("name CA")
+    else:
+        atom_indices = list(atom_selection)
+
+    if atom_indices is None or len(atom_indices) == 0:
+        raise ValueError("No atoms were selected for trajectory alignment; check the atom selection.")
+
+    ref = traj[0]          # frame 0 before the alignment: superpose replaces traj.xyz, it does not write into it
+    return traj.superpose(ref, atom_indices=atom_indices)
+
+
+def _reduce(Xe: np.ndarray, method: str, lag: int, k: int) -> np.ndarray:
+    if method == "pca":
+        return pca_reduce(Xe, n_components=k)
+    if method == "tica":
+        return tica_reduce(Xe, lag=int(max(1, lag)), n_components=k)
+    return vamp_reduce(Xe, lag=int(max(1, lag)), n_components=k)     # VAMP default
+
+
+def compute_universal_metric(
+    traj,
+    feature_specs: Optional[Sequence[str]] = None,
+    align: bool = True,
+    atom_selection: str | Sequence[int] | None = "name CA",
+    method: Literal["vamp", "tica", "pca"] = "vamp",
+    lag: int = 10,
+    *,
+    cache_path: Optional[str] = None,
+) -> Tuple[np.ndarray, Dict[str, Any]]:
+    """A universal 1D metric from many CVs (S/api/features.py:345-420): optional superposition (C-alpha by default),
+    the default feature set phi/psi, chi1, Rg, SASA, H-bond count, secondary-structure fractions unless specs are
+    given, cos/sin expansion of the periodic columns, then one VAMP / TICA / PCA component.  Returns the metric
+    (n_frames,) and metadata.
+
+    Every default feature is invariant under rigid motion, so the alignment changes the metric only through the
+    fp32 rounding of the moved coordinates; its use is the aligned coordinates themselves and ``RMSD_ref``."""
+    logger.info("[universal] Starting computation (align=%s, method=%s, lag=%s)", bool(align), method, int(lag))
+    traj_in = align_trajectory(traj, atom_selection=atom_selection) if align else traj
+    if align:
+        logger.info("[universal] Alignment complete: %d frames", traj_in.n_frames)
+    specs = list(feature_specs) if feature_specs is not None else list(_DEFAULT_UNIVERSAL_SPECS)
+    logger.info("[universal] Computing features: %s", ", ".join(specs))
+    X, cols, periodic = compute_features(traj_in, feature_specs=specs, cache_path=cache_path)
+    logger.info("[universal] Features computed: shape=%s, columns=%d", tuple(X.shape), len(cols))
+    if X.size == 0:
+        return np.zeros((traj.n_frames,), dtype=float), {
+            "columns": cols,
+            "periodic": periodic,
+            "reduction": method,
+            "lag": int(lag),
+            "aligned": bool(align),
+            "specs": specs,
+        }
+    Xe, index_map = trig_expand_periodic(X, periodic)
+    logger.info("[universal] Expanded shape=%s; reducing with %s -> 1D", tuple(Xe.shape), method)
+    metric = _reduce(Xe, method, lag, 1).reshape(-1)
+    meta: Dict[str, Any] = {
+        "columns": cols,
+        "periodic": periodic,
+        "reduction": method,
+        "lag": int(lag),
+        "aligned": bool(align),
+        "specs": specs,
+        "index_map": index_map,
+    }
+    return metric, meta
+
+
+def compute_universal_embedding(
+    traj,
+    feature_specs: Optional[Sequence[str]] = None,
+    align: bool = True,
+    atom_selection: str | Sequence[int] | None = "name CA",
+    method: Literal["vamp", "tica", "pca"] = "vamp",
+    lag: int = 10,
+    n_components: int = 2,
+    *,
+    cache_path: Optional[str] = None,
+) -> Tuple[np.ndarray, Dict[str, Any]]:
+    """A universal low-dimensional embedding (>= 1D) from many CVs (S/api/features.py:423-465): array of shape
+    (n_frames, n_components) and metadata."""
+    specs = list(feature_specs) if feature_specs is not None else list(_DEFAULT_UNIVERSAL_SPECS)
+    traj_in = align_trajectory(traj, atom_selection=atom_selection) if align else traj
+    X, cols, periodic = compute_features(traj_in, feature_specs=specs, cache_path=cache_path)
+    Xe, index_map = trig_expand_periodic(X, periodic)
+    k = int(max(1, n_components))
+    Y = _reduce(Xe, method, lag, k)
+    meta: Dict[str, Any] = {
+        "columns": cols,
+        "periodic": periodic,
+        "reduction": method,
+        "lag": int(lag),
+        "aligned": bool(align),
+        "specs": specs,
+        "n_components": k,
+        "index_map": index_map,
+    }
+    return Y, meta

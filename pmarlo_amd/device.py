@@ -354,6 +354,47 @@ class Engine:
                                           int(col0)), self.handle)
         return out
 
+    def _superpose_args(self, xyz: DeviceArray, sel, ref):
+        if xyz.dtype != np.float32 or len(xyz.shape) != 3 or xyz.shape[2] != 3:
+            raise ValueError("xyz must be float32 with shape (n_frames, n_atoms, 3)")
+        A = xyz.shape[1]
+        s = np.ascontiguousarray(sel, np.int32).reshape(-1)
+        if s.size and (s.min() < 0 or s.max() >= A):
+            raise ValueError(f"atom index out of range [0, {A})")
+        r = np.ascontiguousarray(ref, np.float32)
+        if r.shape != (s.size, 3):
+            raise ValueError(f"ref must have shape ({s.size}, 3): the reference positions of the selected atoms, "
+                             f"got {r.shape}")
+        # S = 0 travels on to the library, whose message names the rule; an empty upload is not possible
+        return (self.to_device(s) if s.size else None), (self.to_device(r) if s.size else None), int(s.size)
+
+    def superpose(self, xyz: DeviceArray, sel, ref, *, out: DeviceArray | None = None, want_rmsd: bool = True):
+        """Rigid-body fit of every frame of xyz (float32 [n, A, 3]) onto `ref` (float32 [S, 3], the reference
+        positions of the atoms `sel`): (aligned float32 [n, A, 3], rmsd float32 [n] or None).  The rotation is
+        proper (det +1) and is applied to all atoms; `out` may be xyz itself (in place)."""
+        sd, rd, S = self._superpose_args(xyz, sel, ref)
+        n, A, _ = xyz.shape
+        if out is None:
+            out = self.empty((n, A, 3), np.float32)
+        elif out.dtype != np.float32 or tuple(out.shape) != (n, A, 3):
+            raise ValueError(f"out must be float32 with shape {(n, A, 3)}")
+        rmsd = self.empty((n,), np.float32) if want_rmsd else None
+        check(lib.msm_superpose(self.handle, xyz.ptr, n, A, sd.ptr if sd else None, S, rd.ptr if rd else None, out.ptr,
+                                rmsd.ptr if rmsd is not None else None), self.handle)
+        self.sync()  # index and reference tables are freed on return
+        return out, rmsd
+
+    def rmsd(self, xyz: DeviceArray, sel, ref) -> DeviceArray:
+        """RMSD of every frame to `ref` after the optimal proper rotation, float32 [n]; reads the selected atoms
+        only."""
+        sd, rd, S = self._superpose_args(xyz, sel, ref)
+        n, A, _ = xyz.shape
+        rmsd = self.empty((n,), np.float32)
+        check(lib.msm_superpose(self.handle, xyz.ptr, n, A, sd.ptr if sd else None, S, rd.ptr if rd else None, None,
+                                rmsd.ptr), self.handle)
+        self.sync()
+        return rmsd
+
     # -- transition counts ----------------------------------------------------
     @staticmethod
     def _seg_ptrs(starts: np.ndarray, stops: np.ndarray):

@@ -15,7 +15,7 @@ from .base import register_feature
 
 __all__ = ["PhiPsiFeature", "Chi1Feature", "DistanceFeature", "AngleFeature", "DihedralFeature",
            "RadiusOfGyrationFeature", "DistancePairFeature", "ContactsPairFeature", "SASAFeature",
-           "HBondsCountFeature", "SecondaryStructureFractionFeature"]
+           "HBondsCountFeature", "SecondaryStructureFractionFeature", "RMSDToReferenceFeature"]
 
 
 def _device_features(traj, **kw) -> np.ndarray:
@@ -122,6 +122,35 @@ class RadiusOfGyrationFeature:
         eng = get_engine()
         out = eng.featurize_rg(eng.to_device(np.ascontiguousarray(traj.xyz, np.float32)))
         self.labels = ["Rg"]
+        return out.to_host().reshape(-1, 1).astype(float)
+
+    def is_periodic(self) -> np.ndarray:
+        return self._periodic
+
+
+class RMSDToReferenceFeature:
+    """``RMSD_ref``: RMSD (nm) of every frame to frame ``ref`` of the same trajectory after the optimal proper
+    rotation on ``selection`` (C-alpha by default; a selection string or a sequence of atom indices) -- the second
+    canonical CV of S/api/feature_profiles.py:41-45 ("CA-aligned RMSD relative to the reference structure").  Not
+    periodic.  What is computed is the mathematical definition; parity with mdtraj's fp32 QCP code is unpinned."""
+
+    name = "RMSD_ref"
+
+    def __init__(self) -> None:
+        self._periodic = np.array([False], dtype=bool)
+        self.labels: list[str] | None = None
+
+    def compute(self, traj, ref=0, selection="name CA", **kwargs) -> np.ndarray:
+        sel = traj.topology.select(selection) if isinstance(selection, str) else np.asarray(list(selection), dtype=int)
+        if len(sel) == 0:
+            raise ValueError(f"RMSD_ref: the selection {selection!r} matches no atoms")
+        ref = int(ref)
+        if not 0 <= ref < traj.n_frames:
+            raise ValueError(f"RMSD_ref: reference frame {ref} out of range [0, {traj.n_frames})")
+        xyz = np.ascontiguousarray(traj.xyz, np.float32)
+        eng = get_engine()
+        out = eng.rmsd(eng.to_device(xyz), sel, xyz[ref][np.asarray(sel, dtype=int)])
+        self.labels = ["RMSD_ref"]
         return out.to_host().reshape(-1, 1).astype(float)
 
     def is_periodic(self) -> np.ndarray:
@@ -265,5 +294,5 @@ class SecondaryStructureFractionFeature:
 
 for _cls in (PhiPsiFeature, Chi1Feature, DistanceFeature, AngleFeature, DihedralFeature, RadiusOfGyrationFeature,
              DistancePairFeature, ContactsPairFeature, SASAFeature, HBondsCountFeature,
-             SecondaryStructureFractionFeature):
+             SecondaryStructureFractionFeature, RMSDToReferenceFeature):
     register_feature(_cls())

@@ -145,6 +145,28 @@ class Trajectory:
             xyz = xyz[None]
         return Trajectory(xyz, self.topology)
 
+    def superpose(self, reference: "Trajectory", frame: int = 0, atom_indices=None, ref_atom_indices=None) -> "Trajectory":
+        """mdtraj's ``Trajectory.superpose`` (without ``parallel``) on the device: every frame is centred on
+        ``atom_indices`` (None: all atoms), rotated by the proper rotation that fits those atoms best onto
+        ``ref_atom_indices`` (None: the same indices) of ``reference[frame]``, and moved to that reference's centroid.
+        Replaces ``self.xyz`` and returns ``self``.  Parity with mdtraj's fp32 QCP code is unpinned."""
+        from ..device import get_engine
+
+        sel = np.arange(self.n_atoms) if atom_indices is None else np.asarray(atom_indices, dtype=int).reshape(-1)
+        ref_sel = sel if ref_atom_indices is None else np.asarray(ref_atom_indices, dtype=int).reshape(-1)
+        if len(sel) != len(ref_sel):
+            raise ValueError(f"atom_indices ({len(sel)}) and ref_atom_indices ({len(ref_sel)}) differ in length")
+        if not 0 <= int(frame) < reference.n_frames:
+            raise ValueError(f"reference frame {frame} out of range [0, {reference.n_frames})")
+        if ref_sel.size and (ref_sel.min() < 0 or ref_sel.max() >= reference.n_atoms):
+            raise ValueError(f"atom index out of range [0, {reference.n_atoms})")
+        ref = np.array(reference.xyz[int(frame)][ref_sel], dtype=np.float32)
+        eng = get_engine()
+        xd = eng.to_device(self.xyz)
+        out, _ = eng.superpose(xd, sel, ref, out=xd, want_rmsd=False)
+        self.xyz = out.to_host()
+        return self
+
 
 def load_pdb(path: str | Path) -> Trajectory:
     """Read ATOM/HETATM records of every MODEL (coordinates in Angstrom -> nm)."""
