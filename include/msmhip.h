@@ -785,6 +785,54 @@ msm_status msm_first_occurrence(msm_ctx* ctx, const int32_t* d_flat, int64_t n, 
 msm_status msm_relabel(msm_ctx* ctx, const int32_t* d_flat, int64_t n, const int32_t* d_map, int n_cells,
                        int32_t* d_labels);
 
+/* ---- representative frames of a state ---------------------------------------------------------
+ * Replaces the per-state host loops of RepresentativePicker (S/conformations/
+ * representative_picker.py) and _find_representatives (S/markov_state_model/_states.py:131-157).
+ * Features d_x f64 [n, ld] with d <= MSM_REP_MAX_D (MSM_ERR_UNSUPPORTED above), labels int32 [n],
+ * optional weights f64 [n] (NULL: w = 1), n < 2^31.  Every output is the same bytes on every run.
+ * msm_group_by_label: d_members int32 [n] holds, for s = 0 .. k-1 in turn, the frames with label s
+ *   in ascending order (np.where(labels == s)); state s = d_members[d_offsets[s] : d_offsets[s+1]],
+ *   d_offsets int64 [k + 1].  Labels outside [0, k) belong to no state; d_members past
+ *   d_offsets[k] is not written.  Frames are ranked in chunks of MSM_REP_GROUP_CHUNK.
+ * msm_state_centroids: d_wsum[s] = sum w, d_centroid f64 [k, d] = sum w x / sum w over the members in
+ *   a fixed order (0 for an empty state), d_flags int32 [k] = MSM_REP_FLAG_* bits of the state's
+ *   weights (0 for an empty state).
+ * msm_state_scores: d_scores f64, laid out like d_members.  MSM_REP_SCORE_CENTROID: |x_i - c_s|_2 for
+ *   every member of every state (needs d_labels, d_centroid; the state list is not read).
+ *   MSM_REP_SCORE_MEDOID: sum_j w^_j |x_i - x_j|_2 over the members j of i's state, w^ = w / sum w or
+ *   1 / n_s, for the states h_states[0 .. n_states) only (needs d_wsum); tasks of MSM_REP_TILE_I rows
+ *   against tiles of MSM_REP_TILE_J rows are built from h_offsets (the host copy of d_offsets) and
+ *   uploaded, so this mode is not capturable.  Both take direct differences under the root.
+ * msm_state_select: d_picks int32 [n_states, n_reps], frame indices, -1 where a state has fewer than
+ *   n_reps members; h_states distinct.  MSM_REP_SELECT_SMALLEST: the members with the smallest
+ *   (score, frame), in that order.  MSM_REP_SELECT_DIVERSE: the member with the smallest score
+ *   (lowest frame on ties), then repeatedly the member farthest from everything picked so far
+ *   (max-min walk, lowest frame on ties); d_scores holds centroid distances, d_mind f64 is workspace
+ *   laid out like d_scores.  Uploads the state list: not capturable. */
+#define MSM_REP_MAX_D 256
+#define MSM_REP_GROUP_CHUNK 1024
+#define MSM_REP_TILE_I 128
+#define MSM_REP_TILE_J 64
+#define MSM_REP_FLAG_NONFINITE 1
+#define MSM_REP_FLAG_NEGATIVE 2
+#define MSM_REP_FLAG_NONPOSITIVE_SUM 4
+#define MSM_REP_SCORE_CENTROID 0
+#define MSM_REP_SCORE_MEDOID 1
+#define MSM_REP_SELECT_SMALLEST 0
+#define MSM_REP_SELECT_DIVERSE 1
+msm_status msm_group_by_label(msm_ctx* ctx, const int32_t* d_labels, int64_t n, int k, int64_t* d_offsets,
+                              int32_t* d_members);
+msm_status msm_state_centroids(msm_ctx* ctx, const double* d_x, int64_t n, int d, int64_t ld, const double* d_w,
+                               const int64_t* d_offsets, const int32_t* d_members, int k, double* d_centroid,
+                               double* d_wsum, int32_t* d_flags);
+msm_status msm_state_scores(msm_ctx* ctx, const double* d_x, int64_t n, int d, int64_t ld, const double* d_w,
+                            const int32_t* d_labels, const int64_t* d_offsets, const int32_t* d_members, int k,
+                            const double* d_centroid, const double* d_wsum, int mode, const int64_t* h_offsets,
+                            const int32_t* h_states, int n_states, double* d_scores);
+msm_status msm_state_select(msm_ctx* ctx, const double* d_x, int64_t n, int d, int64_t ld, const int64_t* d_offsets,
+                            const int32_t* d_members, int k, const double* d_scores, double* d_mind, int mode,
+                            const int32_t* h_states, int n_states, int n_reps, int32_t* d_picks);
+
 /* ------------------------------------------------------------------ */
 /* exchange steps of the sharded path (RCCL over xGMI)                  */
 /* ------------------------------------------------------------------ */

@@ -18,6 +18,12 @@ MSM_OK, MSM_ERR_INVALID, MSM_ERR_HIP, MSM_ERR_NOMEM, MSM_ERR_UNSUPPORTED, MSM_ER
 MSM_F32, MSM_F64 = 0, 1
 # launch thresholds of msm_superpose (MSM_SUPERPOSE_* in include/msmhip.h)
 SUPERPOSE_TILE_FRAMES, SUPERPOSE_TILE_FLOATS, SUPERPOSE_LDS_ATOMS, SUPERPOSE_NARROW_SEL = 64, 12288, 4096, 64
+# representative frames (MSM_REP_* in include/msmhip.h): widest feature row, frames per grouping chunk, the
+# i- and j-tiles of the all-pairs medoid pass, weight flags, score and selection modes
+REP_MAX_D, REP_GROUP_CHUNK, REP_TILE_I, REP_TILE_J = 256, 1024, 128, 64
+REP_FLAG_NONFINITE, REP_FLAG_NEGATIVE, REP_FLAG_NONPOSITIVE_SUM = 1, 2, 4
+REP_SCORE_CENTROID, REP_SCORE_MEDOID = 0, 1
+REP_SELECT_SMALLEST, REP_SELECT_DIVERSE = 0, 1
 
 
 class MsmError(RuntimeError):
@@ -149,6 +155,10 @@ _PROTOTYPES: dict[str, tuple] = {
     "msm_first_occurrence": (_i32, [_vp, _vp, _i64, _i32, _vp]),
     "msm_relabel": (_i32, [_vp, _vp, _i64, _vp, _i32, _vp]),
     "msm_ck_test": (_i32, [_vp, _vp, _i64, _vp, _i64, _i64, _i32, _vp, _i32, _vp, _i64, _vp, _vp]),
+    "msm_group_by_label": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp]),
+    "msm_state_centroids": (_i32, [_vp, _vp, _i64, _i32, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
+    "msm_state_scores": (_i32, [_vp, _vp, _i64, _i32, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp]),
+    "msm_state_select": (_i32, [_vp, _vp, _i64, _i32, _i64, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _vp]),
 }
 
 DECLARED_SYMBOLS = tuple(_PROTOTYPES)

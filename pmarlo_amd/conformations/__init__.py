@@ -1,0 +1,9 @@
+"""pmarlo.conformations on the MI355X engine: representative frames of conformational states."""
+from .representative_picker import (  # noqa: F401
+    FrameIndexLookup,
+    RepresentativeFrame,
+    RepresentativePicker,
+    TrajectoryFrameLocator,
+    TrajectorySegment,
+    build_frame_index_lookup,
+)

@@ -868,6 +868,62 @@ class Engine:
               self.handle)
         return float(score.to_host()[0]), samples
 
+    # -- representative frames of a state -----------------------------------------------------------
+    def group_by_label(self, labels: DeviceArray, k: int) -> tuple[DeviceArray, DeviceArray]:
+        """(offsets int64 [k + 1], members int32 [n]): members[offsets[s]:offsets[s + 1]] are the frames with label s,
+        ascending (np.where); labels outside [0, k) belong to no state."""
+        n = labels.size
+        offsets = self.empty((int(k) + 1,), np.int64)
+        members = self.empty((n,), np.int32)
+        check(lib.msm_group_by_label(self.handle, labels.ptr, n, int(k), offsets.ptr, members.ptr), self.handle)
+        return offsets, members
+
+    def state_centroids(self, x: DeviceArray, offsets: DeviceArray, members: DeviceArray,
+                        weights: DeviceArray | None = None) -> tuple[DeviceArray, DeviceArray, DeviceArray]:
+        """(centroid f64 [k, d], weight sum f64 [k], REP_FLAG_* bits int32 [k]) of the grouped states of x f64 [n, d]."""
+        n, d = x.shape
+        k = offsets.size - 1
+        cen, wsum, flags = self.empty((k, d), np.float64), self.empty((k,), np.float64), self.empty((k,), np.int32)
+        check(lib.msm_state_centroids(self.handle, x.ptr, n, d, d, weights.ptr if weights is not None else None, offsets.ptr,
+                                      members.ptr, k, cen.ptr, wsum.ptr, flags.ptr), self.handle)
+        return cen, wsum, flags
+
+    def state_scores(self, x: DeviceArray, labels: DeviceArray, offsets: DeviceArray, members: DeviceArray,
+                     h_offsets: np.ndarray, *, centroid: DeviceArray | None = None, wsum: DeviceArray | None = None,
+                     weights: DeviceArray | None = None, states=None) -> DeviceArray:
+        """Scores f64 laid out like `members`.  With `states` None: distance of every member to its state's centroid.
+        With a list of states: the medoid score sum_j w^_j |x_i - x_j| of the members of those states (the words of
+        other states are left unwritten)."""
+        n, d = x.shape
+        k = offsets.size - 1
+        ho = np.ascontiguousarray(h_offsets, np.int64)
+        scores = self.empty((n,), np.float64)
+        if states is None:
+            mode, hs, ns = _lib.REP_SCORE_CENTROID, None, 0
+        else:
+            st = np.ascontiguousarray(states, np.int32).reshape(-1)
+            mode, hs, ns = _lib.REP_SCORE_MEDOID, st.ctypes.data, st.size
+        check(lib.msm_state_scores(self.handle, x.ptr, n, d, d, weights.ptr if weights is not None else None, labels.ptr,
+                                   offsets.ptr, members.ptr, k, centroid.ptr if centroid is not None else None,
+                                   wsum.ptr if wsum is not None else None, mode, ho.ctypes.data, hs, ns, scores.ptr),
+              self.handle)
+        return scores
+
+    def state_select(self, x: DeviceArray, offsets: DeviceArray, members: DeviceArray, scores: DeviceArray, states,
+                     n_reps: int, *, diverse: bool = False) -> np.ndarray:
+        """Picks int32 [len(states), n_reps] (frame indices, -1 past a state's size) for distinct `states`: the members
+        with the smallest (score, frame), or with `diverse` the max-min walk from the member with the smallest score."""
+        n, d = x.shape
+        k = offsets.size - 1
+        st = np.ascontiguousarray(states, np.int32).reshape(-1)
+        picks = self.empty((st.size, int(n_reps)), np.int32)
+        mind = self.empty((n,), np.float64) if diverse else None
+        check(lib.msm_state_select(self.handle, x.ptr, n, d, d, offsets.ptr, members.ptr, k, scores.ptr,
+                                   mind.ptr if diverse else None,
+                                   _lib.REP_SELECT_DIVERSE if diverse else _lib.REP_SELECT_SMALLEST, st.ctypes.data, st.size,
+                                   int(n_reps), picks.ptr), self.handle)
+        return picks.to_host()   # synchronises: the workspace is free on return
+
     # -- regular-grid microstates ---------------------------------------------------------------
     def grid_cells(self, x: DeviceArray, edges: np.ndarray) -> DeviceArray:
         """Flat cell index per frame for edges [F, bins + 1] (np.digitize - 1, clipped)."""

@@ -145,6 +145,22 @@ class Trajectory:
             xyz = xyz[None]
         return Trajectory(xyz, self.topology)
 
+    def save_pdb(self, path: str | Path) -> None:
+        """Fixed-column ATOM records from the topology, one MODEL per frame, nm -> Angstrom (8.3f: 1e-3 A)."""
+        top = self.topology
+        chains = top.chain_ids or [" "] * self.n_atoms
+        with open(path, "w") as fh:
+            for m, frame in enumerate(np.asarray(self.xyz, dtype=np.float64) * 10.0):
+                fh.write(f"MODEL     {m + 1:4d}\n")
+                for i, (x, y, z) in enumerate(frame):
+                    name = top.atom_names[i]
+                    name = f" {name:<3s}" if len(name) < 4 else name[:4]   # a short name starts in column 14
+                    fh.write(f"ATOM  {int(top.serials[i]) % 100000:5d} {name} {top.res_names[i][:3]:>3s} "
+                             f"{(chains[i] or ' ')[:1]}{int(top.res_seq[i]) % 10000:4d}    {x:8.3f}{y:8.3f}{z:8.3f}"
+                             f"  1.00  0.00          {top.elements[i][:2]:>2s}\n")
+                fh.write("ENDMDL\n")
+            fh.write("END\n")
+
     def superpose(self, reference: "Trajectory", frame: int = 0, atom_indices=None, ref_atom_indices=None) -> "Trajectory":
         """mdtraj's ``Trajectory.superpose`` (without ``parallel``) on the device: every frame is centred on
         ``atom_indices`` (None: all atoms), rotated by the proper rotation that fits those atoms best onto

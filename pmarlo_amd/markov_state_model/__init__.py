@@ -19,3 +19,4 @@ from .tpt import (ReactiveFlux, coarse_grain_flux, compute_committor, compute_ma
                   compute_macro_populations, find_bottleneck_states, identify_transition_state_ensemble,
                   lump_micro_to_macro_T, pathway_decomposition, reactive_flux)
 from .results import ConnectedCountResult, ITSResult, MSMEstimate  # noqa: F401
+from .states import find_representatives  # noqa: F401
