@@ -763,6 +763,42 @@ msm_status msm_lump_macro(msm_ctx* ctx, const double* d_T, int64_t ldt, const do
 msm_status msm_macro_mfpt(msm_ctx* ctx, const double* d_T, int64_t ldt, int n, double* d_mfpt,
                           int32_t* d_info);
 
+/* ---- trajectory bootstrap in batch (csrc/bootstrap.hip) ----------------------------------------
+ * The device side of UncertaintyQuantifier (S/conformations/uncertainty.py:31-261): every bootstrap sample
+ * resamples whole trajectories with replacement and rebuilds the MSM (_rebuild_msm, :506-530).  Counts are
+ * additive over trajectories, so trajectory s is counted once (msm_count_transitions into slice s of an int64
+ * [n_seg, k*k] buffer) and sample b is the integer combination below; the committor systems of all samples are
+ * then solved by one launch.
+ * msm_combine_counts: d_seg_counts int64 [n_seg, cells]; d_mult int32 [n_boot, ld_mult], column s = how often
+ *   trajectory s occurs in sample b (ld_mult >= n_seg lets a chunk of trajectories point into a wider table);
+ *   d_counts int64 [n_boot, cells] OVERWRITTEN with C_b = sum_s mult[b, s] * C_s, or ADDED TO when accumulate != 0
+ *   (further chunks of trajectories).  Integer arithmetic: exact, no atomics.  1 <= n_seg <= MSM_COMBINE_MAX_SEG
+ *   per call (the values of a cell stay in registers while the samples stream past).
+ * msm_row_normalise_batched: d_counts int64 [batch, k, k] -> d_T f64 [batch, k, k] OVERWRITTEN, T = C / rowsum as
+ *   the IEEE double quotient of the two integers, all-zero rows stay zero (msm_transition_matrix mode 0;
+ *   uncertainty.py:519-522); d_rowsum int64 [batch, k] OVERWRITTEN.
+ * msm_reactive_flux_batched: msm_reactive_flux for `batch` matrices (sample b at d_T + b*t_stride, row stride ldt),
+ *   d_pi f64 [batch, n], ONE d_role int32 [n] for all; d_qplus / d_qminus f64 [batch, n] OVERWRITTEN (may be NULL
+ *   together), d_totals f64 [batch, 4] = {F, Z, rate, mfpt} OVERWRITTEN (may be NULL when the committors are asked
+ *   for), d_info int32 [batch, 2] (forward, backward solve) OVERWRITTEN.  Gross and net flux are not written.
+ *   One workgroup per sample.  n <= MSM_FLUX_LDS_MAX_N: the system matrix and its right-hand side stay in LDS,
+ *   (n*n + n) * 8 bytes <= 128 KiB of the 160 KiB a gfx950 workgroup can have; above, in slab b of the context
+ *   scratch (msm_reactive_flux_batched_scratch_bytes tells the caller how much a batch takes, so that it can
+ *   split one).  Same pivot rule and per-element fma recurrences as msm_solve_f64 on both paths: the committors
+ *   of sample b have the bits msm_reactive_flux returns for that matrix alone; the totals are summed in a fixed
+ *   order of their own.  A singular system sets d_info of its sample only (committors and totals of that sample
+ *   NaN); the other samples are unaffected. */
+#define MSM_COMBINE_MAX_SEG 32      /* trajectories per msm_combine_counts call */
+#define MSM_FLUX_LDS_MAX_N 127      /* largest n of the LDS-resident committor solve */
+msm_status msm_combine_counts(msm_ctx* ctx, const int64_t* d_seg_counts, const int32_t* d_mult, int64_t ld_mult,
+                              int n_seg, int n_boot, int64_t cells, int64_t* d_counts, int accumulate);
+msm_status msm_row_normalise_batched(msm_ctx* ctx, const int64_t* d_counts, int k, int batch, double* d_T,
+                                     int64_t* d_rowsum);
+size_t msm_reactive_flux_batched_scratch_bytes(int n, int batch, int want_committors);
+msm_status msm_reactive_flux_batched(msm_ctx* ctx, const double* d_T, int64_t t_stride, int64_t ldt,
+                                     const double* d_pi, const int32_t* d_role, int n, int batch, double* d_qplus,
+                                     double* d_qminus, double* d_totals, int32_t* d_info);
+
 /* ---- silhouette score (n_states = "auto") ---------------------------------------------------
  * Replaces sklearn.metrics.silhouette_score in _auto_select_n_states (S/markov_state_model/
  * clustering.py:156-233).  d_x f64 [n, ld]: the points SORTED BY CLUSTER, cluster c = rows

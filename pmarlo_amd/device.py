@@ -986,6 +986,98 @@ class Engine:
         check(lib.msm_macro_mfpt(self.handle, T.ptr, n, n, out.ptr, info.ptr), self.handle)
         return out, info.to_host()
 
+    # -- trajectory bootstrap in batch ---------------------------------------------------------------
+    def combine_counts(self, seg_counts: DeviceArray, mult: DeviceArray, *, seg0: int = 0, out: DeviceArray | None = None,
+                       accumulate: bool = False) -> DeviceArray:
+        """C_b = sum_s mult[b, seg0 + s] * seg_counts[s]: int64 [n_boot, ...] from per-trajectory counts int64
+        [n_seg, ...] and the multiplicity table int32 [n_boot, >= seg0 + n_seg]; added to `out` when accumulate."""
+        n_seg, n_boot, ld = seg_counts.shape[0], mult.shape[0], mult.shape[1]
+        if seg_counts.dtype != np.int64 or mult.dtype != np.int32:
+            raise TypeError("seg_counts must be int64 and mult int32")
+        if seg0 < 0 or seg0 + n_seg > ld:
+            raise ValueError("the multiplicity table has no columns for these trajectories")
+        cells = seg_counts.size // n_seg
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate needs the array to add to")
+            out = self.empty((n_boot,) + tuple(seg_counts.shape[1:]), np.int64)
+        for s in range(0, n_seg, _lib.COMBINE_MAX_SEG):
+            m = min(_lib.COMBINE_MAX_SEG, n_seg - s)
+            check(lib.msm_combine_counts(self.handle, seg_counts.ptr + 8 * s * cells, mult.ptr + 4 * (seg0 + s), ld, m,
+                                         n_boot, cells, out.ptr, int(accumulate or s > 0)), self.handle)
+        return out
+
+    def row_normalise_batched(self, counts: DeviceArray, T: DeviceArray | None = None,
+                              rowsum: DeviceArray | None = None) -> tuple[DeviceArray, DeviceArray]:
+        """counts int64 [batch, k, k] -> T f64 [batch, k, k] = C / rowsum (zero rows stay zero), rowsum int64 [batch, k]."""
+        batch, k = counts.shape[0], counts.shape[-1]
+        if counts.dtype != np.int64:
+            raise TypeError("counts must be int64")
+        T = T if T is not None else self.empty((batch, k, k), np.float64)
+        rowsum = rowsum if rowsum is not None else self.empty((batch, k), np.int64)
+        check(lib.msm_row_normalise_batched(self.handle, counts.ptr, k, batch, T.ptr, rowsum.ptr), self.handle)
+        return T, rowsum
+
+    def reactive_flux_batched(self, T: DeviceArray, pi: DeviceArray, role: np.ndarray, *, want_committors: bool = True,
+                              chunk_bytes: int = 1 << 30) -> dict:
+        """msm_reactive_flux_batched on T [batch, n, n], pi [batch, n] and one role [n]: committors [batch, n] (or
+        None), totals [batch, 4] = {F, Z, rate, mfpt} on the device, info [batch, 2] on the host.  The batch is split
+        so that the solver's scratch stays within chunk_bytes (at least one sample a call); the results do not
+        depend on the split."""
+        batch, n = T.shape[0], T.shape[-1]
+        rd = self.to_device(np.ascontiguousarray(role, np.int32))
+        qp = qm = None
+        if want_committors:
+            qp, qm = self.empty((batch, n), np.float64), self.empty((batch, n), np.float64)
+        tot = self.empty((batch, 4), np.float64)
+        info = self.empty((batch, 2), np.int32)
+        per_sample = int(lib.msm_reactive_flux_batched_scratch_bytes(n, 1, int(want_committors)))
+        step = batch if per_sample == 0 else max(1, min(batch, int(chunk_bytes) // per_sample))
+        for b in range(0, batch, step):
+            m = min(step, batch - b)
+            check(lib.msm_reactive_flux_batched(self.handle, T.ptr + 8 * b * n * n, n * n, n, pi.ptr + 8 * b * n, rd.ptr,
+                                                n, m, qp.ptr + 8 * b * n if qp is not None else None,
+                                                qm.ptr + 8 * b * n if qm is not None else None, tot.ptr + 32 * b,
+                                                info.ptr + 8 * b), self.handle)
+        return {"qplus": qp, "qminus": qm, "totals": tot, "info": info.to_host()}
+
+    def bootstrap_transition_matrices(self, labels: DeviceArray, starts, stops, k: int, lag: int, mult: np.ndarray, *,
+                                      chunk_bytes: int = 1 << 28) -> tuple[DeviceArray, DeviceArray]:
+        """Transition matrices of trajectory resamples: T f64 [n_boot, k, k] and rowsum int64 [n_boot, k] from the
+        labels of all trajectories (trajectory s = labels[starts[s]:stops[s]]) and the multiplicity table
+        mult [n_boot, n_seg].  Every trajectory is counted once; a resample's counts are the integer combination.
+        Neither the per-trajectory counts nor the resampled counts need fit at once: both are walked in chunks of
+        at most chunk_bytes (at least one matrix), the resamples on the outside, so that with several chunks of
+        both the trajectories are counted again per chunk of resamples."""
+        starts, stops = self._seg_ptrs(starts, stops)
+        mult = np.ascontiguousarray(mult, np.int32)
+        n_seg = len(starts)
+        if mult.ndim != 2 or mult.shape[1] != n_seg or n_seg == 0 or mult.shape[0] == 0:
+            raise ValueError("mult must be [n_boot, n_seg] with at least one sample and one trajectory")
+        n_boot, mat = mult.shape[0], k * k * 8
+        seg_step = max(1, min(n_seg, int(chunk_bytes) // mat))
+        boot_step = max(1, min(n_boot, int(chunk_bytes) // mat))
+        mult_d = self.to_device(mult)
+        T = self.empty((n_boot, k, k), np.float64)
+        rowsum = self.empty((n_boot, k), np.int64)
+        seg_counts = self.empty((seg_step, k, k), np.int64)
+        counts = self.empty((boot_step, k, k), np.int64)
+        counted = None                       # the chunk of trajectories seg_counts holds
+        for b in range(0, n_boot, boot_step):
+            nb = min(boot_step, n_boot - b)
+            for s in range(0, n_seg, seg_step):
+                ns = min(seg_step, n_seg - s)
+                if counted != s:
+                    for t in range(ns):
+                        self.count_transitions(labels, k, lag, starts=starts[s + t:s + t + 1], stops=stops[s + t:s + t + 1],
+                                               out=seg_counts.view((k, k), offset_elems=t * k * k))
+                    counted = s
+                self.combine_counts(seg_counts.view((ns, k, k)), mult_d.view((nb, n_seg), offset_elems=b * n_seg),
+                                    seg0=s, out=counts.view((nb, k, k)), accumulate=s > 0)
+            self.row_normalise_batched(counts.view((nb, k, k)), T.view((nb, k, k), offset_elems=b * k * k),
+                                       rowsum.view((nb, k), offset_elems=b * k))
+        return T, rowsum
+
     # -- free-energy surfaces ---------------------------------------------------
     def weighted_stats(self, x: DeviceArray, col: int = 0, weights: DeviceArray | None = None) -> np.ndarray:
         """[sum w, sum w^2, weighted mean, weighted variance, min, max] of column `col` of x [n, d] (or of a
