@@ -984,7 +984,7 @@ msm_status launch_filter_dp(msm_ctx* ctx, const T* x, int64_t n, int d, int64_t 
     // (the centre tables are built by every workgroup of the kernel for itself: no staging launch)
     msm_status rs;
     const int64_t n_units = (n + 16 * NF - 1) / (16 * NF);
-    const int kWaves = filter_waves(DP, ACCUM);
+    const int kWaves = filter_waves(DP, ACCUM, sizeof(T) == 8 && !mean);
     const int grid = (int)std::min<int64_t>((n_units + kWaves - 1) / kWaves, (int64_t)ctx->n_cu);
     unsigned long long* stats = nullptr;
     rs = filter_stats_buffer(ctx, &stats);

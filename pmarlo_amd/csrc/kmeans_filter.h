@@ -55,7 +55,12 @@
 //
 // Schedule.  One workgroup of kFilterWaves waves per CU builds the centre tables in its LDS and then takes units of
 // 64 frames: tile loop (matrix pipe + top-two bookkeeping), the loads of the next unit's images and of this unit's
-// coordinates, the cross-lane step, the candidate pick, the commit, step 4 for what is left.  (Step 4 as a scan of all
+// coordinates, the cross-lane step, the candidate pick, the commit, step 4 for what is left.  The d <= 10 accumulate
+// passes keep a frame's fp64 coordinates only until their fp32 copy for the pick is made: a certified frame that moves
+// its member sums (every frame in the first pass, under 10 % after two) reads its row again, L2-warm, all loads ahead
+// of the first atomic; step 4 reads the row of its frame wave-uniformly, next to the fp64 rows of the two best centres.
+// That, and fetching the first unit's images after the tables are built instead of across their staging, takes the fp64
+// no-whitening build from 132 VGPRs to 122: 16 waves without scratch memory (filter_waves).  (Step 4 as a scan of all
 // centres in fp64, rows from global memory, cost 25-30 us per pass for 0.2 % of the frames, in place or queued for the
 // end of the workgroup's units alike: ~10 us of a wave per frame, and the slowest workgroup has 20 of them.  Scoring
 // the eight candidates in fp64 before step 4, one lane and one row at a time, halves the frames that reach step 4 and
@@ -70,12 +75,15 @@ typedef _Float16 v8h __attribute__((ext_vector_type(8)));
 typedef float v4f32 __attribute__((ext_vector_type(4)));
 
 // waves per workgroup (= per CU): one instruction per tile and one 16-byte B operand per frame group keep the assign
-// passes within the 128 VGPRs of 16 waves; the d <= 10 accumulate passes (ten fp64 coordinates for the member sums)
-// need a few more and run 12 waves (a kernel with ANY scratch memory ran 25 us longer per pass)
+// passes within the 128 VGPRs of 16 waves.  The d <= 10 accumulate passes drop the ten fp64 coordinates once the fp32
+// copy for the candidate pick is made and read the row again for the frames that move their member sums (kReloadZ in
+// the kernel): on fp64 frames without whitening (`plain`: the bench step) that fits 16 waves too, 122 VGPRs; on fp32
+// frames or with whitening the 16-wave build still spills 24-60 bytes per lane, so those run 12 waves (a kernel with
+// ANY scratch memory ran 25 us longer per pass)
 #ifdef MSM_KMF_WAVES
-__host__ __device__ constexpr int filter_waves(int, bool) { return MSM_KMF_WAVES; }
+__host__ __device__ constexpr int filter_waves(int, bool, bool) { return MSM_KMF_WAVES; }
 #else
-__host__ __device__ constexpr int filter_waves(int dp, bool heavy) { return dp == 10 && heavy ? 12 : 16; }
+__host__ __device__ constexpr int filter_waves(int dp, bool heavy, bool plain) { return dp == 10 && heavy && !plain ? 12 : 16; }
 #endif
 constexpr int kFilterMaxD = 10;
 constexpr int kFilterRowQ = 3;                                   // uint4 per frame image (48 bytes)
@@ -472,7 +480,7 @@ __device__ __forceinline__ void filter_close_iteration(const unsigned long long*
 
 // ---------------------------------------------------------------------------------------------------------
 template <typename T, int DP, int NF, bool ACCUM, bool WHITEN>
-__global__ __launch_bounds__(64 * filter_waves(DP, ACCUM)) void kmeans_filter_kernel(
+__global__ __launch_bounds__(64 * filter_waves(DP, ACCUM, sizeof(T) == 8 && !WHITEN)) void kmeans_filter_kernel(
     const T* __restrict__ x, int64_t n, int d, int64_t ld, int k, const double* __restrict__ mean,
     const double* __restrict__ stdv, const uint4* __restrict__ image, const double* __restrict__ centers,
     int32_t* __restrict__ labels,
@@ -480,8 +488,11 @@ __global__ __launch_bounds__(64 * filter_waves(DP, ACCUM)) void kmeans_filter_ke
     unsigned long long* __restrict__ counts, unsigned long long* __restrict__ n_scanned, double* upd_centers,
     unsigned int* __restrict__ ticket) {
     using S = FilterShape<DP>;
-    constexpr int kFilterWaves = filter_waves(DP, ACCUM);
+    constexpr int kFilterWaves = filter_waves(DP, ACCUM, sizeof(T) == 8 && !WHITEN);
     constexpr int kMT = 64 * kFilterWaves, RF = S::RF, RQ = kFilterRowQ;
+    // the d <= 10 accumulate passes keep only the fp32 copy of a frame's coordinates after the candidate pick; the few
+    // frames that move their member sums read their fp64 row once more (filter_waves)
+    constexpr bool kReloadZ = ACCUM && DP == 10;
     static_assert(NF == 4, "one frame group per lane quarter: a unit is 64 frames, one per lane in the candidate pick");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     if constexpr (ACCUM) {
@@ -532,7 +543,11 @@ __global__ __launch_bounds__(64 * filter_waves(DP, ACCUM)) void kmeans_filter_ke
 #pragma unroll
         for (int u = 0; u < NF; ++u) b[u] = __builtin_bit_cast(v8h, ub[voff + u * 16 * RQ]);
     };
-    if (unit < u_end) load_images(unit);   // the first unit's images travel while the tables are built
+    // the first unit's images travel while the tables are built; kReloadZ: after that, their 16 registers across the
+    // staging of two tiles were what put the 16-wave build into scratch memory
+    if constexpr (!kReloadZ) {
+        if (unit < u_end) load_images(unit);
+    }
 
     // ---- centre tables, built by every workgroup for itself: wave w stages tiles w, w + W, ... straight into the
     // LDS (a separate staging launch + 113 KB of copies per workgroup did the same for 4.7 us more per pass);
@@ -567,6 +582,9 @@ __global__ __launch_bounds__(64 * filter_waves(DP, ACCUM)) void kmeans_filter_ke
     const bool all_scan = __builtin_amdgcn_readfirstlane(any_bad) != 0;
     KSTAMP(0);
 
+    if constexpr (kReloadZ) {
+        if (unit < u_end) load_images(unit);
+    }
     unsigned long long my_scans = 0;
     // 16-byte loads of a frame's coordinates: fp64 rows of exactly DP features on 16-byte boundaries
     const bool vec_rows = sizeof(T) == 8 && d == DP && ((ld * sizeof(T)) & 15) == 0 && (((uintptr_t)x) & 15) == 0;
@@ -807,10 +825,19 @@ __global__ __launch_bounds__(64 * filter_waves(DP, ACCUM)) void kmeans_filter_ke
                 // delta mode (labels != NULL): the sums follow the frames that CHANGED centre since the last pass
                 // (integer sums: the same bits as a full re-accumulation); else every frame is added
                 if (!labels || old != lab) {
+                    // kReloadZ: the row this wave read for the pick a moment ago, once more (all its loads before the
+                    // first atomic); the registers of z[] were free from the fp32 conversion on
+                    double zm[DP];
+                    if constexpr (kReloadZ) {
+                        load_frame(f0, zm);
+                    } else {
+#pragma unroll
+                        for (int f = 0; f < DP; ++f) zm[f] = z[f];
+                    }
 #pragma unroll
                     for (int f = 0; f < DP; ++f) {
                         if (f < d) {
-                            const unsigned long long fx = (unsigned long long)to_fixed(z[f], scale);
+                            const unsigned long long fx = (unsigned long long)to_fixed(zm[f], scale);
                             atomicAdd(&lsum[(size_t)lab * d + f], fx);
                             if (old >= 0) atomicAdd(&lsum[(size_t)old * d + f], 0ull - fx);
                         }
@@ -891,6 +918,9 @@ __global__ __launch_bounds__(64 * filter_waves(DP, ACCUM)) void kmeans_filter_ke
                     rowb[f] = f < d ? cb[f] : 0.0;
                 }
             }
+            // kReloadZ: the frame's fp64 coordinates travel with those rows (wave-uniform, as in scan_frame)
+            double zz[DP];
+            if constexpr (kReloadZ) load_frame(t, zz);
             const float top = wave_max_f32(t1), sbw = wave_max_f32(sbl);
             const float band = top - 2.0f * __builtin_fmaf(kPickEps, sbw, kPickFloor);
             const unsigned long long in1 = __ballot(t1 >= band);
@@ -898,13 +928,14 @@ __global__ __launch_bounds__(64 * filter_waves(DP, ACCUM)) void kmeans_filter_ke
                 scan_frame(t);
                 continue;
             }
-            // the frame's fp64 coordinates and its previous label are in lane jf's registers
-            double zz[DP];
+            // the frame's previous label is in lane jf's registers, and so are its fp64 coordinates unless kReloadZ
+            if constexpr (!kReloadZ) {
 #pragma unroll
-            for (int f = 0; f < DP; ++f) {
-                const long long bits = __double_as_longlong(z[f]);
-                zz[f] = __longlong_as_double((long long)(((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(bits >> 32), jf) << 32) |
-                                                         (unsigned)__builtin_amdgcn_readlane((int)bits, jf)));
+                for (int f = 0; f < DP; ++f) {
+                    const long long bits = __double_as_longlong(z[f]);
+                    zz[f] = __longlong_as_double((long long)(((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(bits >> 32), jf) << 32) |
+                                                             (unsigned)__builtin_amdgcn_readlane((int)bits, jf)));
+                }
             }
             const int old_t = __builtin_amdgcn_readlane(old, jf);
             int sbi;
