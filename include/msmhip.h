@@ -807,6 +807,29 @@ msm_status msm_reactive_flux_batched(msm_ctx* ctx, const double* d_T, int64_t t_
 msm_status msm_silhouette(msm_ctx* ctx, const double* d_x, int64_t n, int d, int64_t ld,
                           const int64_t* h_offsets, int k, double* d_samples, double* d_score);
 
+/* ---- silhouette samples: any cluster count, any n < 2^31 --------------------------------------
+ * sklearn.metrics.silhouette_samples / silhouette_score (Euclidean).  d_x f64 [n, ld] in frame
+ * order, 1 <= d <= MSM_REP_MAX_D; d_labels int32 [n] on the device, dense ids 0 .. k-1 (an id
+ * may be unused), 2 <= k <= n - 1; violations, a label outside [0, k) included, return
+ * MSM_ERR_INVALID.  d_samples f64 [n] in frame order: s_i = (b_i - a_i) / max(a_i, b_i), 0 for
+ * the member of a singleton cluster and where max(a_i, b_i) = 0; unused ids take no part in
+ * b_i.  *d_score = mean s_i.
+ * The frames are grouped on the device (msm_group_by_label), every cluster is cut into segments
+ * of MSM_SIL_SEG_LEN members, workgroups of MSM_SIL_TILE_I query frames x a group of segments
+ * write one partial distance sum per (query, segment), and a fold adds a cluster's pieces in
+ * segment order.  Distances are direct differences under the root.  No launch holds more than
+ * max_products (i, j, feature) products (0: 2^36) unless one workgroup alone does; the cut
+ * moves work between launches and changes no sum, and there are no atomics: the same bytes for
+ * every cut and on every run.  d_work: msm_silhouette_workspace_bytes(n, d, k) bytes, at most
+ * 256 MiB of partial sums plus 8 (k + 1) + 4 n bytes of grouping, whatever n and k are.
+ * Reads the cluster sizes on the host: not capturable. */
+#define MSM_SIL_SEG_LEN 1024
+#define MSM_SIL_TILE_I 128
+size_t msm_silhouette_workspace_bytes(int64_t n, int d, int k);
+msm_status msm_silhouette_samples(msm_ctx* ctx, const double* d_x, int64_t n, int d, int64_t ld,
+                                  const int32_t* d_labels, int k, void* d_work, size_t work_bytes,
+                                  int64_t max_products, double* d_samples, double* d_score);
+
 /* ---- regular-grid microstates (cluster_mode = "grid") -----------------------------------------
  * Replaces _GridDiscretizer._compute_indices / transform (S/analysis/discretize.py:552-583).
  * msm_grid_cells: d_flat[t] = sum_f idx_f * bins^(F-1-f), idx_f = clip(np.digitize(x[t][f],

@@ -24,6 +24,8 @@ REP_MAX_D, REP_GROUP_CHUNK, REP_TILE_I, REP_TILE_J = 256, 1024, 128, 64
 REP_FLAG_NONFINITE, REP_FLAG_NEGATIVE, REP_FLAG_NONPOSITIVE_SUM = 1, 2, 4
 REP_SCORE_CENTROID, REP_SCORE_MEDOID = 0, 1
 REP_SELECT_SMALLEST, REP_SELECT_DIVERSE = 0, 1
+# silhouette samples (MSM_SIL_* in include/msmhip.h): members of a segment, query frames of a workgroup
+SIL_SEG_LEN, SIL_TILE_I = 1024, 128
 # trajectory bootstrap (MSM_COMBINE_MAX_SEG, MSM_FLUX_LDS_MAX_N in include/msmhip.h)
 COMBINE_MAX_SEG, FLUX_LDS_MAX_N = 32, 127
 
@@ -157,6 +159,8 @@ _PROTOTYPES: dict[str, tuple] = {
     "msm_reactive_flux_batched_scratch_bytes": (_sz, [_i32, _i32, _i32]),
     "msm_reactive_flux_batched": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "msm_silhouette": (_i32, [_vp, _vp, _i64, _i32, _i64, _vp, _i32, _vp, _vp]),
+    "msm_silhouette_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "msm_silhouette_samples": (_i32, [_vp, _vp, _i64, _i32, _i64, _vp, _i32, _vp, _sz, _i64, _vp, _vp]),
     "msm_grid_cells": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _i32, _vp]),
     "msm_first_occurrence": (_i32, [_vp, _vp, _i64, _i32, _vp]),
     "msm_relabel": (_i32, [_vp, _vp, _i64, _vp, _i32, _vp]),

@@ -868,6 +868,24 @@ class Engine:
               self.handle)
         return float(score.to_host()[0]), samples
 
+    def silhouette_samples(self, x: DeviceArray, labels: DeviceArray, k: int, *,
+                           max_products: int | None = None) -> tuple[float, DeviceArray]:
+        """(mean silhouette coefficient, samples f64 [n] in frame order) of x f64 [n, d] under labels int32 [n] with ids
+        0 .. k-1 (unused ids allowed), for any 2 <= k <= n - 1.  No launch holds more than `max_products` (i, j,
+        feature) products (None: 2^36); the cut changes no bit of the result."""
+        if x.dtype != np.float64 or labels.dtype != np.int32:
+            raise TypeError("silhouette_samples takes float64 points and int32 labels")
+        if len(x.shape) != 2 or labels.size != x.shape[0]:
+            raise ValueError(f"silhouette_samples: points {x.shape} and {labels.size} labels do not match")
+        n, d = x.shape
+        work = self.empty((max(int(lib.msm_silhouette_workspace_bytes(n, d, int(k))), 1),), np.uint8)
+        samples = self.empty((n,), np.float64)
+        score = self.empty((1,), np.float64)
+        check(lib.msm_silhouette_samples(self.handle, x.ptr, n, d, d, labels.ptr, int(k), work.ptr, work.nbytes,
+                                         0 if max_products is None else int(max_products), samples.ptr, score.ptr),
+              self.handle)
+        return float(score.to_host()[0]), samples   # synchronises: the workspace is free on return
+
     # -- representative frames of a state -----------------------------------------------------------
     def group_by_label(self, labels: DeviceArray, k: int) -> tuple[DeviceArray, DeviceArray]:
         """(offsets int64 [k + 1], members int32 [n]): members[offsets[s]:offsets[s + 1]] are the frames with label s,

@@ -15,7 +15,7 @@ from ..pipeline import MSMPipeline
 
 logger = logging.getLogger("pmarlo")
 
-__all__ = ["ClusteringResult", "cluster_microstates", "silhouette_score"]
+__all__ = ["ClusteringResult", "cluster_microstates", "silhouette_samples", "silhouette_score"]
 
 # keyword arguments of the reference (clustering.py:236-262): what deeptime's estimators take
 _COMMON_KWARGS = frozenset({"max_iter", "metric", "tolerance", "init_strategy", "n_jobs", "initial_centers"})
@@ -57,23 +57,38 @@ def _fit_once(pipe, yd, k, seed, max_iter, tol, init, init_strategy="kmeans++", 
     return labels, centers, inertia
 
 
-def silhouette_score(X: np.ndarray, labels: np.ndarray) -> float:
-    """sklearn.metrics.silhouette_score (Euclidean) on the GPU: O(n^2 d) pair distances."""
+def _silhouette(X: np.ndarray, labels: np.ndarray) -> tuple[float, np.ndarray]:
     X = np.ascontiguousarray(X, dtype=np.float64)
     labels = np.asarray(labels)
+    if X.ndim != 2 or labels.shape != (X.shape[0],):
+        raise ValueError(f"X must be [n, d] and labels [n], got {X.shape} and {labels.shape}")
     uniq, dense = np.unique(labels, return_inverse=True)
     if not 2 <= uniq.size <= X.shape[0] - 1:
         raise ValueError(f"Number of labels is {uniq.size}. Valid values are 2 to n_samples - 1 (inclusive)")
-    if uniq.size > 32:
-        raise NotImplementedError("silhouette_score on the device supports at most 32 clusters")
-    order = np.argsort(dense, kind="stable")
-    offsets = np.concatenate([[0], np.cumsum(np.bincount(dense, minlength=uniq.size))])
     eng = get_engine()
-    score, _ = eng.silhouette(eng.to_device(X[order]), offsets)
-    return score
+    score, samples = eng.silhouette_samples(eng.to_device(X), eng.to_device(dense.astype(np.int32)), int(uniq.size))
+    return score, samples.to_host()
 
 
-_MAX_SILHOUETTE_POINTS = 200_000
+def silhouette_samples(X: np.ndarray, labels: np.ndarray) -> np.ndarray:
+    """sklearn.metrics.silhouette_samples (Euclidean) on the GPU for any integer labels and any number of clusters:
+    s_i = (b_i - a_i) / max(a_i, b_i) per sample, in the order of X; 0 for the member of a singleton cluster."""
+    return _silhouette(X, labels)[1]
+
+
+def silhouette_score(X: np.ndarray, labels: np.ndarray, *, sample_size: int | None = None,
+                     random_state: int | None = None) -> float:
+    """sklearn.metrics.silhouette_score (Euclidean) on the GPU: O(n^2 d) pair distances, any number of clusters.
+    `sample_size` scores a random subset drawn without replacement by np.random.default_rng(random_state)."""
+    if sample_size is not None:
+        X, labels = np.asarray(X), np.asarray(labels)
+        idx = np.random.default_rng(random_state).choice(X.shape[0], size=int(sample_size), replace=False)
+        X, labels = X[idx], labels[idx]
+    return _silhouette(X, labels)[0]
+
+
+# above this many points an unsampled n_states="auto" scan logs what it is about to compute
+_WARN_SILHOUETTE_POINTS = 2_000_000
 
 
 def _auto_select_n_states(Y, random_state, *, sample_size, override_n_states, kwargs) -> tuple[int, str]:
@@ -92,12 +107,14 @@ def _auto_select_n_states(Y, random_state, *, sample_size, override_n_states, kw
         idx = np.random.default_rng(random_state).choice(Y.shape[0], size=eff, replace=False)
         Ys = Y[idx]
         note = f" sample={eff}"
-    if Ys.shape[0] > _MAX_SILHOUETTE_POINTS:
-        raise ValueError(f"silhouette scoring is O(n^2): pass silhouette_sample_size (got {Ys.shape[0]} points)")
+    if sample_size is None and Ys.shape[0] > _WARN_SILHOUETTE_POINTS:
+        logger.warning("n_states='auto' scores every candidate on all %d points: %.3g pair distances per candidate; "
+                       "pass silhouette_sample_size to bound the time", Ys.shape[0], float(Ys.shape[0]) ** 2)
     eng = get_engine()
     pipe = MSMPipeline(eng)
+    # the points go up once: the fits read them as they are, the scoring reads float64
     yd = eng.to_device(np.ascontiguousarray(Ys))
-    Ys64 = np.ascontiguousarray(Ys, dtype=np.float64)
+    y64 = yd if yd.dtype == np.float64 else eng.to_device(np.ascontiguousarray(Ys, dtype=np.float64))
     seed = 0 if random_state is None else int(random_state)
     scores = []
     for k in range(4, 21):
@@ -112,8 +129,9 @@ def _auto_select_n_states(Y, random_state, *, sample_size, override_n_states, kw
                                            _init_strategy(kwargs, int(Ys.size)))
             if best is None or inertia < best[1]:
                 best = (labels, inertia)
-        lab = best[0].to_host()
-        scores.append((k, silhouette_score(Ys64, lab) if np.unique(lab).size > 1 else -1.0))
+        lab = best[0]      # stays on the device; ids without members take no part in the score
+        occupied = int(np.count_nonzero(eng.state_counts(lab, k).to_host()))
+        scores.append((k, eng.silhouette_samples(y64, lab, k)[0] if occupied > 1 else -1.0))
     if not scores:
         raise ValueError("too few samples for the n_states='auto' scan (needs more than 4)")
     chosen, best = max(scores, key=lambda t: t[1])
