@@ -1508,6 +1508,17 @@ __global__ __launch_bounds__(kEigThreads) void onesided_eig_kernel(const double*
 
 size_t jacobi_lds_bytes(int n, int ld) { return (size_t)(n <= kTriMax ? 3 : 2) * n * ld * sizeof(double); }
 
+// A workgroup has 160 KiB of LDS on gfx950, and the kernels' own __shared__ structs come out of it: a dynamic request
+// that does not leave room for them makes hipFuncSetAttribute fail.  Every kernel that can reach tridiag_eigh carries
+// both structs; tica_solve_kernel<2> and <0> never touch the TriShared one.  tests/_eig_ref.py restates these sizes.
+constexpr size_t kLdsPerWorkgroup = 160 * 1024;
+constexpr size_t kStaticLdsJacobi = sizeof(JacobiShared);
+constexpr size_t kStaticLdsTri = sizeof(JacobiShared) + sizeof(TriShared);
+static_assert(sizeof(JacobiShared) == 5808 && sizeof(TriShared) == 21808, "update the sizes restated in tests/_eig_ref.py");
+constexpr size_t lds_cap(size_t budget, size_t static_bytes) {
+    return budget < kLdsPerWorkgroup - static_bytes ? budget : kLdsPerWorkgroup - static_bytes;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1529,8 +1540,8 @@ msm_status msm_tica_solve(msm_ctx* ctx, const double* d_moments, const double* d
     wk.ev = base + 4 * mat; wk.mean = wk.ev + F; wk.isc = wk.mean + F; wk.order = (int*)(wk.isc + F);
     const size_t lds_budget = 150 * 1024;
     int lds_mats = 0;
-    if (4 * mat * sizeof(double) <= lds_budget) lds_mats = 4;
-    else if (2 * mat * sizeof(double) <= lds_budget) lds_mats = 2;
+    if (4 * mat * sizeof(double) <= lds_cap(lds_budget, kStaticLdsTri)) lds_mats = 4;
+    else if (2 * mat * sizeof(double) <= lds_cap(lds_budget, kStaticLdsJacobi)) lds_mats = 2;
     const size_t lds = (size_t)lds_mats * mat * sizeof(double);
     auto kern = lds_mats == 4 ? tica_solve_kernel<4> : (lds_mats == 2 ? tica_solve_kernel<2> : tica_solve_kernel<0>);
     if (lds > 48 * 1024)
@@ -1549,7 +1560,7 @@ msm_status msm_onesided_tica_eigenvalues(msm_ctx* ctx, const double* d_moments, 
     const int ld = F <= kTriMax ? kTriLd : (F | 1);
     const size_t mat = (size_t)F * ld;
     const size_t lds = 4 * mat * sizeof(double);
-    const bool use_lds = lds <= 140 * 1024;
+    const bool use_lds = lds <= lds_cap(140 * 1024, kStaticLdsTri);
     msm_status rs = msm_reserve_scratch(ctx, ((use_lds ? 0 : 4 * mat) + (size_t)F * F + F) * sizeof(double) +
                                                  (size_t)F * sizeof(int) + 64);
     if (rs != MSM_OK) return rs;
@@ -1578,7 +1589,7 @@ msm_status msm_eigh(msm_ctx* ctx, const double* d_a, int n, double* d_w, double*
     double* gV = gA + mat;
     int* order = (int*)(gV + mat);
     const size_t lds = jacobi_lds_bytes(n, ld);
-    const int use_lds = lds <= 140 * 1024;
+    const int use_lds = lds <= lds_cap(140 * 1024, kStaticLdsTri);
     auto kern = use_lds ? eigh_kernel<true> : eigh_kernel<false>;
     if (use_lds && lds > 48 * 1024)
         MSM_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
