@@ -12,22 +12,44 @@
 #include "common.h"
 #include "wave.h"
 
-// Diagnostic build only (tools/probe/jacobi_probe.hip): per-phase cycle stamps.
+// Diagnostic builds only (tools/probe/jacobi_probe.hip, tri_probe.hip): per-phase cycle stamps.  STAMP_ADD(slot, last)
+// books the shader cycles since `last` into `slot`.  JSTAMP: every thread, into registers, flushed by thread 0 of
+// jacobi_eigh.  TSTAMP (tridiag_eigh), KSTAMP (tica_solve_kernel), LSTAMP (inside the register phases; only with
+// MSM_TRI_STAMPS_FINE): thread 0, straight into g_tri_stamps.
+__device__ __forceinline__ unsigned long long stamp_clock() {
+    unsigned long long t;
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
+    return t;
+}
+#define STAMP_ADD(slot, last) do { const unsigned long long t__ = stamp_clock(); slot += t__ - last; last = t__; } while (0)
 #ifdef MSM_JACOBI_STAMPS
 __device__ unsigned long long g_jacobi_stamps[8];
-#define JSTAMP(i)                                                                          \
-    do {                                                                                   \
-        unsigned long long t__;                                                            \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t__)::"memory");       \
-        acc__[i] += t__ - last__;                                                          \
-        last__ = t__;                                                                      \
-    } while (0)
-#define JSTAMP_INIT unsigned long long acc__[8] = {0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long last__; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(last__)::"memory");
+#define JSTAMP(i) STAMP_ADD(acc__[i], last__)
+#define JSTAMP_INIT unsigned long long acc__[8] = {0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long last__ = stamp_clock();
 #define JSTAMP_FLUSH if (threadIdx.x == 0) { for (int i__ = 0; i__ < 8; ++i__) g_jacobi_stamps[i__] += acc__[i__]; }
 #else
 #define JSTAMP(i)
 #define JSTAMP_INIT
 #define JSTAMP_FLUSH
+#endif
+#ifdef MSM_TRI_STAMPS
+__device__ unsigned long long g_tri_stamps[24];
+#define TSTAMP(i) do { if (threadIdx.x == 0) STAMP_ADD(g_tri_stamps[i], tlast__); } while (0)
+#define TSTAMP_INIT unsigned long long tlast__ = 0; if (threadIdx.x == 0) tlast__ = stamp_clock();
+#define KSTAMP(i) do { if (threadIdx.x == 0) STAMP_ADD(g_tri_stamps[i], klast__); } while (0)
+#define KSTAMP_INIT unsigned long long klast__ = 0; if (threadIdx.x == 0) klast__ = stamp_clock();
+#else
+#define TSTAMP(i)
+#define TSTAMP_INIT
+#define KSTAMP(i)
+#define KSTAMP_INIT
+#endif
+#ifdef MSM_TRI_STAMPS_FINE
+#define LSTAMP(i) TSTAMP(i)
+#define LSTAMP_INIT TSTAMP_INIT
+#else
+#define LSTAMP(i)
+#define LSTAMP_INIT
 #endif
 
 namespace {
@@ -38,9 +60,9 @@ constexpr int kMaxPairs = 128;  // n <= 256
 struct JacobiShared {
     double2 cs[kMaxPairs];  // (c, s) of pivot i: one 16-byte LDS read
     int p[kMaxPairs], q[kMaxPairs];
-    int colw[kMaxPairs];  // p | q << 16            (even-n fast path: one read instead of the
-    int roww[kMaxPairs];  // p * ld | (q * ld) << 16   tournament arithmetic + row multiplies)
-    // second buffer of the pipelined path (n <= 64): rotations of round r+1 are formed by wave 0
+    int reserved[2 * kMaxPairs];  // unused: keeps sizeof (the LDS boundaries in tests/_eig_ref.py); goes only in a change that may move them
+    // tables of the pipelined path (n <= 64), two buffers: colw2 = p | q << 16, roww2 = p * ld | (q * ld) << 16 (one
+    // read instead of the tournament arithmetic and the row multiplies); rotations of round r+1 are formed by wave 0
     // while the other waves still apply round r
     double2 cs2[2][32];
     int colw2[2][32], roww2[2][32];
@@ -100,6 +122,43 @@ __device__ __forceinline__ void pivot_pair(int round, int i, int npad, int& p, i
     q = round - i; if (q < 0) q += npad - 1;
 }
 
+// (xp, xq) <- (c xp - s xq, s xp + c xq): one row of V J, or one column / row of a one-sided block update
+__device__ __forceinline__ void rotate_pair(double c, double s, double& xp, double& xq) {
+    const double yp = fma(-s, xq, c * xp), yq = fma(s, xp, c * xq);
+    xp = yp; xq = yq;
+}
+
+// One 2x2 block of A <- J'AJ: rows p, q of pivot a (ca, sa) crossed with columns p, q of pivot b (cb, sb).  Values
+// in, values out: the fast paths issue all their loads (clamped addresses) before and only predicate the stores.
+__device__ __forceinline__ void rotate_block(double app, double apq, double aqp, double aqq, double ca, double sa,
+                                             double cb, double sb, bool diagonal, double& npp, double& npq,
+                                             double& nqp, double& nqq) {
+    const double rpp = fma(-sa, aqp, ca * app), rpq = fma(-sa, aqq, ca * apq);
+    const double rqp = fma(sa, app, ca * aqp), rqq = fma(sa, apq, ca * aqq);
+    npp = fma(-sb, rpq, cb * rpp); npq = fma(sb, rpp, cb * rpq);
+    nqp = fma(-sb, rqq, cb * rqp); nqq = fma(sb, rqp, cb * rqq);
+    if (diagonal) { npq = 0.0; nqp = 0.0; }  // the pivot is annihilated exactly
+}
+
+__device__ __forceinline__ void set_identity(double* V, int n, int ld) {   // no barrier
+    for (int i = threadIdx.x; i < n * n; i += blockDim.x) V[(i / n) * ld + (i % n)] = (i / n == i % n) ? 1.0 : 0.0;
+}
+
+// Convergence test of a sweep (uniform): ||off||_F <= n*eps*||A||_F.  Rounding of the rotations themselves
+// re-pollutes the zeroed entries at that level, and the eigenvalue error left is second order in it.
+__device__ __forceinline__ bool jacobi_converged(const double* A, int n, int ld, JacobiShared* sh) {
+    double off = 0.0, dia = 0.0;
+    for (int i = threadIdx.x; i < n * n; i += blockDim.x) {
+        const int r = i / n, c = i - r * n;
+        const double v = A[r * ld + c];
+        if (r == c) dia = fma(v, v, dia); else off = fma(v, v, off);
+    }
+    off = block_sum_bcast(off, sh->red, sh->bc);
+    dia = block_sum_bcast(dia, sh->red, sh->bc);
+    const double tol = (double)n * 2.220446049250313e-16;
+    return off <= tol * tol * (dia + off) || off == 0.0;
+}
+
 // A (n x n, row stride ld, symmetric) -> diagonal; V -> eigenvectors in columns.
 // Returns the number of sweeps used (uniform across the block).
 //
@@ -121,7 +180,7 @@ __device__ __forceinline__ int jacobi_eigh(double* A, double* V, int n, int ld, 
         if ((n & 1) == 0 && mh >= 4 && mh <= 32 && mh * mh <= nt && mh * n <= 2 * nt && n * ld < 65536 && nt >= 64)
             return jacobi_eigh_pipelined(A, V, n, ld, sh, max_sweeps);
     }
-    for (int i = tid; i < n * n; i += nt) V[(i / n) * ld + (i % n)] = (i / n == i % n) ? 1.0 : 0.0;
+    set_identity(V, n, ld);
     __syncthreads();
     if (n < 2) return 0;
     const int npad = n + (n & 1);
@@ -130,25 +189,11 @@ __device__ __forceinline__ int jacobi_eigh(double* A, double* V, int n, int ld, 
     JSTAMP_INIT
     for (; sweep < max_sweeps; ++sweep) {
         JSTAMP(0);
-        double off = 0.0, dia = 0.0;
-        for (int i = tid; i < n * n; i += nt) {
-            const int r = i / n, c = i - r * n;
-            const double v = A[r * ld + c];
-            if (r == c) dia = fma(v, v, dia); else off = fma(v, v, off);
-        }
-        off = block_sum_bcast(off, sh->red, sh->bc);
-        dia = block_sum_bcast(dia, sh->red, sh->bc);
-        // converged when ||off||_F <= n*eps*||A||_F: rounding of the rotations themselves
-        // re-pollutes the zeroed entries at that level, and the eigenvalue error left
-        // is second order in it.
-        const double tol = (double)n * 2.220446049250313e-16;
-        if (off <= tol * tol * (dia + off) || off == 0.0) break;
+        if (jacobi_converged(A, n, ld, sh)) break;
         JSTAMP(1);
-        // fast path: one 2x2 block and at most two V items per thread, indices fixed for the sweep
+        // fast path: one 2x2 block and at most two V items per thread, indices fixed for the sweep.  With 1024 threads:
+        // the odd orders up to 63 and n = 2, 4, 6 (the other even orders up to 64 are pipelined)
         const bool fast = (m * m <= nt) && (m * n <= 2 * nt);
-        // n even: nobody sits out, so the fast path needs no padding logic at all (n = 64 with 1024
-        // threads: every thread owns exactly one 2x2 block and two V items)
-        const bool fast_even = fast && (n & 1) == 0 && n * ld < 65536;
         const int my_ia = tid / m, my_ib = tid - my_ia * m;
         const bool has_blk = tid < m * m;
         const int v_ib0 = tid / n, v_r0 = tid - v_ib0 * n;
@@ -166,39 +211,11 @@ __device__ __forceinline__ int jacobi_eigh(double* A, double* V, int n, int ld, 
                 double c = 1.0, s = 0.0;
                 if (q < n) jacobi_rotation(A[p * ld + p], A[q * ld + q], A[p * ld + q], c, s);
                 sh->cs[i] = make_double2(c, s); sh->p[i] = p; sh->q[i] = q;
-                sh->colw[i] = p | (q << 16);
-                sh->roww[i] = (p * ld) | ((q * ld) << 16);
             }
             JSTAMP(2);
             __syncthreads();
             JSTAMP(3);
-            if (fast_even) {
-                // ~70 instructions per thread (the phase is bound by instruction issue: 16 waves
-                // on 4 SIMDs).  All loads first, clamped indices for idle threads, stores guarded.
-                const int wr = sh->roww[my_ia_c], wc = sh->colw[my_ib_c];
-                const int w0 = sh->colw[v_ib0_c], w1 = sh->colw[v_ib1_c];
-                const double2 ra = sh->cs[my_ia_c], rb = sh->cs[my_ib_c], r0 = sh->cs[v_ib0_c], r1 = sh->cs[v_ib1_c];
-                double* Ap = A + (wr & 0xffff);
-                double* Aq = A + (wr >> 16);
-                const int pb = wc & 0xffff, qb = wc >> 16;
-                double* V0 = V + v_r0 * ld;
-                double* V1 = V + v_r1_c * ld;
-                const int vp0 = w0 & 0xffff, vq0 = w0 >> 16, vp1 = w1 & 0xffff, vq1 = w1 >> 16;
-                const double app = Ap[pb], apq = Ap[qb], aqp = Aq[pb], aqq = Aq[qb];
-                const double x0p = V0[vp0], x0q = V0[vq0], x1p = V1[vp1], x1q = V1[vq1];
-                const double rpp = fma(-ra.y, aqp, ra.x * app), rpq = fma(-ra.y, aqq, ra.x * apq);
-                const double rqp = fma(ra.y, app, ra.x * aqp), rqq = fma(ra.y, apq, ra.x * aqq);
-                const double npp = fma(-rb.y, rpq, rb.x * rpp), nqq = fma(rb.y, rqp, rb.x * rqq);
-                double npq = fma(rb.y, rpp, rb.x * rpq), nqp = fma(-rb.y, rqq, rb.x * rqp);
-                if (my_ia_c == my_ib_c) { npq = 0.0; nqp = 0.0; }  // the pivot is annihilated exactly
-                const double y0p = fma(-r0.y, x0q, r0.x * x0p), y0q = fma(r0.y, x0p, r0.x * x0q);
-                const double y1p = fma(-r1.y, x1q, r1.x * x1p), y1q = fma(r1.y, x1p, r1.x * x1q);
-                if (has_blk) { Ap[pb] = npp; Ap[qb] = npq; Aq[pb] = nqp; Aq[qb] = nqq; }
-                if (has_v0) { V0[vp0] = y0p; V0[vq0] = y0q; }
-                if (has_v1) { V1[vp1] = y1p; V1[vq1] = y1q; }
-                JSTAMP(4);
-                JSTAMP(5);
-            } else if (fast) {
+            if (fast) {
                 // Branch-free: every load uses an in-range (clamped) address and is issued
                 // before the first use; only the stores are predicated.  (Predicated LOADS
                 // made the compiler fence each one with s_waitcnt: ~20 exposed LDS latencies.)
@@ -213,24 +230,21 @@ __device__ __forceinline__ int jacobi_eigh(double* A, double* V, int n, int ld, 
                 const double2 ra = sh->cs[my_ia_c], rb = sh->cs[my_ib_c], r0 = sh->cs[v_ib0_c], r1 = sh->cs[v_ib1_c];
                 const double app = A[pa * ld + pb], apq = A[pa * ld + qb_c];
                 const double aqp = A[qa_c * ld + pb], aqq = A[qa_c * ld + qb_c];
-                const double x0p = V[v_r0 * ld + vp0], x0q = V[v_r0 * ld + vq0_c];
-                const double x1p = V[v_r1_c * ld + vp1], x1q = V[v_r1_c * ld + vq1_c];
+                double x0p = V[v_r0 * ld + vp0], x0q = V[v_r0 * ld + vq0_c];
+                double x1p = V[v_r1_c * ld + vp1], x1q = V[v_r1_c * ld + vq1_c];
                 // the index sitting out (odd n) is not rotated
                 const double ca = row_real ? ra.x : 1.0, sa = row_real ? ra.y : 0.0;
                 const double cb = col_real ? rb.x : 1.0, sb = col_real ? rb.y : 0.0;
-                const double rpp = fma(-sa, aqp, ca * app), rpq = fma(-sa, aqq, ca * apq);
-                const double rqp = fma(sa, app, ca * aqp), rqq = fma(sa, apq, ca * aqq);
-                double npp = fma(-sb, rpq, cb * rpp), npq = fma(sb, rpp, cb * rpq);
-                double nqp = fma(-sb, rqq, cb * rqp), nqq = fma(sb, rqp, cb * rqq);
-                if (my_ia_c == my_ib_c) { npq = 0.0; nqp = 0.0; }  // the pivot is annihilated exactly
-                const double y0p = fma(-r0.y, x0q, r0.x * x0p), y0q = fma(r0.y, x0p, r0.x * x0q);
-                const double y1p = fma(-r1.y, x1q, r1.x * x1p), y1q = fma(r1.y, x1p, r1.x * x1q);
+                double npp, npq, nqp, nqq;
+                rotate_block(app, apq, aqp, aqq, ca, sa, cb, sb, my_ia_c == my_ib_c, npp, npq, nqp, nqq);
+                rotate_pair(r0.x, r0.y, x0p, x0q);
+                rotate_pair(r1.x, r1.y, x1p, x1q);
                 if (has_blk) A[pa * ld + pb] = npp;
                 if (has_blk && col_real) A[pa * ld + qb] = npq;
                 if (has_blk && row_real) A[qa * ld + pb] = nqp;
                 if (has_blk && row_real && col_real) A[qa * ld + qb] = nqq;
-                if (v0) { V[v_r0 * ld + vp0] = y0p; V[v_r0 * ld + vq0] = y0q; }
-                if (v1) { V[v_r1_c * ld + vp1] = y1p; V[v_r1_c * ld + vq1] = y1q; }
+                if (v0) { V[v_r0 * ld + vp0] = x0p; V[v_r0 * ld + vq0] = x0q; }
+                if (v1) { V[v_r1_c * ld + vp1] = x1p; V[v_r1_c * ld + vq1] = x1q; }
                 JSTAMP(4);
                 JSTAMP(5);
             } else {
@@ -241,24 +255,21 @@ __device__ __forceinline__ int jacobi_eigh(double* A, double* V, int n, int ld, 
                     if (!row_real && !col_real) continue;
                     const double ca = sh->cs[ia].x, sa = sh->cs[ia].y, cb = sh->cs[ib].x, sb = sh->cs[ib].y;
                     if (!col_real) {          // unpaired column pb: rows of pivot a only
-                        const double ap = A[pa * ld + pb], aq = A[qa * ld + pb];
-                        A[pa * ld + pb] = fma(-sa, aq, ca * ap);
-                        A[qa * ld + pb] = fma(sa, ap, ca * aq);
+                        double ap = A[pa * ld + pb], aq = A[qa * ld + pb];
+                        rotate_pair(ca, sa, ap, aq);
+                        A[pa * ld + pb] = ap; A[qa * ld + pb] = aq;
                         continue;
                     }
                     if (!row_real) {          // unpaired row pa: columns of pivot b only
-                        const double ap = A[pa * ld + pb], aq = A[pa * ld + qb];
-                        A[pa * ld + pb] = fma(-sb, aq, cb * ap);
-                        A[pa * ld + qb] = fma(sb, ap, cb * aq);
+                        double ap = A[pa * ld + pb], aq = A[pa * ld + qb];
+                        rotate_pair(cb, sb, ap, aq);
+                        A[pa * ld + pb] = ap; A[pa * ld + qb] = aq;
                         continue;
                     }
                     const double app = A[pa * ld + pb], apq = A[pa * ld + qb];
                     const double aqp = A[qa * ld + pb], aqq = A[qa * ld + qb];
-                    const double rpp = fma(-sa, aqp, ca * app), rpq = fma(-sa, aqq, ca * apq);
-                    const double rqp = fma(sa, app, ca * aqp), rqq = fma(sa, apq, ca * aqq);
-                    double npp = fma(-sb, rpq, cb * rpp), npq = fma(sb, rpp, cb * rpq);
-                    double nqp = fma(-sb, rqq, cb * rqp), nqq = fma(sb, rqp, cb * rqq);
-                    if (ia == ib) { npq = 0.0; nqp = 0.0; }  // the pivot is annihilated exactly
+                    double npp, npq, nqp, nqq;
+                    rotate_block(app, apq, aqp, aqq, ca, sa, cb, sb, ia == ib, npp, npq, nqp, nqq);
                     A[pa * ld + pb] = npp; A[pa * ld + qb] = npq;
                     A[qa * ld + pb] = nqp; A[qa * ld + qb] = nqq;
                 }
@@ -268,9 +279,9 @@ __device__ __forceinline__ int jacobi_eigh(double* A, double* V, int n, int ld, 
                     const int pb = sh->p[ib], qb = sh->q[ib];
                     if (qb >= n) continue;
                     const double cb = sh->cs[ib].x, sb = sh->cs[ib].y;
-                    const double vp = V[r * ld + pb], vq = V[r * ld + qb];
-                    V[r * ld + pb] = fma(-sb, vq, cb * vp);
-                    V[r * ld + qb] = fma(sb, vp, cb * vq);
+                    double vp = V[r * ld + pb], vq = V[r * ld + qb];
+                    rotate_pair(cb, sb, vp, vq);
+                    V[r * ld + pb] = vp; V[r * ld + qb] = vq;
                 }
                 JSTAMP(5);
             }
@@ -295,7 +306,7 @@ __device__ __forceinline__ int jacobi_eigh(double* A, double* V, int n, int ld, 
 __device__ __forceinline__ int jacobi_eigh_pipelined(double* A, double* V, int n, int ld, JacobiShared* sh,
                                                      int max_sweeps) {
     const int tid = threadIdx.x, nt = blockDim.x;
-    for (int i = tid; i < n * n; i += nt) V[(i / n) * ld + (i % n)] = (i / n == i % n) ? 1.0 : 0.0;
+    set_identity(V, n, ld);
     const int m = n / 2, ring = n - 1;
     auto form_rotations = [&](int round, int buf) {  // lanes 0..m-1 of wave 0
         int p, q;
@@ -313,11 +324,8 @@ __device__ __forceinline__ int jacobi_eigh_pipelined(double* A, double* V, int n
         double* Aq = A + (wr >> 16);
         const int pb = wc & 0xffff, qb = wc >> 16;
         const double app = Ap[pb], apq = Ap[qb], aqp = Aq[pb], aqq = Aq[qb];
-        const double rpp = fma(-ra.y, aqp, ra.x * app), rpq = fma(-ra.y, aqq, ra.x * apq);
-        const double rqp = fma(ra.y, app, ra.x * aqp), rqq = fma(ra.y, apq, ra.x * aqq);
-        const double npp = fma(-rb.y, rpq, rb.x * rpp), nqq = fma(rb.y, rqp, rb.x * rqq);
-        double npq = fma(rb.y, rpp, rb.x * rpq), nqp = fma(-rb.y, rqq, rb.x * rqp);
-        if (ia == ib) { npq = 0.0; nqp = 0.0; }  // the pivot is annihilated exactly
+        double npp, npq, nqp, nqq;
+        rotate_block(app, apq, aqp, aqq, ra.x, ra.y, rb.x, rb.y, ia == ib, npp, npq, nqp, nqq);
         if (live) { Ap[pb] = npp; Ap[qb] = npq; Aq[pb] = nqp; Aq[qb] = nqq; }
     };
     // static roles
@@ -347,16 +355,7 @@ __device__ __forceinline__ int jacobi_eigh_pipelined(double* A, double* V, int n
     __syncthreads();
     int sweep = 0;
     for (; sweep < max_sweeps; ++sweep) {
-        double off = 0.0, dia = 0.0;
-        for (int i = tid; i < n * n; i += nt) {
-            const int r = i / n, c = i - r * n;
-            const double v = A[r * ld + c];
-            if (r == c) dia = fma(v, v, dia); else off = fma(v, v, off);
-        }
-        off = block_sum_bcast(off, sh->red, sh->bc);
-        dia = block_sum_bcast(dia, sh->red, sh->bc);
-        const double tol = (double)n * 2.220446049250313e-16;  // see jacobi_eigh
-        if (off <= tol * tol * (dia + off) || off == 0.0) break;
+        if (jacobi_converged(A, n, ld, sh)) break;
         for (int rr = 0; rr < ring; ++rr) {
             const int next_round = round + 1 == ring ? 0 : round + 1;
             if (tid < 64) {  // wave 0 (uniform branch)
@@ -370,11 +369,11 @@ __device__ __forceinline__ int jacobi_eigh_pipelined(double* A, double* V, int n
                 double* V0 = V + v_r0 * ld;
                 double* V1 = V + v_r1_c * ld;
                 const int vp0 = w0 & 0xffff, vq0 = w0 >> 16, vp1 = w1 & 0xffff, vq1 = w1 >> 16;
-                const double x0p = V0[vp0], x0q = V0[vq0], x1p = V1[vp1], x1q = V1[vq1];
-                const double y0p = fma(-r0.y, x0q, r0.x * x0p), y0q = fma(r0.y, x0p, r0.x * x0q);
-                const double y1p = fma(-r1.y, x1q, r1.x * x1p), y1q = fma(r1.y, x1p, r1.x * x1q);
-                if (has_v0) { V0[vp0] = y0p; V0[vq0] = y0q; }
-                if (has_v1) { V1[vp1] = y1p; V1[vq1] = y1q; }
+                double x0p = V0[vp0], x0q = V0[vq0], x1p = V1[vp1], x1q = V1[vq1];
+                rotate_pair(r0.x, r0.y, x0p, x0q);
+                rotate_pair(r1.x, r1.y, x1p, x1q);
+                if (has_v0) { V0[vp0] = x0p; V0[vq0] = x0q; }
+                if (has_v1) { V1[vp1] = x1p; V1[vq1] = x1q; }
             }
             __syncthreads();
             buf ^= 1;
@@ -384,17 +383,24 @@ __device__ __forceinline__ int jacobi_eigh_pipelined(double* A, double* V, int n
     return sweep;
 }
 
-// order[j] = index of the j-th largest |ev| (stable)
-__device__ void sort_desc_abs(const double* ev, int n, int* order) {
+// Rank by counting: order[r] = the index whose key(i) is the r-th largest (descending) or smallest, equal keys in
+// index order (stable).  No barrier: the caller synchronises before `order` is read.
+template <bool descending, typename Key>
+__device__ __forceinline__ void rank_order(int n, int* order, Key key) {
     for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const double a = fabs(ev[i]);
+        const double a = key(i);
         int rank = 0;
         for (int j = 0; j < n; ++j) {
-            const double b = fabs(ev[j]);
-            rank += (b > a) || (b == a && j < i);
+            const double b = key(j);
+            rank += (descending ? b > a : b < a) || (b == a && j < i);
         }
         order[rank] = i;
     }
+}
+
+// order[j] = index of the j-th largest |ev| (stable)
+__device__ void sort_desc_abs(const double* ev, int n, int* order) {
+    rank_order<true>(n, order, [&](int i) { return fabs(ev[i]); });
     __syncthreads();
 }
 
@@ -486,27 +492,6 @@ __device__ void lower_inverse(const double* G, double* X, int n, int ld) {
 // exactly repeated eigenvalues give repeated vectors: X'X is checked and the caller falls back to Jacobi on its
 // copy of A when the defect exceeds `orth_tol` (or a residual |T x - lambda x| is large).
 // ---------------------------------------------------------------------------------------------------
-#ifdef MSM_TRI_STAMPS
-__device__ unsigned long long g_tri_stamps[24];
-#define TSTAMP(i) do { if (threadIdx.x == 0) { unsigned long long t__; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t__)::"memory"); g_tri_stamps[i] += t__ - tlast__; tlast__ = t__; } } while (0)
-#define TSTAMP_INIT unsigned long long tlast__ = 0; if (threadIdx.x == 0) { asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tlast__)::"memory"); }
-#define KSTAMP(i) do { if (threadIdx.x == 0) { unsigned long long t__; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t__)::"memory"); g_tri_stamps[i] += t__ - klast__; klast__ = t__; } } while (0)
-#define KSTAMP_INIT unsigned long long klast__ = 0; if (threadIdx.x == 0) { asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(klast__)::"memory"); }
-#ifdef MSM_TRI_STAMPS_FINE
-#define LSTAMP(i) TSTAMP(i)
-#define LSTAMP_INIT TSTAMP_INIT
-#else
-#define LSTAMP(i)
-#define LSTAMP_INIT
-#endif
-#else
-#define LSTAMP(i)
-#define LSTAMP_INIT
-#define TSTAMP(i)
-#define TSTAMP_INIT
-#define KSTAMP(i)
-#define KSTAMP_INIT
-#endif
 constexpr int kTriMax = 64;
 constexpr int kTriLd = 65;   // row stride of every matrix handed to tridiag_eigh (a constant: row offsets become immediates)
 struct TriShared {
@@ -530,6 +515,31 @@ typedef double tri_v4f64 __attribute__((ext_vector_type(4)));
 // and trip), i < rows, j < cols, k < inner; opA = A or A', opB = B or B'.  bscale (optional) multiplies column j of
 // opB.  C must not alias A or B.  A 64^3 product costs what it costs on the VALU (the fp64 rates are equal) but
 // reads each operand from the LDS once per tile instead of once per multiply.
+//
+// mfma_tile_acc is one tile: lane (j, g) = (lane & 15, lane >> 4) supplies a(k) = opA(i0 + j, k) and b(k) =
+// opB(k, c0 + j) through loadA(k) / loadB(k), which read clamped (in-range) addresses; aok / bok say whether the
+// lane's row of opA / column of opB lies inside the matrix, and what lies outside is fed as zero.  acc[r] ends up
+// as entry (i0 + g + 4 r, c0 + j) of the tile.
+template <typename LoadA, typename LoadB>
+__device__ __forceinline__ tri_v4f64 mfma_tile_acc(int inner, int g, bool aok, bool bok, LoadA loadA, LoadB loadB) {
+    tri_v4f64 acc = {0.0, 0.0, 0.0, 0.0};
+    for (int k0 = 0; k0 < inner; k0 += 16) {   // four instructions per trip: their operand reads go out together
+        double a[4], b[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const bool kok = k0 + 4 * u + g < inner;
+            const int k = kok ? k0 + 4 * u + g : 0;
+            a[u] = loadA(k);
+            b[u] = loadB(k);
+            if (!(aok && kok)) a[u] = 0.0;
+            if (!(bok && kok)) b[u] = 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u], b[u], acc, 0, 0, 0);
+    }
+    return acc;
+}
+
 template <bool TA, bool TB>
 __device__ __forceinline__ void mfma_mm(double* C, const double* A, const double* B, int rows, int cols, int inner, int ld,
                         const double* bscale = nullptr) {
@@ -541,21 +551,9 @@ __device__ __forceinline__ void mfma_mm(double* C, const double* A, const double
         const bool aok = i0 + j < rows, bok = c0 + j < cols;
         const int ai = aok ? i0 + j : 0, bj = bok ? c0 + j : 0;
         const double bs = bscale ? bscale[bj] : 1.0;
-        tri_v4f64 acc = {0.0, 0.0, 0.0, 0.0};
-        for (int k0 = 0; k0 < inner; k0 += 16) {   // four instructions per trip: their operand reads go out together
-            double a[4], b[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const bool kok = k0 + 4 * u + g < inner;
-                const int k = kok ? k0 + 4 * u + g : 0;
-                a[u] = TA ? A[k * ld + ai] : A[ai * ld + k];
-                b[u] = (TB ? B[bj * ld + k] : B[k * ld + bj]) * bs;
-                if (!(aok && kok)) a[u] = 0.0;
-                if (!(bok && kok)) b[u] = 0.0;
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u], b[u], acc, 0, 0, 0);
-        }
+        const tri_v4f64 acc = mfma_tile_acc(
+            inner, g, aok, bok, [&](int k) { return TA ? A[k * ld + ai] : A[ai * ld + k]; },
+            [&](int k) { return (TB ? B[bj * ld + k] : B[k * ld + bj]) * bs; });
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int row = i0 + g + 4 * r, col = c0 + j;
@@ -1087,21 +1085,8 @@ __device__ __forceinline__ bool tridiag_eigh(double* A, double* Q, double* X, in
             const bool aok = a0 + jj < n, bok = b0 + jj < n;
             const int ai = aok ? a0 + jj : 0, bi = bok ? b0 + jj : 0;
             const double sa = ts->inv[ai], sb = ts->inv[bi];
-            tri_v4f64 acc = {0.0, 0.0, 0.0, 0.0};
-            for (int k0 = 0; k0 < n; k0 += 16) {
-                double a[4], b[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const bool kok = k0 + 4 * u + g < n;
-                    const int k = kok ? k0 + 4 * u + g : 0;
-                    a[u] = X[k * ld + ai] * sa;
-                    b[u] = X[k * ld + bi] * sb;
-                    if (!(aok && kok)) a[u] = 0.0;
-                    if (!(bok && kok)) b[u] = 0.0;
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u], b[u], acc, 0, 0, 0);
-            }
+            const tri_v4f64 acc = mfma_tile_acc(
+                n, g, aok, bok, [&](int k) { return X[k * ld + ai] * sa; }, [&](int k) { return X[k * ld + bi] * sb; });
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int row = a0 + g + 4 * r, col = b0 + jj;
@@ -1123,6 +1108,34 @@ __device__ __forceinline__ bool tridiag_eigh(double* A, double* Q, double* X, in
     __syncthreads();
     TSTAMP(7);
     return true;
+}
+
+// Eigenpairs of the symmetric n x n matrix in A (destroyed): tridiag_eigh when `try_tri` (A, V, X then sit in the LDS
+// with stride kTriLd; X is not touched otherwise), and on its refusal Jacobi on the copy saved in `backup` (n * n,
+// packed, global).  Eigenvalues to ev_out in solver order, vec = the matrix whose columns hold the eigenvectors
+// (A after tridiag_eigh, V after Jacobi).  Returns the Jacobi sweeps, 0 for the tridiagonal path (tell the two apart
+// by vec: Jacobi on a diagonal matrix takes 0 sweeps as well).  The caller synchronises before ev_out is read.
+// Force-inlined: A, V, X must stay known LDS or known global pointers (see tica_solve_kernel).
+__device__ __forceinline__ int eigh_with_fallback(double* A, double* V, double* X, int n, int ld, double* backup,
+                                                  bool try_tri, TriShared* ts, JacobiShared* sh, double orth_tol,
+                                                  double* ev_out, const double*& vec) {
+    const int tid = threadIdx.x, nt = blockDim.x;
+    if (try_tri) {
+        for (int e = tid; e < n * n; e += nt) backup[e] = A[(e / n) * ld + (e % n)];
+        __syncthreads();
+        if (tridiag_eigh(A, V, X, n, ld, ts, orth_tol)) {
+            for (int i = tid; i < n; i += nt) ev_out[i] = ts->lam[i];
+            vec = A;
+            return 0;
+        }
+        __syncthreads();
+        for (int e = tid; e < n * n; e += nt) A[(e / n) * ld + (e % n)] = backup[e];
+        __syncthreads();
+    }
+    const int sweeps = jacobi_eigh(A, V, n, ld, sh, 40);
+    for (int i = tid; i < n; i += nt) ev_out[i] = A[i * ld + i];
+    vec = V;
+    return sweeps;
 }
 
 struct TicaWork {  // global scratch: four n*ld matrices, then ev[n], mean[n], isc[n], order[n]
@@ -1279,25 +1292,8 @@ __global__ __launch_bounds__(kEigThreads) void tica_solve_kernel(
     __syncthreads();
     KSTAMP(10);
     // eigenpairs of the whitened C0t: tridiagonal solver (fallback: Jacobi on the saved copy)
-    const double* Vec = V;
-    bool fast = false;
-    if (kFused && rank <= kTriMax) {
-        for (int e = tid; e < rank * rank; e += nt) wk.A[e] = A[(e / rank) * ld + (e % rank)];
-        __syncthreads();
-        fast = tridiag_eigh(A, V, B1, rank, ld, &ts, 1e-11);
-        if (fast) {
-            for (int i = tid; i < rank; i += nt) wk.ev[i] = ts.lam[i];
-            Vec = A;
-        } else {
-            __syncthreads();
-            for (int e = tid; e < rank * rank; e += nt) A[(e / rank) * ld + (e % rank)] = wk.A[e];
-        }
-        __syncthreads();
-    }
-    if (!fast) {
-        jacobi_eigh(A, V, rank, ld, &sh, 40);
-        for (int i = tid; i < rank; i += nt) wk.ev[i] = A[i * ld + i];
-    }
+    const double* Vec;
+    eigh_with_fallback(A, V, B1, rank, ld, wk.A, kFused && rank <= kTriMax, &ts, &sh, 1e-11, wk.ev, Vec);
     __syncthreads();
     KSTAMP(11);
     if (kFused && n <= kTriMax) {
@@ -1309,15 +1305,7 @@ __global__ __launch_bounds__(kEigThreads) void tica_solve_kernel(
         int* ord = sh.p;            // ord[j] = solver column of the j-th largest |ev|
         if (tid < rank) evl[tid] = wk.ev[tid];
         __syncthreads();
-        if (tid < rank) {
-            const double a = fabs(evl[tid]);
-            int r = 0;
-            for (int j = 0; j < rank; ++j) {
-                const double b = fabs(evl[j]);
-                r += (b > a) || (b == a && j < tid);
-            }
-            ord[r] = tid;
-        }
+        rank_order<true>(rank, ord, [&](int i) { return fabs(evl[i]); });
         mfma_mm<false, false>(B1, B2, Vec, n, rank, rank, ld);   // columns still in solver order (barrier inside)
         {
             const int lane = tid & 63, wave = tid >> 6;
@@ -1370,6 +1358,7 @@ __global__ __launch_bounds__(kEigThreads) void eigh_kernel(const double* __restr
                                                           int* __restrict__ out_sweeps) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     __shared__ JacobiShared sh;
+    __shared__ TriShared ts;   // only eigh_kernel<true> touches it
     const int tid = threadIdx.x, nt = blockDim.x;
     double *A, *V;
     if constexpr (use_lds) { A = reinterpret_cast<double*>(smem_raw); V = A + (size_t)n * ld; }
@@ -1379,35 +1368,19 @@ __global__ __launch_bounds__(kEigThreads) void eigh_kernel(const double* __restr
         A[i * ld + j] = 0.5 * (Ain[e] + Ain[j * n + i]);
     }
     __syncthreads();
-    if constexpr (use_lds) {
-        if (n <= kTriMax) {   // three LDS matrices were requested for this size (jacobi_lds_bytes)
-            __shared__ TriShared ts;
-            double* X = V + (size_t)n * ld;
-            for (int e = tid; e < n * n; e += nt) gA[e] = A[(e / n) * ld + (e % n)];
-            __syncthreads();
-            if (tridiag_eigh(A, V, X, n, ld, &ts, 1e-12)) {
-                for (int j = tid; j < n; j += nt) out_w[j] = ts.lam[j];
-                if (out_v)
-                    for (int e = tid; e < n * n; e += nt) out_v[e] = A[(e / n) * ld + (e % n)];
-                if (tid == 0 && out_sweeps) *out_sweeps = 0;
-                return;
-            }
-            __syncthreads();
-            for (int e = tid; e < n * n; e += nt) A[(e / n) * ld + (e % n)] = gA[e];
-            __syncthreads();
-        }
+    // up to kTriMax three LDS matrices were requested (jacobi_lds_bytes): the third is the tridiagonal solver's X.
+    // out_w takes the eigenvalues in solver order first: final on the tridiagonal path, which yields them ascending
+    const double* vec;
+    const int sweeps = eigh_with_fallback(A, V, V + (size_t)n * ld, n, ld, gA, use_lds && n <= kTriMax, &ts, &sh, 1e-12,
+                                          out_w, vec);
+    if (vec == A) {
+        if (out_v)
+            for (int e = tid; e < n * n; e += nt) out_v[e] = A[(e / n) * ld + (e % n)];
+        if (tid == 0 && out_sweeps) *out_sweeps = 0;
+        return;
     }
-    const int sweeps = jacobi_eigh(A, V, n, ld, &sh, 40);
-    // ascending order by value
-    for (int i = tid; i < n; i += nt) {
-        const double a = A[i * ld + i];
-        int rank = 0;
-        for (int j = 0; j < n; ++j) {
-            const double b = A[j * ld + j];
-            rank += (b < a) || (b == a && j < i);
-        }
-        order[rank] = i;
-    }
+    // Jacobi: ascending order by value
+    rank_order<false>(n, order, [&](int i) { return A[i * ld + i]; });
     __syncthreads();
     for (int j = tid; j < n; j += nt) out_w[j] = A[order[j] * ld + order[j]];
     if (out_v)
@@ -1453,26 +1426,8 @@ __global__ __launch_bounds__(kEigThreads) void onesided_eig_kernel(const double*
     __syncthreads();
     // eigenpairs of the symmetric matrix in P0 (work P2, P3): eigenvalues to gw, eigenvectors to *vec
     auto eigh = [&](const double*& vec) {
-        bool fast = false;
-        if (use_lds && n <= kTriMax) {
-            for (int e = tid; e < n * n; e += nt) gbak[e] = P0[(e / n) * ld + (e % n)];
-            __syncthreads();
-            fast = tridiag_eigh(P0, P2, P3, n, ld, &ts, 1e-12);
-            if (fast) {
-                for (int i = tid; i < n; i += nt) gw[i] = ts.lam[i];
-                vec = P0;
-            } else {
-                __syncthreads();
-                for (int e = tid; e < n * n; e += nt) P0[(e / n) * ld + (e % n)] = gbak[e];
-            }
-            __syncthreads();
-        }
-        if (!fast) {
-            jacobi_eigh(P0, P2, n, ld, &sh, 40);
-            for (int i = tid; i < n; i += nt) gw[i] = P0[i * ld + i];
-            vec = P2;
-            __syncthreads();
-        }
+        eigh_with_fallback(P0, P2, P3, n, ld, gbak, use_lds && n <= kTriMax, &ts, &sh, 1e-12, gw, vec);
+        __syncthreads();
     };
     const double* vec = nullptr;
     eigh(vec);
@@ -1492,16 +1447,7 @@ __global__ __launch_bounds__(kEigThreads) void onesided_eig_kernel(const double*
     }
     __syncthreads();
     eigh(vec);
-    // descending order
-    for (int i = tid; i < n; i += nt) {
-        const double a = gw[i];
-        int rank = 0;
-        for (int j = 0; j < n; ++j) {
-            const double b = gw[j];
-            rank += (b > a) || (b == a && j < i);
-        }
-        order[rank] = i;
-    }
+    rank_order<true>(n, order, [&](int i) { return gw[i]; });   // descending
     __syncthreads();
     for (int j = tid; j < n; j += nt) out_eig[j] = gw[order[j]];
 }
@@ -1519,6 +1465,19 @@ constexpr size_t lds_cap(size_t budget, size_t static_bytes) {
     return budget < kLdsPerWorkgroup - static_bytes ? budget : kLdsPerWorkgroup - static_bytes;
 }
 
+// odd row stride; the fixed one of the tridiagonal solver up to its largest order
+int eig_ld(int n) { return n <= kTriMax ? kTriLd : (n | 1); }
+
+// One workgroup of kEigThreads with `lds_bytes` of dynamic LDS on the context's stream.
+template <typename... Params, typename... Args>
+msm_status launch_single_workgroup(msm_ctx* ctx, void (*kern)(Params...), size_t lds_bytes, Args... args) {
+    if (lds_bytes > 48 * 1024)
+        MSM_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+    hipLaunchKernelGGL(kern, dim3(1), dim3(kEigThreads), lds_bytes, ctx->stream, args...);
+    MSM_CHECK_LAUNCH(ctx);
+    return MSM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1529,7 +1488,7 @@ msm_status msm_tica_solve(msm_ctx* ctx, const double* d_moments, const double* d
     MSM_REQUIRE(ctx, F >= 1 && F <= 2 * kMaxPairs, "msm_tica_solve: need 1 <= F <= %d (got %d)", 2 * kMaxPairs, F);
     MSM_REQUIRE(ctx, epsilon >= 0.0, "msm_tica_solve: epsilon must be >= 0");
     MSM_REQUIRE(ctx, d_moments && d_eigvals && d_coeffs && d_mean && d_rank, "msm_tica_solve: NULL pointer");
-    const int ld = F <= kTriMax ? kTriLd : (F | 1);  // odd stride; the fixed one of the tridiagonal solver for F <= 64
+    const int ld = eig_ld(F);
     const size_t mat = (size_t)F * ld;
     const size_t need = (4 * mat + 3 * F) * sizeof(double) + (size_t)F * sizeof(int) + 64;
     msm_status rs = msm_reserve_scratch(ctx, need);
@@ -1544,12 +1503,8 @@ msm_status msm_tica_solve(msm_ctx* ctx, const double* d_moments, const double* d
     else if (2 * mat * sizeof(double) <= lds_cap(lds_budget, kStaticLdsJacobi)) lds_mats = 2;
     const size_t lds = (size_t)lds_mats * mat * sizeof(double);
     auto kern = lds_mats == 4 ? tica_solve_kernel<4> : (lds_mats == 2 ? tica_solve_kernel<2> : tica_solve_kernel<0>);
-    if (lds > 48 * 1024)
-        MSM_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(1), dim3(kEigThreads), lds, ctx->stream, d_moments, d_scale, F, ld, epsilon,
-                       kinetic_map, wk, d_eigvals, d_coeffs, d_mean, d_rank);
-    MSM_CHECK_LAUNCH(ctx);
-    return MSM_OK;
+    return launch_single_workgroup(ctx, kern, lds, d_moments, d_scale, F, ld, epsilon, kinetic_map, wk, d_eigvals, d_coeffs,
+                                   d_mean, d_rank);
 }
 
 msm_status msm_onesided_tica_eigenvalues(msm_ctx* ctx, const double* d_moments, int F, double clip, double* d_eigvals) {
@@ -1557,7 +1512,7 @@ msm_status msm_onesided_tica_eigenvalues(msm_ctx* ctx, const double* d_moments, 
     MSM_REQUIRE(ctx, F >= 1 && F <= 2 * kMaxPairs, "msm_onesided_tica_eigenvalues: need 1 <= F <= %d (got %d)",
                 2 * kMaxPairs, F);
     MSM_REQUIRE(ctx, d_moments && d_eigvals && clip > 0.0, "msm_onesided_tica_eigenvalues: bad arguments");
-    const int ld = F <= kTriMax ? kTriLd : (F | 1);
+    const int ld = eig_ld(F);
     const size_t mat = (size_t)F * ld;
     const size_t lds = 4 * mat * sizeof(double);
     const bool use_lds = lds <= lds_cap(140 * 1024, kStaticLdsTri);
@@ -1569,19 +1524,14 @@ msm_status msm_onesided_tica_eigenvalues(msm_ctx* ctx, const double* d_moments, 
     double* gw = gbak + (size_t)F * F;
     int* order = (int*)(gw + F);
     auto kern = use_lds ? onesided_eig_kernel<true> : onesided_eig_kernel<false>;
-    if (use_lds && lds > 48 * 1024)
-        MSM_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(1), dim3(kEigThreads), use_lds ? lds : 0, ctx->stream, d_moments, F, ld, clip, gP, gbak,
-                       gw, order, d_eigvals);
-    MSM_CHECK_LAUNCH(ctx);
-    return MSM_OK;
+    return launch_single_workgroup(ctx, kern, use_lds ? lds : 0, d_moments, F, ld, clip, gP, gbak, gw, order, d_eigvals);
 }
 
 msm_status msm_eigh(msm_ctx* ctx, const double* d_a, int n, double* d_w, double* d_v, int* d_sweeps) {
     if (!ctx) return MSM_ERR_INVALID;
     MSM_REQUIRE(ctx, n >= 1 && n <= 2 * kMaxPairs, "msm_eigh: need 1 <= n <= %d (got %d)", 2 * kMaxPairs, n);
     MSM_REQUIRE(ctx, d_a && d_w, "msm_eigh: NULL pointer");
-    const int ld = n <= kTriMax ? kTriLd : (n | 1);
+    const int ld = eig_ld(n);
     const size_t mat = (size_t)n * ld;
     msm_status rs = msm_reserve_scratch(ctx, 2 * mat * sizeof(double) + (size_t)n * sizeof(int) + 64);
     if (rs != MSM_OK) return rs;
@@ -1591,12 +1541,7 @@ msm_status msm_eigh(msm_ctx* ctx, const double* d_a, int n, double* d_w, double*
     const size_t lds = jacobi_lds_bytes(n, ld);
     const int use_lds = lds <= lds_cap(140 * 1024, kStaticLdsTri);
     auto kern = use_lds ? eigh_kernel<true> : eigh_kernel<false>;
-    if (use_lds && lds > 48 * 1024)
-        MSM_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(1), dim3(kEigThreads), use_lds ? lds : 0, ctx->stream, d_a, n, ld, gA, gV, order,
-                       d_w, d_v, d_sweeps);
-    MSM_CHECK_LAUNCH(ctx);
-    return MSM_OK;
+    return launch_single_workgroup(ctx, kern, use_lds ? lds : 0, d_a, n, ld, gA, gV, order, d_w, d_v, d_sweeps);
 }
 
 }  // extern "C"
