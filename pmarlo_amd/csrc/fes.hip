@@ -19,6 +19,7 @@
 namespace {
 
 constexpr int kT = 256;
+constexpr size_t kHistLdsBytes = 64 * 1024;   // dynamic LDS of hist2d_kernel: edges, then bins
 typedef double v4f64 __attribute__((ext_vector_type(4)));
 
 // ---------------------------------------------------------------------------------------------
@@ -101,24 +102,31 @@ __device__ __forceinline__ int edge_bin(const double* e, int nb, double inv_d, d
     return i;
 }
 
-template <bool WEIGHTED, bool LDS_BINS>
+// LDS_EDGES: both edge tables are staged in LDS (with the bins behind them when LDS_BINS); otherwise they are read
+// from global memory, which any table length allows (a 1-D histogram of several thousand bins is nx x 1)
+template <bool WEIGHTED, bool LDS_BINS, bool LDS_EDGES>
 __global__ __launch_bounds__(kT) void hist2d_kernel(const double* __restrict__ x, int64_t sx, const double* __restrict__ y,
                                                     int64_t sy, int64_t n, const double* __restrict__ w, double scale,
                                                     const double* __restrict__ xe, int nx, const double* __restrict__ ye,
                                                     int ny, unsigned long long* __restrict__ bins) {
+    static_assert(LDS_EDGES || !LDS_BINS, "the LDS bins sit behind the LDS edges");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     double* lxe = reinterpret_cast<double*>(smem);
     double* lye = lxe + nx + 1;
     unsigned long long* lb = reinterpret_cast<unsigned long long*>(lye + ny + 1);
-    for (int i = threadIdx.x; i <= nx; i += kT) lxe[i] = xe[i];
-    for (int i = threadIdx.x; i <= ny; i += kT) lye[i] = ye[i];
+    if (LDS_EDGES) {
+        for (int i = threadIdx.x; i <= nx; i += kT) lxe[i] = xe[i];
+        for (int i = threadIdx.x; i <= ny; i += kT) lye[i] = ye[i];
+    }
     if (LDS_BINS)
         for (int i = threadIdx.x; i < nx * ny; i += kT) lb[i] = 0ull;
-    __syncthreads();
-    const double inv_dx = nx / (lxe[nx] - lxe[0]), inv_dy = ny / (lye[ny] - lye[0]);
+    if (LDS_EDGES) __syncthreads();
+    const double* ex = LDS_EDGES ? lxe : xe;
+    const double* ey = LDS_EDGES ? lye : ye;
+    const double inv_dx = nx / (ex[nx] - ex[0]), inv_dy = ny / (ey[ny] - ey[0]);
     for (int64_t i = (int64_t)blockIdx.x * kT + threadIdx.x; i < n; i += (int64_t)gridDim.x * kT) {
-        const int ix = edge_bin(lxe, nx, inv_dx, x[i * sx]);
-        const int iy = edge_bin(lye, ny, inv_dy, y[i * sy]);
+        const int ix = edge_bin(ex, nx, inv_dx, x[i * sx]);
+        const int iy = edge_bin(ey, ny, inv_dy, y[i * sy]);
         if (ix < 0 || iy < 0) continue;
         const unsigned long long inc = WEIGHTED ? (unsigned long long)__double2ll_rn(w[i] * scale) : 1ull;
         atomicAdd((LDS_BINS ? lb : bins) + ix * ny + iy, inc);
@@ -323,7 +331,7 @@ __global__ __launch_bounds__(256) void clip_or_wrap_kernel(const double* __restr
         const double v = x[t * stride];
         double r;
         if (mode == 1) {
-            r = fmin(fmax(v, lo), hi);
+            r = v < lo ? lo : (v > hi ? hi : v);       // np.clip: a NaN stays NaN (fmin / fmax would drop it)
         } else {
             r = fmod(v - lo, span);
             if (r != 0.0) { if (r < 0.0) r += span; } else r = 0.0;
@@ -356,7 +364,8 @@ msm_status msm_hist2d(msm_ctx* ctx, const double* d_x, int64_t sx, const double*
                       const double* d_w, double w_absmax, const double* d_xedges, int nx, const double* d_yedges, int ny,
                       double* d_hist) {
     if (!ctx) return MSM_ERR_INVALID;
-    MSM_REQUIRE(ctx, n >= 0 && nx >= 1 && ny >= 1 && (int64_t)nx * ny <= (1 << 24), "msm_hist2d: bad shape");
+    MSM_REQUIRE(ctx, n >= 0 && nx >= 1 && ny >= 1 && (int64_t)nx * ny <= (1 << 24),
+                "msm_hist2d: bad shape (need n >= 0, nx >= 1, ny >= 1 and at most 2^24 = 16777216 cells)");
     MSM_REQUIRE(ctx, d_xedges && d_yedges && d_hist && (n == 0 || (d_x && d_y)), "msm_hist2d: NULL pointer");
     MSM_REQUIRE(ctx, !d_w || (w_absmax > 0.0 && w_absmax < 1e300), "msm_hist2d: w_absmax must bound |w| (> 0)");
     const int cells = nx * ny;
@@ -371,15 +380,24 @@ msm_status msm_hist2d(msm_ctx* ctx, const double* d_x, int64_t sx, const double*
         scale = std::ldexp(1.0, e);
     }
     if (n > 0) {
+        // dynamic LDS stays within the 64 KiB a kernel has without opting in: the edges go there when they fit, the
+        // bins when they fit behind them; a longer edge table is read from global memory
         const size_t edge_bytes = (size_t)(nx + ny + 2) * sizeof(double);
-        const bool lds_bins = (size_t)cells * 8 + edge_bytes <= 64 * 1024;
-        const size_t lds = edge_bytes + (lds_bins ? (size_t)cells * 8 : 0);
+        const bool lds_edges = edge_bytes <= kHistLdsBytes;
+        const bool lds_bins = (size_t)cells * 8 + edge_bytes <= kHistLdsBytes;
+        const size_t lds = lds_edges ? edge_bytes + (lds_bins ? (size_t)cells * 8 : 0) : 0;
         const int grid = (int)std::min<int64_t>((n + kT * 8 - 1) / (kT * 8), (int64_t)ctx->n_cu * 4);
-#define MSM_H2D(W, L)                                                                                              \
-        hipLaunchKernelGGL((hist2d_kernel<W, L>), dim3(grid), dim3(kT), lds, ctx->stream, d_x, sx, d_y, sy, n, d_w, \
+#define MSM_H2D(W, L, E)                                                                                              \
+        hipLaunchKernelGGL((hist2d_kernel<W, L, E>), dim3(grid), dim3(kT), lds, ctx->stream, d_x, sx, d_y, sy, n, d_w, \
                            scale, d_xedges, nx, d_yedges, ny, bins)
-        if (d_w) { if (lds_bins) MSM_H2D(true, true); else MSM_H2D(true, false); }
-        else { if (lds_bins) MSM_H2D(false, true); else MSM_H2D(false, false); }
+#define MSM_H2D_W(W)                                                       \
+        do {                                                               \
+            if (lds_bins) MSM_H2D(W, true, true);                          \
+            else if (lds_edges) MSM_H2D(W, false, true);                   \
+            else MSM_H2D(W, false, false);                                 \
+        } while (0)
+        if (d_w) MSM_H2D_W(true); else MSM_H2D_W(false);
+#undef MSM_H2D_W
 #undef MSM_H2D
         MSM_CHECK_LAUNCH(ctx);
     }
