@@ -327,6 +327,23 @@ msm_status msm_tica_solve(msm_ctx* ctx, const double* d_moments, const double* d
                           double epsilon, int kinetic_map, double* d_eigvals, double* d_coeffs,
                           double* d_mean, int* d_rank);
 
+/* The same solve when only the n_lead leading components are read (tica_reduce keeps `n_components` of them:
+ * S/markov_state_model/reduction.py:109; deeptime 0.4.5 TICA(dim=...) truncates the same sorted list).
+ * d_coeffs and d_eigvals are 0 from min(n_lead, rank) on; d_mean and d_rank as msm_tica_solve gives them.
+ * n_lead <= 0 or n_lead >= F: msm_tica_solve.
+ * F <= 64 (C00 of full rank or not), 2 (n_lead + 2) < rank: of the whitened rank x rank problem only the
+ * n_lead + 2 eigenvalues at either end of the spectrum are bracketed and only the vectors of the n_lead + 1 at
+ * either end are formed and tested.  Column i < n_lead of d_coeffs and d_eigvals[i] then carry the bits
+ * msm_tica_solve gives them, with ONE exception: msm_tica_solve gives up the tridiagonal solver's result for Jacobi
+ * when any of its rank vectors fails the residual or orthogonality test; a failure that involves a vector this
+ * entry does not form goes unseen here, the tridiagonal result is kept, and the kept pairs agree with
+ * msm_tica_solve to solver accuracy (the bounds both meet), not bit for bit.
+ * Every other case (F > 64, the Jacobi paths, 2 (n_lead + 2) >= rank, a tie in |eigenvalue| at the cut, an
+ * eigenvalue within 1e-6 of the norm of the vectors formed) computes all pairs and truncates: bits always equal. */
+msm_status msm_tica_solve_leading(msm_ctx* ctx, const double* d_moments, const double* d_scale, int F,
+                                  double epsilon, int kinetic_map, double* d_eigvals, double* d_coeffs,
+                                  double* d_mean, int* d_rank, int n_lead);
+
 /* Y[t][c] = sum_f (((x[t][f] - mu[f]) * inv_sigma[f]) - mean2[f]) * W[f][c], fp64 FMA chain
  * over ascending f.  Replaces model.transform(X_prep) of tica_reduce
  * (S/markov_state_model/reduction.py:109).  NaN -> 0 after centring.

@@ -880,8 +880,37 @@ __device__ __forceinline__ bool ldl_whiten_registers(const double* C, double* W,
 // A: symmetric n x n (destroyed; on success its columns hold the eigenvectors, ascending eigenvalues in
 // ts->lam).  Q (ends up holding Q'), X: n x n work matrices (same stride).  Returns false (uniformly) when the result must not be
 // used; the caller then solves its own copy of A by Jacobi.  blockDim.x == 1024.
-__device__ __forceinline__ bool tridiag_eigh(double* A, double* Q, double* X, int n, int ld, TriShared* ts, double orth_tol) {
+//
+// want > 0: only the `want` pairs of largest |eigenvalue| will be read (order: |ev| descending, equal ones by solver
+// index, the rule of rank_order<true>; sel: an LDS array of n ints).  They lie among the want + 1 algebraically
+// smallest and the want + 1 largest eigenvalues, the candidates.  Only those nc = 2 (want + 1) and one guard beyond them
+// at either end are bracketed, each by the instructions and probe points the full solve spends on it, and everything
+// after (twisted factorisation, acceptance test, Z = Q X) runs on the candidates' nc columns alone -- the arithmetic
+// of a column does not depend on where it sits, so every number carries the bits the full solve gives it.  On return
+// kept = nc, ts->lam[0 .. nc) and columns 0 .. nc - 1 of A hold the candidates by ascending solver index; ranked among
+// themselves by the same rule, the first `want` are the leading pairs of the whole spectrum in their order.
+// kept = 0 says that all n pairs were computed, as without `want`:
+//   * when candidates and guards are all there is, 2 (want + 2) >= n;
+//   * when the candidates ranked want-th and (want + 1)-th have the same |ev|: an eigenvalue outside the candidates can
+//     enter the leading set only through such a tie (it has want + 1 candidates no smaller than itself on its side of
+//     the spectrum, of which at most want - 1 may rank ahead of it), and then the full order decides;
+//   * when a guard lies within kTriGuard (of |T| <= 1) of the candidate next to it: the two vectors would fail the
+//     orthogonality test of the full solve, which this one could not see.
+// Going back costs a second eigenvalue phase (about 63 k cycles, 27 us, on top of what the full solve takes): the
+// phase is one dependent chain per wave, as long for the missing brackets as for all of them.
+// What stays out of sight is every failed acceptance that involves a vector this solve does not form -- a residual
+// of such a vector, a pair of such vectors short of orthogonal, or a candidate and a guard more than kTriGuard apart
+// that still miss orth_tol: it sends the full solve to Jacobi and not this one, and the kept pairs then agree to the
+// accuracy of the two solvers, not bit for bit.
+// kTriGuard is an observed figure, not a bound: pairs up to ~1e-9 |T| apart are the ones seen to miss the tolerances
+// (the comment above TriShared), and the guard keeps three decades from that.  The estimate n eps / gap of the
+// defect of two independently computed vectors would ask for n eps / orth_tol = 1.4e-3 at n = 64, orth_tol = 1e-11,
+// which neighbours in an ordinary whitened spectrum undercut while their vectors pass the test by orders of magnitude.
+constexpr double kTriGuard = 1e-6;
+__device__ __forceinline__ bool tridiag_eigh(double* A, double* Q, double* X, int n, int ld, TriShared* ts, double orth_tol,
+                                             int want, int* sel, int& kept) {
     const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63, wave = tid >> 6;
+    kept = 0;
     if (n == 1) {
         if (tid == 0) { ts->lam[0] = A[0]; A[0] = 1.0; }
         __syncthreads();
@@ -932,31 +961,60 @@ __device__ __forceinline__ bool tridiag_eigh(double* A, double* Q, double* X, in
     // ---- (2) eigenvalues: eigenvalue i = tid / 8 is bracketed by 8 lanes (the first eight waves, two per SIMD).
     // 20 rounds: 9^20 = 2^63.4, the brackets end at rounding level (2^55.7 left 4e-12 of orthogonality defect on a
     // cond-1e4 matrix)
-    if (tid < 8 * kTriMax && wave * 8 < n) {
-        const int i = tid >> 3, t = tid & 7;
-        const int nblocks = (n + 7) >> 3;
-        double lo = ts->gl, hi = ts->gu;
-        const double frac = (double)(t + 1) * (1.0 / 9.0);
-        for (int it = 0; it < 20; ++it) {
-            const double x = fma(hi - lo, frac, lo);
-            const int c = sturm_count(ts, nblocks, x);
-            double nlo = c <= i ? x : lo, nhi = c > i ? x : hi;
-            lo = row8_reduce(nlo, hw_max_f64);   // the 8 lanes of eigenvalue i agree on the tightest bracket
-            hi = row8_reduce(nhi, hw_min_f64);
+    // Leading pairs only: the nb = 2 (want + 2) eigenvalues at the two ends are bracketed, slot b is eigenvalue b at the
+    // lower end, n - nb + b at the upper one; otherwise nb = n and slot b is eigenvalue b.  The loop runs once, or twice
+    // when a tie at the cut or a close guard sends it back for all n.
+    bool lead = want > 0 && 2 * (want + 2) < n;
+    int nb = lead ? 2 * (want + 2) : n;
+    int na = n;   // columns of X from here on
+    for (;;) {
+        if (tid < 8 * kTriMax && wave * 8 < nb) {
+            const int b = tid >> 3, t = tid & 7;
+            const int i = !lead || b < want + 2 ? b : n - nb + b;
+            const int nblocks = (n + 7) >> 3;
+            double lo = ts->gl, hi = ts->gu;
+            const double frac = (double)(t + 1) * (1.0 / 9.0);
+            for (int it = 0; it < 20; ++it) {
+                const double x = fma(hi - lo, frac, lo);
+                const int c = sturm_count(ts, nblocks, x);
+                double nlo = c <= i ? x : lo, nhi = c > i ? x : hi;
+                lo = row8_reduce(nlo, hw_max_f64);   // the 8 lanes of eigenvalue i agree on the tightest bracket
+                hi = row8_reduce(nhi, hw_min_f64);
+            }
+            if (b < nb && t == 0) ts->lam[i] = 0.5 * (lo + hi);
         }
-        if (i < n && t == 0) ts->lam[i] = 0.5 * (lo + hi);
+        __syncthreads();
+        if (!lead) break;
+        const int nc = 2 * (want + 1);   // candidate c is eigenvalue c (c <= want) or n - nc + c
+        const auto cand = [&](int c) { return c <= want ? c : n - nc + c; };
+        const auto key = [&](int c) { return fabs(ts->lam[cand(c)] / ts->scale); };   // the value the caller's sort sees
+        rank_order<true>(nc, sel, key);
+        __syncthreads();
+        const bool lone = ts->lam[want + 1] - ts->lam[want] > kTriGuard &&
+                          ts->lam[n - want - 1] - ts->lam[n - want - 2] > kTriGuard;
+        if (lone && key(sel[want - 1]) != key(sel[want])) {   // uniform
+            const double lk = tid < nc ? ts->lam[cand(tid)] : 0.0;   // the candidates move to the front
+            __syncthreads();
+            if (tid < nc) ts->lam[tid] = lk;
+            __syncthreads();
+            na = nc;
+            break;
+        }
+        __syncthreads();   // sel and lam have been read: lam is written again
+        lead = false;
+        nb = n;
     }
-    __syncthreads();
     TSTAMP(4);
-    // ---- (3) eigenvectors of T, eigenvalue i = lane: wave 0 runs the forward pivots q_j (into X[:, i]), wave 1
-    // the backward pivots r_j (their reciprocals into A[:, i]); gamma_j = q_j - e_j^2 / r_{j+1} is smallest at the
-    // twist k; z_k = 1, z_j = -(e_j / q_j) z_{j+1} above it (wave 0), z_{j+1} = -(e_j / r_{j+1}) z_j below (wave 1).
+    // ---- (3) eigenvectors of T, column i = lane (eigenvalue i, or the i-th candidate): wave 0 runs the forward pivots
+    // q_j (into X[:, i]), wave 1 the backward pivots r_j (their reciprocals into A[:, i]); gamma_j = q_j - e_j^2 / r_{j+1}
+    // is smallest at the twist k; z_k = 1, z_j = -(e_j / q_j) z_{j+1} above it (wave 0), z_{j+1} = -(e_j / r_{j+1}) z_j
+    // below (wave 1).
     // Every loop takes its rows eight at a time so that the LDS reads of a block are in flight together.
     const double tiny = 1e-290;
-    double* Xc = X + (lane < n ? lane : 0);
-    double* Ac = A + (lane < n ? lane : 0);
-    const double lamb = ts->lam[lane < n ? lane : 0];
-    if (wave == 0 && lane < n) {
+    double* Xc = X + (lane < na ? lane : 0);
+    double* Ac = A + (lane < na ? lane : 0);
+    const double lamb = ts->lam[lane < na ? lane : 0];
+    if (wave == 0 && lane < na) {
         double q = ts->de[0].x - lamb;
         Xc[0] = q;
         for (int j0 = 1; j0 < n; j0 += 8) {
@@ -972,7 +1030,7 @@ __device__ __forceinline__ bool tridiag_eigh(double* A, double* Q, double* X, in
                 }
             }
         }
-    } else if (wave == 1 && lane < n) {
+    } else if (wave == 1 && lane < na) {
         double r = ts->de[n - 1].x - lamb;
         if (fabs(r) < tiny) r = -tiny;
         double ir = nr_rcp(r);
@@ -998,7 +1056,7 @@ __device__ __forceinline__ bool tridiag_eigh(double* A, double* Q, double* X, in
     }
     __syncthreads();
     int kk = n - 1;
-    if (wave < 2 && lane < n) {
+    if (wave < 2 && lane < na) {
         double gbest = fabs(Xc[(n - 1) * ld]);   // gamma_{n-1} = q_{n-1}
         for (int j0 = n - 2; j0 >= 0; j0 -= 8) {
             double g[8];
@@ -1013,7 +1071,7 @@ __device__ __forceinline__ bool tridiag_eigh(double* A, double* Q, double* X, in
         }
     }
     __syncthreads();   // both waves have read every q before the z overwrite them
-    if (wave == 0 && lane < n) {
+    if (wave == 0 && lane < na) {
         double z = 1.0, nrm2 = 1.0;
         for (int j0 = n - 2; j0 >= 0; j0 -= 8) {
             double f[8];
@@ -1035,7 +1093,7 @@ __device__ __forceinline__ bool tridiag_eigh(double* A, double* Q, double* X, in
         }
         Xc[kk * ld] = 1.0;
         ts->praw[lane] = nrm2;
-    } else if (wave == 1 && lane < n) {
+    } else if (wave == 1 && lane < na) {
         double z = 1.0, nrm2 = 0.0;
         for (int j0 = 0; j0 + 1 < n; j0 += 8) {
             double f[8];
@@ -1056,7 +1114,7 @@ __device__ __forceinline__ bool tridiag_eigh(double* A, double* Q, double* X, in
         ts->uq[lane] = nrm2;
     }
     __syncthreads();
-    if (tid < n) {
+    if (tid < na) {
         const double nrm2 = ts->praw[tid] + ts->uq[tid];
         const bool ok = nrm2 > 0.0 && nrm2 < 1e300;
         ts->inv[tid] = nr_rsqrt(ok ? nrm2 : 1.0);
@@ -1069,8 +1127,8 @@ __device__ __forceinline__ bool tridiag_eigh(double* A, double* Q, double* X, in
     {
         double worst = 0.0;
         bool bad = false;
-        for (int e0 = tid; e0 < n * n; e0 += nt) {
-            const int j = e0 / n, i = e0 - j * n;
+        for (int e0 = tid; e0 < n * na; e0 += nt) {
+            const int j = e0 / na, i = e0 - j * na;
             const double x0 = X[j * ld + i];
             const double xm = j > 0 ? ts->e[j - 1] * X[(j - 1) * ld + i] : 0.0;
             const double xp = j + 1 < n ? ts->e[j] * X[(j + 1) * ld + i] : 0.0;
@@ -1078,11 +1136,11 @@ __device__ __forceinline__ bool tridiag_eigh(double* A, double* Q, double* X, in
             bad = bad || !(fabs(tx) <= 1e-10);   // scaled matrix: |T| <= 1
         }
         const int jj = lane & 15, g = lane >> 4;
-        const int tiles = (n + 15) >> 4;
+        const int tiles = (na + 15) >> 4;
         for (int t = wave; t < tiles * tiles; t += nt >> 6) {
             const int a0 = (t / tiles) * 16, b0 = (t - (t / tiles) * tiles) * 16;
             if (b0 > a0) continue;   // X'X is symmetric
-            const bool aok = a0 + jj < n, bok = b0 + jj < n;
+            const bool aok = a0 + jj < na, bok = b0 + jj < na;
             const int ai = aok ? a0 + jj : 0, bi = bok ? b0 + jj : 0;
             const double sa = ts->inv[ai], sb = ts->inv[bi];
             const tri_v4f64 acc = mfma_tile_acc(
@@ -1090,7 +1148,7 @@ __device__ __forceinline__ bool tridiag_eigh(double* A, double* Q, double* X, in
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int row = a0 + g + 4 * r, col = b0 + jj;
-                if (row < n && col < n) worst = fmax(worst, fabs(acc[r] - (row == col ? 1.0 : 0.0)));
+                if (row < na && col < na) worst = fmax(worst, fabs(acc[r] - (row == col ? 1.0 : 0.0)));
             }
         }
         if (bad) worst = 1e300;
@@ -1103,10 +1161,11 @@ __device__ __forceinline__ bool tridiag_eigh(double* A, double* Q, double* X, in
         TSTAMP(6);
         if (ts->bad || !(worst <= orth_tol)) return false;
     }
-    mfma_mm<true, false>(A, Q, X, n, n, n, ld, ts->inv);   // Q holds Q'
-    if (tid < n) ts->lam[tid] /= ts->scale;
+    mfma_mm<true, false>(A, Q, X, n, na, n, ld, ts->inv);   // Q holds Q'
+    if (tid < na) ts->lam[tid] /= ts->scale;
     __syncthreads();
     TSTAMP(7);
+    kept = na < n ? na : 0;
     return true;
 }
 
@@ -1115,19 +1174,24 @@ __device__ __forceinline__ bool tridiag_eigh(double* A, double* Q, double* X, in
 // packed, global).  Eigenvalues to ev_out in solver order, vec = the matrix whose columns hold the eigenvectors
 // (A after tridiag_eigh, V after Jacobi).  Returns the Jacobi sweeps, 0 for the tridiagonal path (tell the two apart
 // by vec: Jacobi on a diagonal matrix takes 0 sweeps as well).  The caller synchronises before ev_out is read.
+// want > 0: only the `want` pairs of largest |eigenvalue| will be read.  kept > 0 on return says that only `kept` pairs
+// were computed (tridiag_eigh): ev_out[0 .. kept) and columns 0 .. kept - 1 of vec, in solver order; the `want` leading
+// ones are among them and rank among them as among all n.  kept = 0: all n.
 // Force-inlined: A, V, X must stay known LDS or known global pointers (see tica_solve_kernel).
 __device__ __forceinline__ int eigh_with_fallback(double* A, double* V, double* X, int n, int ld, double* backup,
                                                   bool try_tri, TriShared* ts, JacobiShared* sh, double orth_tol,
-                                                  double* ev_out, const double*& vec) {
+                                                  double* ev_out, const double*& vec, int want, int& kept) {
     const int tid = threadIdx.x, nt = blockDim.x;
+    kept = 0;
     if (try_tri) {
         for (int e = tid; e < n * n; e += nt) backup[e] = A[(e / n) * ld + (e % n)];
         __syncthreads();
-        if (tridiag_eigh(A, V, X, n, ld, ts, orth_tol)) {
-            for (int i = tid; i < n; i += nt) ev_out[i] = ts->lam[i];
+        if (tridiag_eigh(A, V, X, n, ld, ts, orth_tol, want, sh->p, kept)) {
+            for (int i = tid; i < (kept ? kept : n); i += nt) ev_out[i] = ts->lam[i];
             vec = A;
             return 0;
         }
+        kept = 0;
         __syncthreads();
         for (int e = tid; e < n * n; e += nt) A[(e / n) * ld + (e % n)] = backup[e];
         __syncthreads();
@@ -1150,7 +1214,7 @@ struct TicaWork {  // global scratch: four n*ld matrices, then ev[n], mean[n], i
 template <int lds_mats>
 __global__ __launch_bounds__(kEigThreads) void tica_solve_kernel(
     const double* __restrict__ mom, const double* __restrict__ scale, int n, int ld, double epsilon, int kinetic_map,
-    TicaWork wk, double* __restrict__ out_eig, double* __restrict__ out_W, double* __restrict__ out_mean,
+    int n_lead, TicaWork wk, double* __restrict__ out_eig, double* __restrict__ out_W, double* __restrict__ out_mean,
     int* __restrict__ out_rank) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     __shared__ JacobiShared sh;
@@ -1292,24 +1356,33 @@ __global__ __launch_bounds__(kEigThreads) void tica_solve_kernel(
     __syncthreads();
     KSTAMP(10);
     // eigenpairs of the whitened C0t: tridiagonal solver (fallback: Jacobi on the saved copy)
+    // only the first `keep` pairs (by |ev|) go out.  Where the LDS tail follows (F <= kTriMax, full rank or not) the
+    // tridiagonal solver may compute just `kept` candidates for them, which that tail knows how to rank; the generic
+    // tail (F = 65 with rank <= 64 reaches the tridiagonal solver too) and every other solver get all `rank` pairs,
+    // kept = 0, and the tails truncate
+    const int keep = n_lead > 0 && n_lead < rank ? n_lead : rank;
+    const bool lds_tail = kFused && n <= kTriMax;
     const double* Vec;
-    eigh_with_fallback(A, V, B1, rank, ld, wk.A, kFused && rank <= kTriMax, &ts, &sh, 1e-11, wk.ev, Vec);
+    int kept;
+    eigh_with_fallback(A, V, B1, rank, ld, wk.A, kFused && rank <= kTriMax, &ts, &sh, 1e-11, wk.ev, Vec,
+                       lds_tail && keep < rank ? keep : 0, kept);
     __syncthreads();
     KSTAMP(11);
-    if (kFused && n <= kTriMax) {
+    if (lds_tail) {
         // ---- the same tail with everything small in the LDS: eigenvalues, their order (|ev| descending, stable), the
         // sign of every column of R = L Rt (its largest-magnitude entry, first occurrence, made positive); the signs
         // and the kinetic-map factors are applied on the way out instead of in place
         double* evl = ts.praw;      // eigenvalues in solver order
         double* sgn = ts.uq;        // +-1 per solver column
         int* ord = sh.p;            // ord[j] = solver column of the j-th largest |ev|
-        if (tid < rank) evl[tid] = wk.ev[tid];
+        const int ncol = kept ? kept : rank;   // solver columns at hand
+        if (tid < ncol) evl[tid] = wk.ev[tid];
         __syncthreads();
-        rank_order<true>(rank, ord, [&](int i) { return fabs(evl[i]); });
-        mfma_mm<false, false>(B1, B2, Vec, n, rank, rank, ld);   // columns still in solver order (barrier inside)
+        rank_order<true>(ncol, ord, [&](int i) { return fabs(evl[i]); });
+        mfma_mm<false, false>(B1, B2, Vec, n, ncol, rank, ld);   // columns still in solver order (barrier inside)
         {
             const int lane = tid & 63, wave = tid >> 6;
-            for (int j = wave; j < rank; j += nt >> 6) {          // one wave per column, lane = row
+            for (int j = wave; j < ncol; j += nt >> 6) {          // one wave per column, lane = row
                 double best = lane < n ? fabs(B1[lane * ld + j]) : -1.0;
                 int bi = lane;
                 double val = lane < n ? B1[lane * ld + j] : 0.0;
@@ -1321,14 +1394,14 @@ __global__ __launch_bounds__(kEigThreads) void tica_solve_kernel(
         for (int e = tid; e < n * n; e += nt) {
             const int i = e / n, j = e - i * n;
             double v = 0.0;
-            if (j < rank) {
+            if (j < keep) {
                 const int c = ord[j];
                 v = B1[i * ld + c] * sgn[c];
                 if (kinetic_map) v *= evl[c];
             }
             out_W[e] = v;
         }
-        for (int j = tid; j < n; j += nt) out_eig[j] = j < rank ? evl[ord[j]] : 0.0;
+        for (int j = tid; j < n; j += nt) out_eig[j] = j < keep ? evl[ord[j]] : 0.0;
         KSTAMP(12);
         return;
     }
@@ -1339,13 +1412,13 @@ __global__ __launch_bounds__(kEigThreads) void tica_solve_kernel(
     for (int e = tid; e < n * n; e += nt) {
         const int i = e / n, j = e - i * n;
         double v = 0.0;
-        if (j < rank) {
+        if (j < keep) {
             v = B1[i * ld + wk.order[j]];
             if (kinetic_map) v *= wk.ev[wk.order[j]];
         }
         out_W[e] = v;
     }
-    for (int j = tid; j < n; j += nt) out_eig[j] = j < rank ? wk.ev[wk.order[j]] : 0.0;
+    for (int j = tid; j < n; j += nt) out_eig[j] = j < keep ? wk.ev[wk.order[j]] : 0.0;
     KSTAMP(12);
 }
 
@@ -1371,8 +1444,9 @@ __global__ __launch_bounds__(kEigThreads) void eigh_kernel(const double* __restr
     // up to kTriMax three LDS matrices were requested (jacobi_lds_bytes): the third is the tridiagonal solver's X.
     // out_w takes the eigenvalues in solver order first: final on the tridiagonal path, which yields them ascending
     const double* vec;
+    int kept;   // all pairs are asked for: stays 0
     const int sweeps = eigh_with_fallback(A, V, V + (size_t)n * ld, n, ld, gA, use_lds && n <= kTriMax, &ts, &sh, 1e-12,
-                                          out_w, vec);
+                                          out_w, vec, 0, kept);
     if (vec == A) {
         if (out_v)
             for (int e = tid; e < n * n; e += nt) out_v[e] = A[(e / n) * ld + (e % n)];
@@ -1426,7 +1500,8 @@ __global__ __launch_bounds__(kEigThreads) void onesided_eig_kernel(const double*
     __syncthreads();
     // eigenpairs of the symmetric matrix in P0 (work P2, P3): eigenvalues to gw, eigenvectors to *vec
     auto eigh = [&](const double*& vec) {
-        eigh_with_fallback(P0, P2, P3, n, ld, gbak, use_lds && n <= kTriMax, &ts, &sh, 1e-12, gw, vec);
+        int kept;   // all pairs are asked for: stays 0
+        eigh_with_fallback(P0, P2, P3, n, ld, gbak, use_lds && n <= kTriMax, &ts, &sh, 1e-12, gw, vec, 0, kept);
         __syncthreads();
     };
     const double* vec = nullptr;
@@ -1484,6 +1559,12 @@ extern "C" {
 
 msm_status msm_tica_solve(msm_ctx* ctx, const double* d_moments, const double* d_scale, int F, double epsilon,
                           int kinetic_map, double* d_eigvals, double* d_coeffs, double* d_mean, int* d_rank) {
+    return msm_tica_solve_leading(ctx, d_moments, d_scale, F, epsilon, kinetic_map, d_eigvals, d_coeffs, d_mean, d_rank, 0);
+}
+
+msm_status msm_tica_solve_leading(msm_ctx* ctx, const double* d_moments, const double* d_scale, int F, double epsilon,
+                                  int kinetic_map, double* d_eigvals, double* d_coeffs, double* d_mean, int* d_rank,
+                                  int n_lead) {
     if (!ctx) return MSM_ERR_INVALID;
     MSM_REQUIRE(ctx, F >= 1 && F <= 2 * kMaxPairs, "msm_tica_solve: need 1 <= F <= %d (got %d)", 2 * kMaxPairs, F);
     MSM_REQUIRE(ctx, epsilon >= 0.0, "msm_tica_solve: epsilon must be >= 0");
@@ -1503,8 +1584,8 @@ msm_status msm_tica_solve(msm_ctx* ctx, const double* d_moments, const double* d
     else if (2 * mat * sizeof(double) <= lds_cap(lds_budget, kStaticLdsJacobi)) lds_mats = 2;
     const size_t lds = (size_t)lds_mats * mat * sizeof(double);
     auto kern = lds_mats == 4 ? tica_solve_kernel<4> : (lds_mats == 2 ? tica_solve_kernel<2> : tica_solve_kernel<0>);
-    return launch_single_workgroup(ctx, kern, lds, d_moments, d_scale, F, ld, epsilon, kinetic_map, wk, d_eigvals, d_coeffs,
-                                   d_mean, d_rank);
+    return launch_single_workgroup(ctx, kern, lds, d_moments, d_scale, F, ld, epsilon, kinetic_map,
+                                   n_lead > 0 && n_lead < F ? n_lead : 0, wk, d_eigvals, d_coeffs, d_mean, d_rank);
 }
 
 msm_status msm_onesided_tica_eigenvalues(msm_ctx* ctx, const double* d_moments, int F, double clip, double* d_eigvals) {

@@ -582,8 +582,10 @@ class Engine:
         return out
 
     def tica_solve(self, moments: DeviceArray, F: int, *, scale: DeviceArray | None = None,
-                   epsilon: float = 1e-6, kinetic_map: bool = True, out=None):
-        """-> (eigvals [F], coeffs [F,F], mean [F], rank int32[1]) on the device (`out`: the same four, preallocated)."""
+                   epsilon: float = 1e-6, kinetic_map: bool = True, out=None, n_lead: int = 0):
+        """-> (eigvals [F], coeffs [F,F], mean [F], rank int32[1]) on the device (`out`: the same four, preallocated).
+        n_lead in 1 .. F-1: only the first n_lead components are wanted; they carry the bits of the full solve, the
+        columns and eigenvalues after them are zero (0 or >= F: all of them)."""
         if out is not None:
             eig, W, mean, rank = out
         else:
@@ -591,9 +593,9 @@ class Engine:
             W = self.empty((F, F), np.float64)
             mean = self.empty((F,), np.float64)
             rank = self.empty((1,), np.int32)
-        check(lib.msm_tica_solve(self.handle, moments.ptr, scale.ptr if scale is not None else None, F,
-                                 float(epsilon), int(bool(kinetic_map)), eig.ptr, W.ptr, mean.ptr, rank.ptr),
-              self.handle)
+        check(lib.msm_tica_solve_leading(self.handle, moments.ptr, scale.ptr if scale is not None else None, F,
+                                         float(epsilon), int(bool(kinetic_map)), eig.ptr, W.ptr, mean.ptr, rank.ptr,
+                                         int(n_lead)), self.handle)
         return eig, W, mean, rank
 
     def project(self, x: DeviceArray, mu: DeviceArray, inv_sigma: DeviceArray, W: DeviceArray, d: int, *,

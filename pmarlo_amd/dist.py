@@ -30,6 +30,7 @@ With ``comm=None`` the same code runs on a single GPU (bench.py at N = 1, tests)
 from __future__ import annotations
 
 import ctypes as C
+import inspect
 import os
 import time
 from dataclasses import dataclass
@@ -376,6 +377,10 @@ class ShardedMSM:
             self.m2 = eng.empty((F,), np.float64)
             self.rank_d = eng.empty((1,), np.int32)
             self.Y = eng.empty((n, d), np.float64)
+            # an engine that can solve for the leading components alone is told how many the projection reads (this
+            # class runs on any object with Engine's methods: one whose tica_solve predates n_lead solves for all)
+            can_lead = "n_lead" in inspect.signature(eng.tica_solve).parameters
+            self._lead_kw = {"n_lead": int(cfg.tica_dim)} if can_lead else {}
         else:
             self.Y = self.x
         self.labels = eng.empty((n,), np.int32)
@@ -436,8 +441,9 @@ class ShardedMSM:
                                    out=(self.mean, self.scale, self.inv_scale))
             self._stamp("moments")
             # 2. TICA solve (every rank solves the same F x F problem on identical bits)
+            #    and only the tica_dim components the projection reads are solved for
             eng.tica_solve(b["lagged"], F, scale=self.scale, epsilon=1e-6, kinetic_map=True,
-                           out=(self.eig, self.W, self.m2, self.rank_d))
+                           out=(self.eig, self.W, self.m2, self.rank_d), **self._lead_kw)
             self._stamp("tica_solve")
             # 3. projection; max |Y| (the fixed-point scale of the Lloyd sums needs it) falls out of the same pass
             # (x - shift) / sigma - m2: m2 is the symmetric mean about the SAME shift the moments used

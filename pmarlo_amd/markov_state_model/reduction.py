@@ -245,7 +245,7 @@ def tica_fit_transform_trajectories(features: np.ndarray, traj_lengths: Sequence
     mu, _, _, has_nan = pipe.standardise_params(xd, scale=False)
     one = eng.to_device(np.ones(Xm.shape[1]))
     mom = pipe.tica_moments(xd, lag, mu, segments=segs, assume_finite=not has_nan, symmetric=True)
-    model = pipe.tica_solve(mom, mu, one, one, lag, n_components)
+    model = pipe.tica_solve(mom, mu, one, one, lag, n_components, all_pairs=True)   # the model goes to the caller whole
     model.dim = min(n_components, int(model.rank.to_host()[0]))
     Y = pipe.tica_transform(model, xd, assume_finite=not has_nan).to_host()
     keep: List[np.ndarray] = []

@@ -105,9 +105,12 @@ class MSMPipeline:
         return self.tica_solve(mom, mu, sigma, inv_sigma, lag, dim, epsilon=epsilon, kinetic_map=kinetic_map)
 
     def tica_solve(self, moments: DeviceArray, mu, sigma, inv_sigma, lag: int, dim: int, *, epsilon: float = 1e-6,
-                   kinetic_map: bool = True) -> TicaModel:
+                   kinetic_map: bool = True, all_pairs: bool = False) -> TicaModel:
+        """The model keeps `dim` components and only those are solved for (columns and eigenvalues from `dim` on are
+        zero); all_pairs: the whole spectrum, for a caller that reads eigenvalues or columns past `dim`."""
         F = mu.shape[0]
-        eig, W, mean, rank = self.eng.tica_solve(moments, F, scale=sigma, epsilon=epsilon, kinetic_map=kinetic_map)
+        eig, W, mean, rank = self.eng.tica_solve(moments, F, scale=sigma, epsilon=epsilon, kinetic_map=kinetic_map,
+                                                 n_lead=0 if all_pairs else int(dim))
         return TicaModel(mu, sigma, inv_sigma, eig, W, mean, rank, int(lag), int(dim), moments)
 
     def tica_transform(self, model: TicaModel, x: DeviceArray, out: DeviceArray | None = None,

@@ -36,7 +36,8 @@ def main():
     inv = eng.to_device(1.0 / std.to_host())
     mom = eng.empty((2 * F * F + 2 * F + 1,), np.float64)
     res["lagged_moments"] = timeit(eng, lambda: eng.lagged_moments(xd, lag, mean, out=mom, assume_finite=True))
-    res["tica_solve"] = timeit(eng, lambda: eng.tica_solve(mom, F, scale=std))
+    res["tica_solve"] = timeit(eng, lambda: eng.tica_solve(mom, F, scale=std), reps=30)
+    res["tica_solve_leading"] = timeit(eng, lambda: eng.tica_solve(mom, F, scale=std, n_lead=d), reps=30)
     eig, W, m2, rank = eng.tica_solve(mom, F, scale=std)
     rngm = np.random.default_rng(1)
     Bm = rngm.normal(size=(F, F))
