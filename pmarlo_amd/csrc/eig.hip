@@ -383,22 +383,7 @@ __device__ __forceinline__ int jacobi_eigh_pipelined(double* A, double* V, int n
     return sweep;
 }
 
-// Rank by counting: order[r] = the index whose key(i) is the r-th largest (descending) or smallest, equal keys in
-// index order (stable).  No barrier: the caller synchronises before `order` is read.
-template <bool descending, typename Key>
-__device__ __forceinline__ void rank_order(int n, int* order, Key key) {
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const double a = key(i);
-        int rank = 0;
-        for (int j = 0; j < n; ++j) {
-            const double b = key(j);
-            rank += (descending ? b > a : b < a) || (b == a && j < i);
-        }
-        order[rank] = i;
-    }
-}
-
-// order[j] = index of the j-th largest |ev| (stable)
+// order[j] = index of the j-th largest |ev| (stable; rank_order: wave.h)
 __device__ void sort_desc_abs(const double* ev, int n, int* order) {
     rank_order<true>(n, order, [&](int i) { return fabs(ev[i]); });
     __syncthreads();
@@ -509,37 +494,10 @@ struct TriShared {
     double taupub[2];
 };
 
-typedef double tri_v4f64 __attribute__((ext_vector_type(4)));
-
 // C[i][j] = sum_k opA(i,k) opB(k,j) on the matrix cores (v_mfma_f64_16x16x4_f64; one 16 x 16 tile of C per wave
 // and trip), i < rows, j < cols, k < inner; opA = A or A', opB = B or B'.  bscale (optional) multiplies column j of
 // opB.  C must not alias A or B.  A 64^3 product costs what it costs on the VALU (the fp64 rates are equal) but
-// reads each operand from the LDS once per tile instead of once per multiply.
-//
-// mfma_tile_acc is one tile: lane (j, g) = (lane & 15, lane >> 4) supplies a(k) = opA(i0 + j, k) and b(k) =
-// opB(k, c0 + j) through loadA(k) / loadB(k), which read clamped (in-range) addresses; aok / bok say whether the
-// lane's row of opA / column of opB lies inside the matrix, and what lies outside is fed as zero.  acc[r] ends up
-// as entry (i0 + g + 4 r, c0 + j) of the tile.
-template <typename LoadA, typename LoadB>
-__device__ __forceinline__ tri_v4f64 mfma_tile_acc(int inner, int g, bool aok, bool bok, LoadA loadA, LoadB loadB) {
-    tri_v4f64 acc = {0.0, 0.0, 0.0, 0.0};
-    for (int k0 = 0; k0 < inner; k0 += 16) {   // four instructions per trip: their operand reads go out together
-        double a[4], b[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const bool kok = k0 + 4 * u + g < inner;
-            const int k = kok ? k0 + 4 * u + g : 0;
-            a[u] = loadA(k);
-            b[u] = loadB(k);
-            if (!(aok && kok)) a[u] = 0.0;
-            if (!(bok && kok)) b[u] = 0.0;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u], b[u], acc, 0, 0, 0);
-    }
-    return acc;
-}
-
+// reads each operand from the LDS once per tile instead of once per multiply.  One tile: mfma_tile_acc (wave.h).
 template <bool TA, bool TB>
 __device__ __forceinline__ void mfma_mm(double* C, const double* A, const double* B, int rows, int cols, int inner, int ld,
                         const double* bscale = nullptr) {
@@ -551,7 +509,7 @@ __device__ __forceinline__ void mfma_mm(double* C, const double* A, const double
         const bool aok = i0 + j < rows, bok = c0 + j < cols;
         const int ai = aok ? i0 + j : 0, bj = bok ? c0 + j : 0;
         const double bs = bscale ? bscale[bj] : 1.0;
-        const tri_v4f64 acc = mfma_tile_acc(
+        const v4f64 acc = mfma_tile_acc(
             inner, g, aok, bok, [&](int k) { return TA ? A[k * ld + ai] : A[ai * ld + k]; },
             [&](int k) { return (TB ? B[bj * ld + k] : B[k * ld + bj]) * bs; });
 #pragma unroll
@@ -1143,7 +1101,7 @@ __device__ __forceinline__ bool tridiag_eigh(double* A, double* Q, double* X, in
             const bool aok = a0 + jj < na, bok = b0 + jj < na;
             const int ai = aok ? a0 + jj : 0, bi = bok ? b0 + jj : 0;
             const double sa = ts->inv[ai], sb = ts->inv[bi];
-            const tri_v4f64 acc = mfma_tile_acc(
+            const v4f64 acc = mfma_tile_acc(
                 n, g, aok, bok, [&](int k) { return X[k * ld + ai] * sa; }, [&](int k) { return X[k * ld + bi] * sb; });
 #pragma unroll
             for (int r = 0; r < 4; ++r) {

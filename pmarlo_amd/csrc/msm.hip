@@ -201,19 +201,15 @@ struct SpecArgs {
     const int* n_ptr;     // [batch] (or NULL -> n_fixed)
     int n_fixed;
     int p;                // subspace size (<= kMaxP)
-    int n_iter;
     int init;             // 1: (re)initialise the basis
     unsigned long long seed;
-    double* Z;            // [batch][n_max * p] basis (persists between calls)
-    double* W;            // [batch][n_max * p]
-    size_t zw_stride;
+    size_t zw_stride;     // between the bases of two matrices (each n_max * p, in the workspace)
     double* ritz;         // [batch][4 * kMaxP]: re | im | previous re | previous im   (sorted by |.| desc)
     double* pi;           // [batch][n_max] or NULL
     size_t pi_stride;
-    double* change;       // [batch] max relative change of the top `n_watch` Ritz values over the last check gap
+    double* change;       // [batch] worst residual of the top `n_watch` Ritz pairs (watched_residuals)
     int n_watch;
     double freeze_tol;    // > 0: a matrix whose `change` (from the previous call) is <= this is left as it is
-    int check_gap;
     int* status;          // [batch] 0 ok, else hqr failure index
     // implied timescales (optional)
     int n_its;            // 0: skip
@@ -234,7 +230,6 @@ __device__ __forceinline__ bool spec_frozen(const SpecArgs& ar, int b) {
     return ar.freeze_tol > 0.0 && !ar.init && ar.change[b] <= ar.freeze_tol;
 }
 
-
 struct SpecShared {
     double G[kMaxP * kMaxP];
     double R[kMaxP * kMaxP];
@@ -251,7 +246,6 @@ struct SpecShared {
 // per entry walking all rows) read every operand element p times from the LDS: 8 us at n = 200, p = 32, LDS-bandwidth
 // bound.  Here a wave takes a 16 x 16 tile of M and a share of the rows (16 rows per trip: four v_mfma_f64_16x16x4
 // whose operand reads go out together); the shares of a tile are added in share order.  scratch: LDS, >= 3 kMaxP^2 doubles.
-typedef double spec_v4f64 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void spec_gram_fast(const double* __restrict__ A, const double* __restrict__ B, int n, int p,
                                                double* M, double* scratch) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
@@ -265,23 +259,9 @@ __device__ __forceinline__ void spec_gram_fast(const double* __restrict__ A, con
         const int a0 = (t / tp) * 16, b0 = (t - (t / tp) * tp) * 16;
         const bool aok = a0 + j < p, bok = b0 + j < p;
         const int ac = aok ? a0 + j : 0, bc = bok ? b0 + j : 0;
-        spec_v4f64 acc = {0.0, 0.0, 0.0, 0.0};
         const int k_begin = sh_id * trips_per_share * 16, k_end = min(n, k_begin + trips_per_share * 16);
-        for (int k0 = k_begin; k0 < k_end; k0 += 16) {
-            double av[4], bv[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int k = k0 + 4 * u + g;
-                const bool kok = k < k_end;
-                const int kk = kok ? k : 0;
-                av[u] = A[kk * p + ac];
-                bv[u] = B[kk * p + bc];
-                if (!(aok && kok)) av[u] = 0.0;
-                if (!(bok && kok)) bv[u] = 0.0;
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u], bv[u], acc, 0, 0, 0);
-        }
+        const v4f64 acc = mfma_tile_acc(k_end - k_begin, g, aok, bok, [&](int k) { return A[(k_begin + k) * p + ac]; },
+                                        [&](int k) { return B[(k_begin + k) * p + bc]; });
         double* part = scratch + (size_t)(sh_id * tiles + t) * 256;
 #pragma unroll
         for (int r = 0; r < 4; ++r) part[(g + 4 * r) * 16 + j] = acc[r];
@@ -297,9 +277,10 @@ __device__ __forceinline__ void spec_gram_fast(const double* __restrict__ A, con
     __syncthreads();
 }
 
-__device__ void spec_ritz(SpecShared* sh, int p, double* out_re, double* out_im) {
-    // wave 0: eigenvalues of a copy of H (lanes share the row / column updates); lane 0 sorts them by
-    // descending magnitude
+// Eigenvalues of H (p x p) into out_re / out_im by descending magnitude; equal magnitudes by larger real part, then
+// by index.  All of it by wave 0: the lanes share the row / column updates of the eigensolve on a copy of H, and
+// rank_order's index i = lane stays inside the wave (p <= kMaxP < 64), so wave barriers order it.
+__device__ __noinline__ void spec_ritz(SpecShared* sh, int p, double* out_re, double* out_im) {
     if (threadIdx.x < 64) {
         for (int i = threadIdx.x; i < p * p; i += 64) sh->Hw[i] = sh->H[i];
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
@@ -308,26 +289,19 @@ __device__ void spec_ritz(SpecShared* sh, int p, double* out_re, double* out_im)
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
         __builtin_amdgcn_wave_barrier();
         if (rc && threadIdx.x == 0) sh->status = rc;
-    }
-    if (threadIdx.x == 0) {
-        for (int i = 0; i < p; ++i) {
-            const double a = sh->wr[i] * sh->wr[i] + sh->wi[i] * sh->wi[i];
-            int rank = 0;
-            for (int j = 0; j < p; ++j) {
-                const double b = sh->wr[j] * sh->wr[j] + sh->wi[j] * sh->wi[j];
-                rank += (b > a) || (b == a && (sh->wr[j] > sh->wr[i] || (sh->wr[j] == sh->wr[i] && j < i)));
-            }
-            sh->order[rank] = i;
-        }
-        for (int r = 0; r < p; ++r) { out_re[r] = sh->wr[sh->order[r]]; out_im[r] = sh->wi[sh->order[r]]; }
+        rank_order<true>(p, sh->order, [&](int i) { return sh->wr[i] * sh->wr[i] + sh->wi[i] * sh->wi[i]; },
+                         [&](int i) { return sh->wr[i]; });
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        for (int r = threadIdx.x; r < p; r += 64) { out_re[r] = sh->wr[sh->order[r]]; out_im[r] = sh->wi[sh->order[r]]; }
     }
     __syncthreads();
 }
 
 // ---- multi-workgroup driver --------------------------------------------------------------
 // One subspace-iteration step is  W = T'Z  (the only O(n^2 p) part: spread over the chip) followed
-// by a light single-workgroup step per matrix (sum of the row-split partials, and every few
-// steps Gram + Cholesky-QR; Rayleigh-Ritz / residuals / pi / implied timescales at the end).
+// by a light single-workgroup step per matrix (sum of the row-split partials, then Gram +
+// Cholesky-QR; Rayleigh-Ritz / residuals / pi / implied timescales at the end).
 // T is stochastic (|lambda| <= 1) so the basis needs no rescaling between orthogonalisations.
 constexpr int kSpecSplits = 16;       // most row splits of T per apply launch (fixed-order partial sums); a large batch
                                       // fills the chip without splitting and takes 1: a sixteenth of the partial-product
@@ -391,15 +365,13 @@ __device__ unsigned long long g_spec_stamps[8];
 #define SSTAMP_INIT
 #endif
 
-// mode bits
+// mode bits of spec_step_kernel: a launch seeds (kStepInit), orthonormalises (kStepOrtho, kStepTwice) or finishes
 constexpr int kStepInit = 1;     // seeded basis -> orthonormal Z (no partials involved)
 constexpr int kStepOrtho = 2;    // Z <- orth(W)
 constexpr int kStepTwice = 4;    // with kStepOrtho: a second Cholesky-QR pass over Z (the basis the Rayleigh-Ritz step gets
                                  // when the iterations ran on a power of T: one pass leaves ~cond(W)^2 eps of non-orthogonality)
 constexpr int kStepFinish = 8;   // Rayleigh-Ritz, residuals, pi, implied timescales
 
-// Z = W R^-1 for upper-triangular R (p x p in LDS): R^-1 by one wave (lane = column), then a
-// p-term dot product per element.
 // Cholesky factor R (upper, G = R'R) of the p x p Gram matrix (both in LDS, row stride p) by ONE wave: lane j keeps
 // column j of R in registers (compile-time indices through template recursion -- `#pragma unroll` with a break left the
 // arrays in scratch memory), the pivot-row elements come by v_readlane, and the dependent chain holds only the
@@ -476,7 +448,7 @@ __device__ __forceinline__ void spec_times_rinv(const double* Rinv, int p, const
         const int i0 = rb * 16;
         const bool rok = i0 + j < n;
         const int ri = rok ? i0 + j : 0;
-        spec_v4f64 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
+        v4f64 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
         for (int k0 = 0; k0 < p; k0 += 16) {
             double av[4], b0[4], b1[4];
 #pragma unroll
@@ -507,18 +479,33 @@ __device__ __forceinline__ void spec_times_rinv(const double* Rinv, int p, const
     __syncthreads();
 }
 
-__device__ __forceinline__ void spec_apply_rinv(SpecShared* sh, int p, const double* W, double* Z, int n) {
-    double* Rinv = sh->Hw;  // p x p
-    if (threadIdx.x < 64) rinv_wave(sh->R, sh->G, Rinv, p);
-    __syncthreads();
-    spec_times_rinv(Rinv, p, W, Z, n);
-}
-
-__device__ void spec_cholesky(SpecShared* sh, int p) {
-    if (threadIdx.x < 64) chol_wave(sh->G, sh->R, p);
+// The two one-wave steps of a Cholesky-QR pass, each followed by the workgroup's barrier (all in LDS, p x p, row
+// stride p).  Rpad: work space of kMaxP^2 doubles (the Gram matrix is no longer needed when the inverse is formed).
+__device__ __forceinline__ void cholesky(const double* G, double* R, int p) {
+    if (threadIdx.x < 64) chol_wave(G, R, p);
     __syncthreads();
 }
+// out of line for the three passes of spec_step_kernel: the unrolled factorisation is 29 KB of code
+__device__ __noinline__ void cholesky_call(const double* G, double* R, int p) { cholesky(G, R, p); }
+__device__ __forceinline__ void invert_upper(const double* R, double* Rpad, double* Rinv, int p) {
+    if (threadIdx.x < 64) rinv_wave(R, Rpad, Rinv, p);
+    __syncthreads();
+}
 
+// One Cholesky-QR pass: Z = W R^-1 with W'W = R'R, so Z'Z = I (Z may be W: spec_times_rinv).  G, R: kMaxP^2 doubles
+// of LDS each, scratch: 3 kMaxP^2 (Gram shares, then R^-1).  stamp(1..3) follows the Gram matrix, the factor and Z.
+struct no_stamp { __device__ __forceinline__ void operator()(int) const {} };
+template <typename Stamp = no_stamp>
+__device__ __forceinline__ void orthonormalise(double* G, double* R, double* scratch, const double* W, double* Z, int n,
+                                               int p, Stamp stamp = Stamp{}) {
+    spec_gram_fast(W, W, n, p, G, scratch);
+    stamp(1);
+    cholesky_call(G, R, p);
+    stamp(2);
+    invert_upper(R, G, scratch, p);
+    spec_times_rinv(scratch, p, W, Z, n);
+    stamp(3);
+}
 
 // ---- persistent driver: the subspace iterations of a matrix inside ONE launch ------------------------------
 // The loop above is two latency-bound launches per iteration (~77 us at n = 500: 3.9 ms for 50 iterations, 1.5 s for
@@ -569,11 +556,6 @@ struct PersistShared {     // (SpecShared carries 49 KB of Rayleigh-Ritz work sp
     double R[kMaxP * kMaxP];
     double Rinv[kMaxP * kMaxP];
 };
-
-__device__ __forceinline__ void persist_cholesky(PersistShared* sh, int p) {
-    if (threadIdx.x < 64) chol_wave(sh->G, sh->R, p);
-    __syncthreads();
-}
 
 __global__ __launch_bounds__(kSolveThreads) void spec_persist_kernel(SpecArgs ar, PersistArgs pa) {
     extern __shared__ __attribute__((aligned(16))) double plds[];
@@ -666,33 +648,31 @@ __global__ __launch_bounds__(kSolveThreads) void spec_persist_kernel(SpecArgs ar
                 sh.G[e] = v;
             }
             __syncthreads();
-          for (int pass = 0; pass < ((pa.twice && it == pa.n_iter - 1) ? 2 : 1); ++pass) {
-            if (pass == 1) {            // Gram matrix of the basis just formed: every member has all of it
-                for (int e = tid; e < p * p; e += kSolveThreads) {
-                    const int a = e / p, c = e - a * p;
-                    double v = 0.0;
-                    for (int i = 0; i < n; ++i) v = fma(Zl[i * ldz + a], Zl[i * ldz + c], v);
-                    sh.G[e] = v;
+            for (int pass = 0; pass < ((pa.twice && it == pa.n_iter - 1) ? 2 : 1); ++pass) {
+                if (pass == 1) {            // Gram matrix of the basis just formed: every member has all of it
+                    for (int e = tid; e < p * p; e += kSolveThreads) {
+                        const int a = e / p, c = e - a * p;
+                        double v = 0.0;
+                        for (int i = 0; i < n; ++i) v = fma(Zl[i * ldz + a], Zl[i * ldz + c], v);
+                        sh.G[e] = v;
+                    }
+                    __syncthreads();
+                }
+                cholesky(sh.G, sh.R, p);
+                invert_upper(sh.R, sh.G, sh.Rinv, p);
+                // Z = W R^-1, row by row in place (a thread owns a row: no hazard)
+                for (int i = tid; i < n; i += kSolveThreads) {
+                    double w[kMaxP];
+#pragma unroll
+                    for (int m = 0; m < kMaxP; ++m) w[m] = m < p ? Zl[i * ldz + m] : 0.0;
+                    for (int c = 0; c < p; ++c) {
+                        double v = 0.0;
+                        for (int m = 0; m <= c; ++m) v = fma(w[m], sh.Rinv[m * p + c], v);
+                        Zl[i * ldz + c] = v;
+                    }
                 }
                 __syncthreads();
             }
-            persist_cholesky(&sh, p);
-            double* Rinv = sh.Rinv;     // R^-1 by one wave (lane = column)
-            if (tid < 64) rinv_wave(sh.R, sh.G, Rinv, p);
-            __syncthreads();
-            // Z = W R^-1, row by row in place (a thread owns a row: no hazard)
-            for (int i = tid; i < n; i += kSolveThreads) {
-                double w[kMaxP];
-#pragma unroll
-                for (int m = 0; m < kMaxP; ++m) w[m] = m < p ? Zl[i * ldz + m] : 0.0;
-                for (int c = 0; c < p; ++c) {
-                    double v = 0.0;
-                    for (int m = 0; m <= c; ++m) v = fma(w[m], Rinv[m * p + c], v);
-                    Zl[i * ldz + c] = v;
-                }
-            }
-            __syncthreads();
-          }
         }
         // the finishing launch expects the orthonormal basis in bufA; the last exchange may still be read from there
         group_barrier(ctr, pa.G, epoch, pa.error);
@@ -703,9 +683,6 @@ __global__ __launch_bounds__(kSolveThreads) void spec_persist_kernel(SpecArgs ar
         group_barrier(ctr, pa.G, epoch, pa.error);   // nobody overwrites Tl / the Gram partials of a matrix still in use
     }
 }
-
-// Z <- Z R^-1 in place (a wave reads all of its 16 rows before it writes them)
-__device__ __forceinline__ void spec_apply_rinv_inplace(SpecShared* sh, int p, double* Z, int n) { spec_apply_rinv(sh, p, Z, Z, n); }
 
 // Complex Ritz pairs theta = a +- i b get a true residual like the real ones (their change between two launches was
 // the measure before: a solve with a complex pair among the watched values could not finish in one launch).  A pair whose
@@ -727,7 +704,285 @@ __device__ __forceinline__ void spec_complex_partner(const double* H, int p, dou
     __builtin_amdgcn_wave_barrier();
 }
 
-// Z: current (orthonormal unless between orthogonalisations) basis; Wb: the other buffer.
+// H y = theta y by one wave (small_eig::eigenvector_wave), out of line: the finish has seven call sites
+__device__ __noinline__ void ritz_eigenvector(const double* H, int p, double th_re, double* y, double* work, double th_im = 0.0) {
+    small_eig::eigenvector_wave(H, p, p, th_re, y, work, th_im);
+}
+
+// ---- the phases of spec_step_kernel, in the order it runs them (every thread of the workgroup calls each) ----------
+
+// what a finishing launch reports for an empty matrix
+__device__ __forceinline__ void finish_empty(const SpecArgs& ar, int b, double* ritz) {
+    if (threadIdx.x == 0) { ar.change[b] = 0.0; ar.status[b] = 0; }
+    for (int i = threadIdx.x; i < 4 * kMaxP; i += blockDim.x) ritz[i] = 0.0;
+    for (int i = threadIdx.x; i < ar.n_its; i += blockDim.x) {
+        ar.its_eig[(size_t)b * ar.n_its + i] = __builtin_nan("");
+        ar.its_ts[(size_t)b * ar.n_its + i] = __builtin_nan("");
+    }
+}
+
+// W = the starting block: a constant first column, the others uniform in [-1, 1) from a hash of (seed, element)
+__device__ __forceinline__ void seed_basis(unsigned long long seed, double* W, int n, int p) {
+    for (int e = threadIdx.x; e < n * p; e += blockDim.x) {
+        const int c = e % p;
+        double v;
+        if (c == 0) v = 1.0;
+        else {
+            unsigned long long h = seed + 0x9E3779B97F4A7C15ull * (unsigned long long)(e + 1);
+            h = (h ^ (h >> 30)) * 0xBF58476D1CE4E5B9ull;
+            h = (h ^ (h >> 27)) * 0x94D049BB133111EBull;
+            h ^= h >> 31;
+            v = (double)(h >> 11) * (2.0 / 9007199254740992.0) - 1.0;
+        }
+        W[e] = v;
+    }
+    __syncthreads();
+}
+
+// W[e] = sum over the row splits of part[split][e], e < np, in split order
+__device__ __forceinline__ void sum_partials(const double* __restrict__ part, size_t split_stride, int splits, double* W,
+                                             int np) {
+    int e = threadIdx.x;
+    if (splits == kSpecSplits) {
+        for (; e + (int)blockDim.x < np; e += 2 * blockDim.x) {  // 2 x kSpecSplits loads in flight
+            double v0[kSpecSplits], v1[kSpecSplits];
+#pragma unroll
+            for (int sp = 0; sp < kSpecSplits; ++sp) {
+                v0[sp] = part[sp * split_stride + e];
+                v1[sp] = part[sp * split_stride + e + blockDim.x];
+            }
+            double a0 = 0.0, a1 = 0.0;
+#pragma unroll
+            for (int sp = 0; sp < kSpecSplits; ++sp) { a0 += v0[sp]; a1 += v1[sp]; }
+            W[e] = a0;
+            W[e + blockDim.x] = a1;
+        }
+        for (; e < np; e += blockDim.x) {
+            double v = 0.0;
+#pragma unroll
+            for (int sp = 0; sp < kSpecSplits; ++sp) v += part[sp * split_stride + e];
+            W[e] = v;
+        }
+    } else {
+        // few splits (large batches: one): eight elements in flight per thread
+        for (; e + 7 * (int)blockDim.x < np; e += 8 * blockDim.x) {
+            double a[8];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) a[q] = part[e + q * blockDim.x];
+            for (int sp = 1; sp < splits; ++sp)
+#pragma unroll
+                for (int q = 0; q < 8; ++q) a[q] += part[sp * split_stride + e + q * blockDim.x];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) W[e + q * blockDim.x] = a[q];
+        }
+        for (; e < np; e += blockDim.x) {
+            double v = part[e];
+            for (int sp = 1; sp < splits; ++sp) v += part[sp * split_stride + e];
+            W[e] = v;
+        }
+    }
+    __syncthreads();
+}
+
+// Rayleigh-Ritz on the orthonormal basis Z with W = T'Z: H = Z'W, its eigenvalues into ritz [re | im] (zeros from p
+// on).  The values the previous call left become the "previous" ones (complex pairs are judged by their change
+// across calls: one small nonsymmetric eigensolve per call instead of two).
+__device__ __forceinline__ void rayleigh_ritz(SpecShared* sh, const double* Z, const double* W, int n, int p, double* ritz) {
+    for (int i = threadIdx.x; i < 2 * kMaxP; i += blockDim.x) ritz[2 * kMaxP + i] = ritz[i];
+    __syncthreads();
+    spec_gram_fast(Z, W, n, p, sh->H, sh->Hw);
+    spec_ritz(sh, p, ritz, ritz + kMaxP);
+    for (int i = p + threadIdx.x; i < kMaxP; i += blockDim.x) { ritz[i] = 0.0; ritz[kMaxP + i] = 0.0; }
+    __syncthreads();
+}
+
+// index (in wr / wi) of the eigenvalue nearest 1: the stationary distribution is its Ritz vector
+__device__ __forceinline__ int nearest_one(const SpecShared* sh, int p) {
+    int id = 0;
+    double bd = 1e300;
+    for (int i = 0; i < p; ++i) {
+        const double dr = sh->wr[i] - 1.0, di = sh->wi[i];
+        const double dd = dr * dr + di * di;
+        if (dd < bd) { bd = dd; id = i; }
+    }
+    return id;
+}
+
+// The Ritz vectors the finish needs (one per watched Ritz value, one for the stationary distribution) are inverse
+// iterations of ~50 us each by ONE wave: when their work space fits they run side by side on separate waves (7 vectors
+// at p = 12: 0.43 -> 0.1 ms for this launch), wave w into slot w of Hw; wider subspaces take them one after the other.
+constexpr int ritz_slot(int p) { return p * p + 3 * p; }   // [y p | work p p + 2 p] of one inverse iteration
+__device__ __forceinline__ void ritz_vectors_side_by_side(SpecShared* sh, int p, const double* ritz, int nw, int pi_id,
+                                                          bool want_pi) {
+    const int w = threadIdx.x >> 6;
+    double* u = sh->Hw + min(w, nw) * ritz_slot(p);
+    if (w < nw && ritz[kMaxP + w] == 0.0) ritz_eigenvector(sh->H, p, ritz[w], u, u + p);
+    else if (w < nw && spec_complex_ok(ritz[w], ritz[kMaxP + w])) {
+        ritz_eigenvector(sh->H, p, ritz[w], u, u + p, ritz[kMaxP + w]);
+        spec_complex_partner(sh->H, p, ritz[w], ritz[kMaxP + w], u, u + p);      // v into the (now free) work space
+    }
+    else if (w == nw && want_pi) ritz_eigenvector(sh->H, p, sh->wr[pi_id], u, u + p);
+    __syncthreads();
+}
+// The Ritz vector y of theta (H y = theta y; kComplex: [u p | v p], the real invariant plane of theta = re +- i im):
+// slot `slot` of the side-by-side run, else computed here by wave 0.
+template <bool kComplex = false>
+__device__ __forceinline__ const double* ritz_vector(SpecShared* sh, int p, bool side_by_side, int slot, double th_re,
+                                                     double th_im = 0.0) {
+    if (side_by_side) return sh->Hw + slot * ritz_slot(p);
+    if (threadIdx.x < 64) {
+        if constexpr (kComplex) {
+            ritz_eigenvector(sh->H, p, th_re, sh->y, sh->Hw + p, th_im);
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            for (int c = threadIdx.x; c < p; c += 64) sh->Hw[c] = sh->y[c];
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            spec_complex_partner(sh->H, p, th_re, th_im, sh->Hw, sh->Hw + p);
+        } else ritz_eigenvector(sh->H, p, th_re, sh->y, sh->Hw);
+    }
+    __syncthreads();
+    return kComplex ? sh->Hw : sh->y;
+}
+
+// Row i of x = Z y, and of t = W y when kWithT (T'x, as W = T'Z), for NV vectors y spaced p apart: one fma chain per
+// output over ascending c
+template <int NV> struct RowProjection { double x[NV], t[NV]; };
+template <int NV, bool kWithT>
+__device__ __forceinline__ RowProjection<NV> project_row(const double* Zi, const double* Wi, const double* y, int p) {
+    RowProjection<NV> r;
+#pragma unroll
+    for (int v = 0; v < NV; ++v) r.x[v] = r.t[v] = 0.0;
+    for (int c = 0; c < p; ++c) {
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+            r.x[v] = fma(Zi[c], y[v * p + c], r.x[v]);
+            if constexpr (kWithT) r.t[v] = fma(Wi[c], y[v * p + c], r.t[v]);
+        }
+    }
+    return r;
+}
+
+// ||T'x - theta x|| / ||x|| of a Ritz pair in real arithmetic: x = Z y for a real theta (NV = 1), x = Z (u + i v) with
+// y = [u p | v p] for theta = th_re + i th_im (NV = 2)
+template <int NV>
+__device__ __forceinline__ double pair_residual(SpecShared* sh, const double* Z, const double* W, int n, int p,
+                                                const double* y, double th_re, double th_im = 0.0) {
+    double rn = 0.0, xn = 0.0;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const auto r = project_row<NV, true>(Z + (size_t)i * p, W + (size_t)i * p, y, p);
+        if constexpr (NV == 1) {
+            const double d = r.t[0] - th_re * r.x[0];
+            rn = fma(d, d, rn);
+            xn = fma(r.x[0], r.x[0], xn);
+        } else {
+            const double rr = r.t[0] - (th_re * r.x[0] - th_im * r.x[1]), ri = r.t[1] - (th_im * r.x[0] + th_re * r.x[1]);
+            rn = fma(rr, rr, fma(ri, ri, rn));
+            xn = fma(r.x[0], r.x[0], fma(r.x[1], r.x[1], xn));
+        }
+    }
+    rn = block_sum_bcast(rn, sh->red, &sh->bc);
+    xn = block_sum_bcast(xn, sh->red, &sh->bc);
+    return sqrt(rn / fmax(xn, 1e-300));
+}
+// relative change of Ritz value wv since the previous call
+__device__ __forceinline__ double ritz_change(const double* ritz, int wv) {
+    const double th_re = ritz[wv], th_im = ritz[kMaxP + wv];
+    const double dr = th_re - ritz[2 * kMaxP + wv], di = th_im - ritz[3 * kMaxP + wv];
+    return sqrt(dr * dr + di * di) / fmax(sqrt(th_re * th_re + th_im * th_im), 1e-300);
+}
+
+// Convergence measure: the worst true residual ||T'x - theta x|| / ||x|| over the watched Ritz pairs.  (Changes of Ritz
+// values alone stagnate on clustered spectra and would stop too early.)  A complex pair's plane comes from the SQUARED
+// shifted matrix: with another eigenvalue very close to the pair its residual floors near eps / gap^2, so once there
+// is a previous call the smaller of residual and change counts; a pair that fails spec_complex_ok has the change alone.
+__device__ __forceinline__ double watched_residuals(SpecShared* sh, const double* Z, const double* W, int n, int p,
+                                                    const double* ritz, int nw, bool side_by_side, bool init) {
+    double worst = 0.0;
+    for (int wv = 0; wv < nw; ++wv) {
+        const double th_re = ritz[wv], th_im = ritz[kMaxP + wv];
+        double res;
+        if (th_im == 0.0) res = pair_residual<1>(sh, Z, W, n, p, ritz_vector(sh, p, side_by_side, wv, th_re), th_re);
+        else if (spec_complex_ok(th_re, th_im)) {
+            res = pair_residual<2>(sh, Z, W, n, p, ritz_vector<true>(sh, p, side_by_side, wv, th_re, th_im), th_re, th_im);
+            if (!init) res = fmin(res, ritz_change(ritz, wv));
+        } else res = init ? 1.0 : ritz_change(ritz, wv);   // no history yet
+        worst = fmax(worst, res);
+    }
+    return worst;
+}
+
+// pi = Z y scaled to sum 1, y the Ritz vector of the eigenvalue nearest 1
+__device__ __forceinline__ void stationary_distribution(SpecShared* sh, const double* Z, int n, int p, const double* y,
+                                                        double* pi) {
+    double part = 0.0;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const double v = project_row<1, false>(Z + (size_t)i * p, nullptr, y, p).x[0];
+        pi[i] = v;
+        part += v;
+    }
+    const double tot = block_sum_bcast(part, sh->red, &sh->bc);
+    for (int i = threadIdx.x; i < n; i += blockDim.x) pi[i] = pi[i] / tot;
+}
+
+// leading left eigenvectors (x' T = theta x'), Ritz values by descending magnitude, equal ones by index (the order
+// deeptime's eigenvectors() returns); unit 2-norm, the component of largest magnitude (lowest index on ties)
+// positive; NaN for a complex pair or beyond the subspace.  vecs: [n_vecs][ld]
+__device__ __forceinline__ void left_vectors(SpecShared* sh, const double* Z, int n, int p, double* vecs, int n_vecs, int ld) {
+    rank_order<true>(p, sh->order, [&](int i) { return sh->wr[i] * sh->wr[i] + sh->wi[i] * sh->wi[i]; });
+    __syncthreads();
+    for (int q = 0; q < n_vecs; ++q) {
+        double* out = vecs + (size_t)q * ld;
+        const int id = q < p ? sh->order[q] : -1;
+        if (id < 0 || sh->wi[id] != 0.0) {
+            for (int i = threadIdx.x; i < n; i += blockDim.x) out[i] = __builtin_nan("");
+            continue;
+        }
+        __syncthreads();
+        const double* y = ritz_vector(sh, p, false, 0, sh->wr[id]);
+        double nn = 0.0, big = 0.0;
+        for (int i = threadIdx.x; i < n; i += blockDim.x) {
+            const double v = project_row<1, false>(Z + (size_t)i * p, nullptr, y, p).x[0];
+            out[i] = v;
+            nn = fma(v, v, nn);
+            big = fmax(big, fabs(v));
+        }
+        nn = block_sum_bcast(nn, sh->red, &sh->bc);
+        big = block_max_bcast(big, sh->red, &sh->bc);
+        double first = -(double)n;                       // -(lowest index that attains the maximum)
+        for (int i = threadIdx.x; i < n; i += blockDim.x)
+            if (fabs(out[i]) == big) { first = -(double)i; break; }
+        first = block_max_bcast(first, sh->red, &sh->bc);
+        const int lead = min(n - 1, max(0, (int)(-first)));
+        const double scale = (out[lead] < 0.0 ? -1.0 : 1.0) / sqrt(fmax(nn, 1e-300));
+        __syncthreads();                                 // every thread has read out[lead]
+        for (int i = threadIdx.x; i < n; i += blockDim.x) out[i] *= scale;
+    }
+    __syncthreads();
+}
+
+// implied timescales (_its.py:543-604 on one matrix; utils.py:17-57): the top n_its + 1 Ritz values by magnitude,
+// re-sorted by descending real part (equal ones by index), without the first
+__device__ __forceinline__ void implied_timescales(SpecShared* sh, const double* ritz, int p, int n_its, double lag,
+                                                   double* its_eig, double* its_ts) {
+    const int kreq = min(n_its + 1, p);
+    rank_order<true>(kreq, sh->order, [&](int i) { return ritz[i]; });
+    __syncthreads();
+    for (int i = threadIdx.x; i < n_its; i += blockDim.x) {
+        double ev = __builtin_nan(""), ts = __builtin_nan("");
+        if (i + 1 < kreq) {
+            ev = fabs(ritz[sh->order[i + 1]]);
+            ev = fmin(fmax(ev, 1e-12), 1.0 - 1e-12);
+            ts = -fmax(1.0, lag) / log(ev);
+        }
+        its_eig[i] = ev;
+        its_ts[i] = ts;
+    }
+}
+
+// One launch of the loop per matrix: seed the basis (kStepInit), or sum the partials of W = T'Z and orthonormalise
+// (kStepOrtho, twice with kStepTwice), or sum them and finish (kStepFinish).  Zall: the orthonormal basis; Wall: the
+// other buffer, which holds W when it does not fit the LDS.
 template <bool lds_w>
 __global__ __launch_bounds__(kSolveThreads) void spec_step_kernel(SpecArgs ar, int mode, double* __restrict__ Zall,
                                                                  double* __restrict__ Wall,
@@ -739,24 +994,16 @@ __global__ __launch_bounds__(kSolveThreads) void spec_step_kernel(SpecArgs ar, i
     const int tid = threadIdx.x;
     const int n = ar.n_ptr ? ar.n_ptr[b] : ar.n_fixed;
     double* Z = Zall + (size_t)b * ar.zw_stride;
-    double* Wg = Wall + (size_t)b * ar.zw_stride;
     // A lone workgroup pays ~2 us for every dependent trip to memory another XCD has just
     // written: W = T'Z is summed into LDS in one round of loads and stays there for the Gram
     // matrix, the triangular solve and the residuals.
-    double* W = lds_w ? w_lds : Wg;
+    double* W = lds_w ? w_lds : Wall + (size_t)b * ar.zw_stride;
     double* ritz = ar.ritz + (size_t)b * 4 * kMaxP;
     if (spec_frozen(ar, b)) return;   // uniform over the workgroup; outputs of the previous call stand
     if (tid == 0) sh.status = 0;
     __syncthreads();
     if (n <= 0) {
-        if (mode & kStepFinish) {
-            if (tid == 0) { ar.change[b] = 0.0; ar.status[b] = 0; }
-            for (int i = tid; i < 4 * kMaxP; i += blockDim.x) ritz[i] = 0.0;
-            for (int i = tid; i < ar.n_its; i += blockDim.x) {
-                ar.its_eig[(size_t)b * ar.n_its + i] = __builtin_nan("");
-                ar.its_ts[(size_t)b * ar.n_its + i] = __builtin_nan("");
-            }
-        }
+        if (mode & kStepFinish) finish_empty(ar, b, ritz);
         return;
     }
     const int p = min(ar.p, n);
@@ -765,303 +1012,39 @@ __global__ __launch_bounds__(kSolveThreads) void spec_step_kernel(SpecArgs ar, i
     // Cholesky-QR breaks down (NaN Ritz values, "hqr did not converge").  The seeded basis stays as it is until the finish.
     if (p == n && !(mode & (kStepInit | kStepFinish))) return;
     if (mode & kStepInit) {
-        for (int e = tid; e < n * p; e += blockDim.x) {
-            const int c = e % p;
-            double v;
-            if (c == 0) v = 1.0;
-            else {
-                unsigned long long h = ar.seed + 0x9E3779B97F4A7C15ull * (unsigned long long)(e + 1);
-                h = (h ^ (h >> 30)) * 0xBF58476D1CE4E5B9ull;
-                h = (h ^ (h >> 27)) * 0x94D049BB133111EBull;
-                h ^= h >> 31;
-                v = (double)(h >> 11) * (2.0 / 9007199254740992.0) - 1.0;
-            }
-            W[e] = v;
-        }
-        __syncthreads();
-        spec_gram_fast(W, W, n, p, sh.G, sh.Hw);
-        spec_cholesky(&sh, p);
-        spec_apply_rinv(&sh, p, W, Z, n);
+        seed_basis(ar.seed, W, n, p);
+        orthonormalise(sh.G, sh.R, sh.Hw, W, Z, n, p);
         return;
     }
     SSTAMP_INIT
-    // W = sum of the row-split partials, fixed order
-    {
-        const double* part = partial_all + (size_t)b * part_stride;
-        const size_t split_stride = (size_t)ar.n_fixed * ar.p;
-        int e = tid;
-        if (ar.splits == kSpecSplits) {
-            for (; e + (int)blockDim.x < n * p; e += 2 * blockDim.x) {  // 2 x kSpecSplits loads in flight
-                double v0[kSpecSplits], v1[kSpecSplits];
-#pragma unroll
-                for (int sp = 0; sp < kSpecSplits; ++sp) {
-                    v0[sp] = part[sp * split_stride + e];
-                    v1[sp] = part[sp * split_stride + e + blockDim.x];
-                }
-                double a0 = 0.0, a1 = 0.0;
-#pragma unroll
-                for (int sp = 0; sp < kSpecSplits; ++sp) { a0 += v0[sp]; a1 += v1[sp]; }
-                W[e] = a0;
-                W[e + blockDim.x] = a1;
-            }
-            for (; e < n * p; e += blockDim.x) {
-                double v = 0.0;
-#pragma unroll
-                for (int sp = 0; sp < kSpecSplits; ++sp) v += part[sp * split_stride + e];
-                W[e] = v;
-            }
-        } else {
-            // few splits (large batches: one): eight elements in flight per thread
-            for (; e + 7 * (int)blockDim.x < n * p; e += 8 * blockDim.x) {
-                double a[8];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) a[q] = part[e + q * blockDim.x];
-                for (int sp = 1; sp < ar.splits; ++sp)
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) a[q] += part[sp * split_stride + e + q * blockDim.x];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) W[e + q * blockDim.x] = a[q];
-            }
-            for (; e < n * p; e += blockDim.x) {
-                double v = part[e];
-                for (int sp = 1; sp < ar.splits; ++sp) v += part[sp * split_stride + e];
-                W[e] = v;
-            }
-        }
-        __syncthreads();
-        if (lds_w && !(mode & (kStepOrtho | kStepFinish))) {  // plain power step: the next apply reads global
-            for (int q = tid; q < n * p; q += blockDim.x) Wg[q] = W[q];
-        }
-    }
+    sum_partials(partial_all + (size_t)b * part_stride, (size_t)ar.n_fixed * ar.p, ar.splits, W, n * p);
     SSTAMP(0);
     if (mode & kStepOrtho) {
-        spec_gram_fast(W, W, n, p, sh.G, sh.Hw);
-        SSTAMP(1);
-        spec_cholesky(&sh, p);
-        SSTAMP(2);
-        spec_apply_rinv(&sh, p, W, Z, n);
-        SSTAMP(3);
-        if (mode & kStepTwice) {
-            spec_gram_fast(Z, Z, n, p, sh.G, sh.Hw);
-            spec_cholesky(&sh, p);
-            spec_apply_rinv_inplace(&sh, p, Z, n);
-        }
+        orthonormalise(sh.G, sh.R, sh.Hw, W, Z, n, p, [&](int slot) { SSTAMP(slot); });
+        if (mode & kStepTwice) orthonormalise(sh.G, sh.R, sh.Hw, Z, Z, n, p);
     }
-    if (!(mode & kStepFinish)) {
-        if (tid == 0 && sh.status) ar.status[b] = sh.status;
-        return;
-    }
-    // ---- Rayleigh-Ritz on the (orthonormal) basis Z with W = T'Z.  The values the previous call left
-    // become the "previous" ones (complex pairs are judged by their change across calls: one small
-    // nonsymmetric eigensolve per call instead of two).
-    for (int i = tid; i < 2 * kMaxP; i += blockDim.x) ritz[2 * kMaxP + i] = ritz[i];
-    __syncthreads();
-    spec_gram_fast(Z, W, n, p, sh.H, sh.Hw);
-    spec_ritz(&sh, p, ritz, ritz + kMaxP);
-    for (int i = p + tid; i < kMaxP; i += blockDim.x) { ritz[i] = 0.0; ritz[kMaxP + i] = 0.0; }
-    __syncthreads();
-    // Convergence measure: the true residual ||T'x - theta x|| / ||x|| of every watched REAL
-    // Ritz pair (x = Z y, T'x = W y); for complex values, the change since the last check.
-    // (Changes of Ritz values alone stagnate on clustered spectra and would stop too early.)
-    // The Ritz vectors these steps need (one per watched real Ritz value, one for the stationary distribution) are
-    // inverse iterations of ~50 us each by ONE wave: when their work space fits they run side by side on separate
-    // waves (7 vectors at p = 12: 0.43 -> 0.1 ms for this launch); wider subspaces take them one after the other.
-    const int nw = min(ar.n_watch, p);
-    const int per = p * p + 3 * p;                          // [y p | work p p + 2 p] of one inverse iteration
-    const bool side_by_side = (nw + 1) * per <= 3 * kMaxP * kMaxP && nw + 1 <= (int)(blockDim.x >> 6);
-    int pi_id = 0;
-    {
-        double bd = 1e300;
-        for (int i = 0; i < p; ++i) {
-            const double dr = sh.wr[i] - 1.0, di = sh.wi[i];
-            const double dd = dr * dr + di * di;
-            if (dd < bd) { bd = dd; pi_id = i; }
-        }
-    }
-    if (side_by_side) {
-        const int w = tid >> 6;
-        if (w < nw && ritz[kMaxP + w] == 0.0)
-            small_eig::eigenvector_wave(sh.H, p, p, ritz[w], sh.Hw + w * per, sh.Hw + w * per + p);
-        else if (w < nw && spec_complex_ok(ritz[w], ritz[kMaxP + w])) {
-            double* u = sh.Hw + w * per;
-            small_eig::eigenvector_wave(sh.H, p, p, ritz[w], u, u + p, ritz[kMaxP + w]);
-            spec_complex_partner(sh.H, p, ritz[w], ritz[kMaxP + w], u, u + p);      // v into the (now free) work space
-        }
-        else if (w == nw && ar.pi)
-            small_eig::eigenvector_wave(sh.H, p, p, sh.wr[pi_id], sh.Hw + w * per, sh.Hw + w * per + p);
-        __syncthreads();
-    }
-    {
-        double worst = 0.0;
-        for (int wv = 0; wv < nw; ++wv) {
-            const double th_re = ritz[wv], th_im = ritz[kMaxP + wv];
-            if (th_im != 0.0) {
-                if (spec_complex_ok(th_re, th_im)) {
-                    // true residual of the complex pair x = Z (u + i v):  T'x - theta x  in real arithmetic
-                    const double* uv = sh.Hw + wv * per;       // [u p | v p]
-                    if (!side_by_side) {
-                        if (tid < 64) {
-                            small_eig::eigenvector_wave(sh.H, p, p, th_re, sh.y, sh.Hw + p, th_im);
-                            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                            __builtin_amdgcn_wave_barrier();
-                            for (int c = tid; c < p; c += 64) sh.Hw[c] = sh.y[c];
-                            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                            __builtin_amdgcn_wave_barrier();
-                            spec_complex_partner(sh.H, p, th_re, th_im, sh.Hw, sh.Hw + p);
-                        }
-                        __syncthreads();
-                        uv = sh.Hw;
-                    }
-                    double rn = 0.0, xn = 0.0;
-                    for (int i = tid; i < n; i += blockDim.x) {
-                        double xr = 0.0, xi = 0.0, tr = 0.0, ti = 0.0;
-                        for (int c = 0; c < p; ++c) {
-                            const double z = Z[(size_t)i * p + c], w_ = W[(size_t)i * p + c];
-                            xr = fma(z, uv[c], xr);
-                            xi = fma(z, uv[p + c], xi);
-                            tr = fma(w_, uv[c], tr);
-                            ti = fma(w_, uv[p + c], ti);
-                        }
-                        const double rr = tr - (th_re * xr - th_im * xi), ri = ti - (th_im * xr + th_re * xi);
-                        rn = fma(rr, rr, fma(ri, ri, rn));
-                        xn = fma(xr, xr, fma(xi, xi, xn));
-                    }
-                    rn = block_sum_bcast(rn, sh.red, &sh.bc);
-                    xn = block_sum_bcast(xn, sh.red, &sh.bc);
-                    // (the plane comes from the SQUARED shifted matrix: with another eigenvalue very close to the pair
-                    // its residual floors near eps / gap^2; the change between launches then still decides)
-                    double res = sqrt(rn / fmax(xn, 1e-300));
-                    if (!ar.init) {
-                        const double dr = th_re - ritz[2 * kMaxP + wv], di = th_im - ritz[3 * kMaxP + wv];
-                        res = fmin(res, sqrt(dr * dr + di * di) / fmax(sqrt(th_re * th_re + th_im * th_im), 1e-300));
-                    }
-                    worst = fmax(worst, res);
-                    continue;
-                }
-                const double dr = th_re - ritz[2 * kMaxP + wv], di = th_im - ritz[3 * kMaxP + wv];
-                const double mag = sqrt(th_re * th_re + th_im * th_im);
-                const double ch = ar.init ? 1.0 : sqrt(dr * dr + di * di) / fmax(mag, 1e-300);   // no history yet
-                worst = fmax(worst, ch);
-                continue;
-            }
-            const double* yv = sh.y;
-            if (side_by_side) yv = sh.Hw + wv * per;
-            else {
-                if (tid < 64) small_eig::eigenvector_wave(sh.H, p, p, th_re, sh.y, sh.Hw);
-                __syncthreads();
-            }
-            double rn = 0.0, xn = 0.0;
-            for (int i = tid; i < n; i += blockDim.x) {
-                double xv = 0.0, tv = 0.0;
-                for (int c = 0; c < p; ++c) {
-                    xv = fma(Z[(size_t)i * p + c], yv[c], xv);
-                    tv = fma(W[(size_t)i * p + c], yv[c], tv);
-                }
-                const double r = tv - th_re * xv;
-                rn = fma(r, r, rn);
-                xn = fma(xv, xv, xn);
-            }
-            rn = block_sum_bcast(rn, sh.red, &sh.bc);
-            xn = block_sum_bcast(xn, sh.red, &sh.bc);
-            worst = fmax(worst, sqrt(rn / fmax(xn, 1e-300)));
-        }
+    if (mode & kStepFinish) {
+        rayleigh_ritz(&sh, Z, W, n, p, ritz);
+        const int nw = min(ar.n_watch, p), pi_id = nearest_one(&sh, p);
+        const bool side_by_side = (nw + 1) * ritz_slot(p) <= 3 * kMaxP * kMaxP && nw + 1 <= (int)(blockDim.x >> 6);
+        if (side_by_side) ritz_vectors_side_by_side(&sh, p, ritz, nw, pi_id, ar.pi != nullptr);
+        const double worst = watched_residuals(&sh, Z, W, n, p, ritz, nw, side_by_side, ar.init != 0);
         if (tid == 0) ar.change[b] = worst;
-    }
-    __syncthreads();
-    // stationary distribution: Ritz vector of the eigenvalue nearest 1
-    if (ar.pi) {
-        const double* yv = sh.y;
-        if (side_by_side) yv = sh.Hw + nw * per;
-        else {
-            if (tid < 64) small_eig::eigenvector_wave(sh.H, p, p, sh.wr[pi_id], sh.y, sh.Hw);
-            __syncthreads();
-        }
-        double* pi = ar.pi + (size_t)b * ar.pi_stride;
-        double part = 0.0;
-        for (int i = tid; i < n; i += blockDim.x) {
-            double v = 0.0;
-            for (int c = 0; c < p; ++c) v = fma(Z[(size_t)i * p + c], yv[c], v);
-            pi[i] = v;
-            part += v;
-        }
-        const double tot = block_sum_bcast(part, sh.red, &sh.bc);
-        for (int i = tid; i < n; i += blockDim.x) pi[i] = pi[i] / tot;
-    }
-    __syncthreads();
-    // leading left eigenvectors (x' T = theta x'), Ritz values by descending magnitude (the order
-    // deeptime's eigenvectors() returns); unit 2-norm, the component of largest magnitude (lowest
-    // index on ties) positive; NaN for a complex pair or beyond the subspace
-    if (ar.vecs && ar.n_vecs > 0) {
-        if (tid == 0) {
-            for (int i = 0; i < p; ++i) {
-                const double mi = sh.wr[i] * sh.wr[i] + sh.wi[i] * sh.wi[i];
-                int rank = 0;
-                for (int j = 0; j < p; ++j) {
-                    const double mj = sh.wr[j] * sh.wr[j] + sh.wi[j] * sh.wi[j];
-                    rank += (mj > mi) || (mj == mi && j < i);
-                }
-                sh.order[rank] = i;
-            }
-        }
         __syncthreads();
-        for (int q = 0; q < ar.n_vecs; ++q) {
-            double* out = ar.vecs + ((size_t)b * ar.n_vecs + q) * ar.n_fixed;
-            const int id = q < p ? sh.order[q] : -1;
-            if (id < 0 || sh.wi[id] != 0.0) {
-                for (int i = tid; i < n; i += blockDim.x) out[i] = __builtin_nan("");
-                continue;
-            }
-            __syncthreads();
-            if (tid < 64) small_eig::eigenvector_wave(sh.H, p, p, sh.wr[id], sh.y, sh.Hw);
-            __syncthreads();
-            double nn = 0.0, big = 0.0;
-            for (int i = tid; i < n; i += blockDim.x) {
-                double v = 0.0;
-                for (int c = 0; c < p; ++c) v = fma(Z[(size_t)i * p + c], sh.y[c], v);
-                out[i] = v;
-                nn = fma(v, v, nn);
-                big = fmax(big, fabs(v));
-            }
-            nn = block_sum_bcast(nn, sh.red, &sh.bc);
-            big = block_max_bcast(big, sh.red, &sh.bc);
-            double first = -(double)n;                       // -(lowest index that attains the maximum)
-            for (int i = tid; i < n; i += blockDim.x)
-                if (fabs(out[i]) == big) { first = -(double)i; break; }
-            first = block_max_bcast(first, sh.red, &sh.bc);
-            const int lead = min(n - 1, max(0, (int)(-first)));
-            const double scale = (out[lead] < 0.0 ? -1.0 : 1.0) / sqrt(fmax(nn, 1e-300));
-            __syncthreads();                                 // every thread has read out[lead]
-            for (int i = tid; i < n; i += blockDim.x) out[i] *= scale;
-        }
+        if (ar.pi)
+            stationary_distribution(&sh, Z, n, p, ritz_vector(&sh, p, side_by_side, nw, sh.wr[pi_id]),
+                                    ar.pi + (size_t)b * ar.pi_stride);
         __syncthreads();
-    }
-    // implied timescales (_its.py:543-604 on one matrix; utils.py:17-57)
-    if (ar.n_its > 0 && tid == 0) {
-        const int n_its = ar.n_its;
-        const int kreq = min(n_its + 1, p);
-        // top kreq by magnitude are ritz[0..kreq); re-sort by descending real part
-        int idx[kMaxP];
-        for (int i = 0; i < kreq; ++i) {
-            int rank = 0;
-            for (int j = 0; j < kreq; ++j) rank += (ritz[j] > ritz[i]) || (ritz[j] == ritz[i] && j < i);
-            idx[rank] = i;
-        }
-        const double lag = ar.lags ? ar.lags[b] : 1.0;
-        for (int i = 0; i < n_its; ++i) {
-            double ev = __builtin_nan(""), ts = __builtin_nan("");
-            if (i + 1 < kreq) {
-                ev = fabs(ritz[idx[i + 1]]);
-                ev = fmin(fmax(ev, 1e-12), 1.0 - 1e-12);
-                ts = -fmax(1.0, lag) / log(ev);
-            }
-            ar.its_eig[(size_t)b * n_its + i] = ev;
-            ar.its_ts[(size_t)b * n_its + i] = ts;
-        }
+        if (ar.vecs && ar.n_vecs > 0)
+            left_vectors(&sh, Z, n, p, ar.vecs + (size_t)b * ar.n_vecs * ar.n_fixed, ar.n_vecs, ar.n_fixed);
+        if (ar.n_its > 0)
+            implied_timescales(&sh, ritz, p, ar.n_its, ar.lags ? ar.lags[b] : 1.0, ar.its_eig + (size_t)b * ar.n_its,
+                               ar.its_ts + (size_t)b * ar.n_its);
     }
     if (tid == 0 && sh.status) ar.status[b] = sh.status;
-    if (tid == 0 && ar.persist_error && *ar.persist_error) ar.status[b] = 777;   // a group barrier of the persistent launch timed out
+    // a group barrier of the persistent launch timed out
+    if ((mode & kStepFinish) && tid == 0 && ar.persist_error && *ar.persist_error) ar.status[b] = 777;
 }
-
 
 // ---- powers of the transition matrices (the iteration operator of msm_spectrum) -----------------------------------
 // C_b = A_b A_b for a batch of packed square matrices of order n_b <= n_fixed (row stride ld), on the fp64 matrix
@@ -1083,7 +1066,6 @@ __global__ __launch_bounds__(256) void square_batch_kernel(const double* __restr
     double* Cb = C + (size_t)b * stride;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int j = lane & 15, g = lane >> 4;
-    typedef double v4f64 __attribute__((ext_vector_type(4)));
     v4f64 acc[4];
 #pragma unroll
     for (int ct = 0; ct < 4; ++ct) acc[ct] = v4f64{0.0, 0.0, 0.0, 0.0};
@@ -1132,23 +1114,24 @@ msm_status msm_transition_matrix(msm_ctx* ctx, const void* d_counts, int counts_
     msm_status rs = msm_reserve_scratch(ctx, (size_t)k * sizeof(double));
     if (rs != MSM_OK) return rs;
     double* colsum = (double*)ctx->scratch;
+    // the count type, picked once: launch(CT{}) with CT = double or long long
+    auto with_count_type = [&](auto launch) {
+        if (counts_are_f64) launch(double{});
+        else launch((long long)0);
+    };
     if (mode == 0 && ctx->km_stats) {        // one launch (the scratch holds the diagonal instead of the column sums)
         unsigned int* ticket = (unsigned int*)ctx->km_stats + 3;
-        if (counts_are_f64)
-            hipLaunchKernelGGL(row_normalise_kernel<double>, dim3(k), dim3(kThreads), 0, ctx->stream, (const double*)d_counts, k,
-                               d_rowsum, d_T, colsum, ticket, d_diag_mass);
-        else
-            hipLaunchKernelGGL(row_normalise_kernel<long long>, dim3(k), dim3(kThreads), 0, ctx->stream,
-                               (const long long*)d_counts, k, d_rowsum, d_T, colsum, ticket, d_diag_mass);
+        with_count_type([&](auto ct) {
+            hipLaunchKernelGGL(row_normalise_kernel<decltype(ct)>, dim3(k), dim3(kThreads), 0, ctx->stream,
+                               (const decltype(ct)*)d_counts, k, d_rowsum, d_T, colsum, ticket, d_diag_mass);
+        });
         MSM_CHECK_LAUNCH(ctx);
         return MSM_OK;
     }
-    if (counts_are_f64)
-        hipLaunchKernelGGL(rowcol_sums_kernel<double>, dim3(k), dim3(kThreads), 0, ctx->stream, (const double*)d_counts, k,
-                           d_rowsum, colsum);
-    else
-        hipLaunchKernelGGL(rowcol_sums_kernel<long long>, dim3(k), dim3(kThreads), 0, ctx->stream,
-                           (const long long*)d_counts, k, d_rowsum, colsum);
+    with_count_type([&](auto ct) {
+        hipLaunchKernelGGL(rowcol_sums_kernel<decltype(ct)>, dim3(k), dim3(kThreads), 0, ctx->stream,
+                           (const decltype(ct)*)d_counts, k, d_rowsum, colsum);
+    });
     MSM_CHECK_LAUNCH(ctx);
     if (mode == 1) {
         hipLaunchKernelGGL(active_set_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_rowsum, colsum, k, epsilon, 0,
@@ -1156,12 +1139,10 @@ msm_status msm_transition_matrix(msm_ctx* ctx, const void* d_counts, int counts_
         MSM_CHECK_LAUNCH(ctx);
         MSM_HIP(ctx, hipMemsetAsync(d_T, 0, (size_t)k * k * sizeof(double), ctx->stream));
     }
-    if (counts_are_f64)
-        hipLaunchKernelGGL(build_T_kernel<double>, dim3(k), dim3(kThreads), 0, ctx->stream, (const double*)d_counts, k,
-                           mode, alpha, d_rowsum, d_active, d_n_active, d_T);
-    else
-        hipLaunchKernelGGL(build_T_kernel<long long>, dim3(k), dim3(kThreads), 0, ctx->stream,
-                           (const long long*)d_counts, k, mode, alpha, d_rowsum, d_active, d_n_active, d_T);
+    with_count_type([&](auto ct) {
+        hipLaunchKernelGGL(build_T_kernel<decltype(ct)>, dim3(k), dim3(kThreads), 0, ctx->stream,
+                           (const decltype(ct)*)d_counts, k, mode, alpha, d_rowsum, d_active, d_n_active, d_T);
+    });
     MSM_CHECK_LAUNCH(ctx);
     if (d_diag_mass && mode == 0) {
         hipLaunchKernelGGL(diag_mass_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_T, k, d_diag_mass);
@@ -1215,6 +1196,107 @@ msm_status msm_matrix_power(msm_ctx* ctx, const double* d_T, int64_t t_stride, i
     return MSM_OK;
 }
 
+// The persistent launch of a shape; tests/_spectrum_ref.spectrum_path restates this rule line for line.
+struct PersistPlan {
+    int first_cols;     // columns of T per member the LDS budget allows (below 8: no persistent launch)
+    int cols, G;        // columns per member after evening the shares out, members per group
+    int groups, slots;  // groups (0: the batch is too large for one group per matrix), groups per XCD in use
+    size_t lds_bytes;
+    bool resident;      // at most one workgroup per CU
+};
+static PersistPlan plan_persist(int n_max, int p, int batch, int n_cu) {
+    const size_t budget = (size_t)(160 - 24 - 4) * 1024 / sizeof(double);   // LDS less PersistShared and slack
+    const size_t fixed = (size_t)n_max * (p | 1);
+    int cols = budget > fixed + (size_t)8 * (n_max + p + 2) ? (int)((budget - fixed) / (size_t)(n_max + p + 2)) : 0;
+    cols = std::min(cols, n_max);
+    auto fits = [&](int c) { return (size_t)n_max * (c | 1) + fixed + (size_t)c * p <= budget; };
+    while (cols >= 8 && !fits(cols)) --cols;
+    PersistPlan pl = {};
+    pl.first_cols = cols;
+    if (cols >= 8) {
+        const int G = (n_max + cols - 1) / cols;
+        while (cols > 1 && (n_max + cols - 2) / (cols - 1) == G && fits(cols - 1)) --cols;   // even shares: the fewest columns that keep G
+        // a group lives on one XCD (32 CUs): G <= 32; groups per XCD = 32 / G, eight XCDs
+        const int per_xcd = G <= 32 ? 32 / G : 0;
+        // Only when every matrix gets a group at once: a large batch (a lag scan with posterior samples) already
+        // fills the chip with independent single-workgroup steps, and a group per matrix would serialise it.
+        const int groups = batch <= 8 * per_xcd ? batch : 0;
+        const int slots = (groups + 7) / 8;          // group q = slot * 8 + xcd
+        pl.cols = cols; pl.G = G; pl.groups = groups; pl.slots = slots;
+        pl.lds_bytes = ((size_t)n_max * (cols | 1) + (size_t)n_max * (p | 1) + (size_t)cols * p) * sizeof(double);
+        pl.resident = slots * G * 8 <= n_cu;
+    }
+    return pl;
+}
+
+// All n_iter iterations in one launch of spec_persist_kernel.  *error is set to the kernel's barrier-timeout flag when
+// the launch persisted and left alone when it did not (not resident together on this device / in this state: the
+// caller runs the launch loop).
+static msm_status launch_persist(msm_ctx* ctx, const PersistPlan& pl, const SpecArgs& ar_it, int n_max, int p, int batch,
+                                 int n_iter, bool twice, double* bufA, double* bufB, const int** error) {
+    const size_t gram_bytes = (size_t)pl.groups * 2 * pl.G * kMaxP * kMaxP * sizeof(double);
+    msm_status rs = msm_reserve_aux(ctx, gram_bytes + (size_t)pl.groups * sizeof(unsigned) + 64);
+    if (rs != MSM_OK) return rs;
+    PersistArgs pa;
+    pa.gram = (double*)ctx->aux;
+    pa.counters = (unsigned*)((char*)ctx->aux + gram_bytes);
+    pa.error = (int*)(pa.counters + pl.groups);
+    pa.G = pl.G; pa.groups = pl.groups; pa.cols = pl.cols; pa.batch = batch; pa.n_iter = n_iter;
+    pa.twice = twice ? 1 : 0;
+    pa.bufA = bufA; pa.bufB = bufB;
+    MSM_HIP(ctx, hipMemsetAsync(pa.counters, 0, (size_t)pl.groups * sizeof(unsigned) + sizeof(int), ctx->stream));
+    MSM_HIP(ctx, hipFuncSetAttribute((const void*)spec_persist_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)pl.lds_bytes));
+    // Residency: the barriers need every workgroup of the grid on a CU at once.  The grid is at most one
+    // workgroup per CU (checked here against the occupancy the runtime reports), the stream is in order, and a
+    // barrier that is not met within ~1 s raises the error flag instead of spinning on; a plain launch is
+    // used because rocprofv3 crashes at exit of a process that made a cooperative launch (MSM_SPEC_COOP=1
+    // asks for hipLaunchCooperativeKernel all the same).
+    const unsigned grid = (unsigned)(pl.slots * pl.G * 8);
+    int per_cu = 0;
+    hipError_t le = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)spec_persist_kernel, kSolveThreads,
+                                                                 pl.lds_bytes);
+    if (le == hipSuccess && (per_cu < 1 || !pl.resident)) le = hipErrorCooperativeLaunchTooLarge;
+    if (le == hipSuccess) {
+        const char* coop = getenv("MSM_SPEC_COOP");
+        if (coop && coop[0] == '1') {
+            void* kargs[] = {(void*)&ar_it, (void*)&pa};
+            le = hipLaunchCooperativeKernel((const void*)spec_persist_kernel, dim3(grid), dim3(kSolveThreads), kargs,
+                                            (unsigned)pl.lds_bytes, ctx->stream);
+        } else {
+            hipLaunchKernelGGL(spec_persist_kernel, dim3(grid), dim3(kSolveThreads), pl.lds_bytes, ctx->stream, ar_it, pa);
+            le = hipGetLastError();
+        }
+    }
+    if (getenv("MSM_SPEC_DEBUG"))
+        fprintf(stderr, "msm_spectrum: persistent launch n=%d p=%d cols=%d G=%d groups=%d lds=%zu -> %s\n", n_max, p,
+                pl.cols, pl.G, pl.groups, pl.lds_bytes, hipGetErrorString(le));
+    if (le == hipSuccess) *error = pa.error;
+    else (void)hipGetLastError();
+    return MSM_OK;
+}
+
+static SpecArgs fill_spec_args(const msm_ctx* ctx, const double* d_T, int64_t t_stride, int ld, const int32_t* d_n,
+                               int n_max, int batch, int p, int init, uint64_t seed, int n_watch, double* d_ritz,
+                               double* d_pi, int64_t pi_stride, double* d_change, int32_t* d_status, int n_its,
+                               const double* d_lags, double* d_its_eig, double* d_its_ts, double freeze_tol,
+                               double* d_vecs, int n_vecs) {
+    SpecArgs ar;
+    ar.T = d_T; ar.t_stride = (size_t)t_stride; ar.ld = ld; ar.n_ptr = d_n; ar.n_fixed = n_max;
+    ar.p = p; ar.init = init; ar.seed = seed;
+    ar.zw_stride = (size_t)n_max * p + kSolveThreads;
+    ar.ritz = d_ritz; ar.pi = d_pi; ar.pi_stride = (size_t)pi_stride; ar.change = d_change;
+    ar.n_watch = n_watch;
+    ar.freeze_tol = freeze_tol;
+    ar.vecs = d_vecs; ar.n_vecs = n_vecs;
+    ar.status = d_status; ar.n_its = n_its; ar.lags = d_lags; ar.its_eig = d_its_eig; ar.its_ts = d_its_ts;
+    ar.persist_error = nullptr;
+    // enough workgroups for the product to fill the chip four times over, no more splits than that needs
+    const int64_t per_split = (int64_t)((n_max + 255) / 256) * batch;
+    ar.splits = (int)std::max<int64_t>(1, std::min<int64_t>(kSpecSplits, (4 * (int64_t)ctx->n_cu + per_split - 1) / per_split));
+    return ar;
+}
+
 static msm_status spectrum_impl(msm_ctx* ctx, const double* d_T, const double* d_iter, int64_t t_stride, int ld,
                                 const int32_t* d_n, int n_max,
                         int batch, int p, int n_iter, int init, uint64_t seed, int n_watch, void* d_workspace,
@@ -1228,148 +1310,59 @@ static msm_status spectrum_impl(msm_ctx* ctx, const double* d_T, const double* d
     MSM_REQUIRE(ctx, n_iter >= 0 && n_its >= 0 && n_its < kMaxP, "msm_spectrum: bad n_iter / n_its");
     MSM_REQUIRE(ctx, d_T && d_workspace && d_ritz && d_change && d_status, "msm_spectrum: NULL pointer");
     MSM_REQUIRE(ctx, n_its == 0 || (d_its_eig && d_its_ts), "msm_spectrum: its outputs missing");
-    SpecArgs ar;
-    ar.T = d_T; ar.t_stride = (size_t)t_stride; ar.ld = ld; ar.n_ptr = d_n; ar.n_fixed = n_max;
-    ar.p = p; ar.n_iter = n_iter; ar.init = init; ar.seed = seed;
-    const size_t zw = (size_t)n_max * p + kSolveThreads;
+    SpecArgs ar = fill_spec_args(ctx, d_T, t_stride, ld, d_n, n_max, batch, p, init, seed, n_watch, d_ritz, d_pi, pi_stride,
+                                 d_change, d_status, n_its, d_lags, d_its_eig, d_its_ts, freeze_tol, d_vecs, n_vecs);
     double* bufA = (double*)d_workspace;              // the orthonormal basis lives here between calls
-    double* bufB = bufA + zw * batch;
-    double* partial = bufB + zw * batch;
+    double* bufB = bufA + ar.zw_stride * batch;       // W = T'Z where it does not fit the LDS
+    double* partial = bufB + ar.zw_stride * batch;
     const size_t part_stride = (size_t)kSpecSplits * n_max * p;
-    ar.Z = bufA; ar.W = bufB;
-    ar.zw_stride = zw;
-    ar.ritz = d_ritz; ar.pi = d_pi; ar.pi_stride = (size_t)pi_stride; ar.change = d_change;
-    ar.n_watch = n_watch;
-    ar.freeze_tol = freeze_tol;
-    ar.vecs = d_vecs; ar.n_vecs = n_vecs;
-    ar.status = d_status; ar.n_its = n_its; ar.lags = d_lags; ar.its_eig = d_its_eig; ar.its_ts = d_its_ts;
-    ar.persist_error = nullptr;
-    {   // enough workgroups for the product to fill the chip four times over, no more splits than that needs
-        const int64_t per_split = (int64_t)((n_max + 255) / 256) * batch;
-        ar.splits = (int)std::max<int64_t>(1, std::min<int64_t>(kSpecSplits, (4 * (int64_t)ctx->n_cu + per_split - 1) / per_split));
-    }
-    // orthogonalise every kOrthoEvery applications and always after the last one; compare the
-    // complex Ritz values against those right after an earlier orthogonalisation.  Every step:
-    // Cholesky-QR squares the condition number of W, and a metastable T damps the fast directions
-    // by lambda^q -- already q = 6 un-orthogonalised applications broke the factorisation.
-    constexpr int kOrthoEvery = 1;
-    ar.check_gap = n_iter;
     // the ITERATIONS may run on a power of T (d_iter, msm_matrix_power: same invariant subspaces, convergence ratio to
     // that power); the Rayleigh-Ritz step, the residuals and everything reported come from T itself
     SpecArgs ar_it = ar;
     if (d_iter) ar_it.T = d_iter;
-    auto apply = [&](const double* zin, const SpecArgs& aa) {
+    auto* apply_kernel = p <= 8 ? spec_apply_kernel<8> : p <= 16 ? spec_apply_kernel<16>
+                         : p <= 24 ? spec_apply_kernel<24> : spec_apply_kernel<32>;
+    auto apply = [&](const SpecArgs& aa) {     // partial = the row-split products of T'Z, Z = bufA
         const dim3 grid((unsigned)((n_max + 255) / 256), (unsigned)aa.splits, (unsigned)batch);
-        if (p <= 8) hipLaunchKernelGGL(spec_apply_kernel<8>, grid, dim3(kApplyThreads), 0, ctx->stream, aa, zin, partial, part_stride);
-        else if (p <= 16) hipLaunchKernelGGL(spec_apply_kernel<16>, grid, dim3(kApplyThreads), 0, ctx->stream, aa, zin, partial, part_stride);
-        else if (p <= 24) hipLaunchKernelGGL(spec_apply_kernel<24>, grid, dim3(kApplyThreads), 0, ctx->stream, aa, zin, partial, part_stride);
-        else hipLaunchKernelGGL(spec_apply_kernel<32>, grid, dim3(kApplyThreads), 0, ctx->stream, aa, zin, partial, part_stride);
+        hipLaunchKernelGGL(apply_kernel, grid, dim3(kApplyThreads), 0, ctx->stream, aa, bufA, partial, part_stride);
     };
     const size_t w_bytes = (size_t)n_max * p * sizeof(double);
     const bool lds_w = w_bytes <= 96 * 1024;
     if (lds_w && w_bytes > 12 * 1024)
         MSM_HIP(ctx, hipFuncSetAttribute((const void*)spec_step_kernel<true>,
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)w_bytes));
-    auto step = [&](int mode, double* z, double* w) {
-        if (lds_w && !(mode & kStepInit))
-            hipLaunchKernelGGL(spec_step_kernel<true>, dim3(batch), dim3(kSolveThreads), w_bytes, ctx->stream, ar, mode,
-                               z, w, partial, part_stride);
-        else
-            hipLaunchKernelGGL(spec_step_kernel<false>, dim3(batch), dim3(kSolveThreads), 0, ctx->stream, ar, mode, z,
-                               w, partial, part_stride);
+    auto step = [&](int mode) {                // W in the LDS when it fits (seeding leaves it in bufB)
+        const bool in_lds = lds_w && !(mode & kStepInit);
+        hipLaunchKernelGGL(in_lds ? spec_step_kernel<true> : spec_step_kernel<false>, dim3(batch), dim3(kSolveThreads),
+                           in_lds ? w_bytes : 0, ctx->stream, ar, mode, bufA, bufB, partial, part_stride);
     };
     if (init || !(freeze_tol > 0.0))   // frozen matrices keep their status
         MSM_HIP(ctx, hipMemsetAsync(d_status, 0, sizeof(int32_t) * batch, ctx->stream));
-    if (init) step(kStepInit, bufA, bufB);
+    if (init) step(kStepInit);
     MSM_CHECK_LAUNCH(ctx);
     // ---- the iterations: one persistent launch when the shape allows (see spec_persist_kernel)
-    bool persisted = false;
     if (n_iter > 0 && spec_persist_enabled()) {
-        const size_t budget = (size_t)(160 - 24 - 4) * 1024 / sizeof(double);   // LDS less PersistShared and slack
-        const size_t fixed = (size_t)n_max * (p | 1);
-        int cols = budget > fixed + (size_t)8 * (n_max + p + 2) ? (int)((budget - fixed) / (size_t)(n_max + p + 2)) : 0;
-        cols = std::min(cols, n_max);
-        auto fits = [&](int c) { return (size_t)n_max * (c | 1) + fixed + (size_t)c * p <= budget; };
-        while (cols >= 8 && !fits(cols)) --cols;
-        if (getenv("MSM_SPEC_DEBUG")) fprintf(stderr, "msm_spectrum: n=%d p=%d first cols=%d\n", n_max, p, cols);
-        if (cols >= 8) {
-            const int G = (n_max + cols - 1) / cols;
-            while (cols > 1 && (n_max + cols - 2) / (cols - 1) == G && fits(cols - 1)) --cols;   // even shares: the fewest columns that keep G
-            // a group lives on one XCD (32 CUs): G <= 32; groups per XCD = 32 / G, eight XCDs
-            const int per_xcd = G <= 32 ? 32 / G : 0;
-            // Only when every matrix gets a group at once: a large batch (a lag scan with posterior samples) already
-            // fills the chip with independent single-workgroup steps, and a group per matrix would serialise it.
-            const int groups = batch <= 8 * per_xcd ? batch : 0;
-            if (groups >= 1) {
-                const int slots = (groups + 7) / 8;          // group q = slot * 8 + xcd
-                const size_t gram_bytes = (size_t)groups * 2 * G * kMaxP * kMaxP * sizeof(double);
-                const size_t need = gram_bytes + (size_t)groups * sizeof(unsigned) + 64;
-                msm_status rs = msm_reserve_aux(ctx, need);
-                if (rs != MSM_OK) return rs;
-                PersistArgs pa;
-                pa.gram = (double*)ctx->aux;
-                pa.counters = (unsigned*)((char*)ctx->aux + gram_bytes);
-                pa.error = (int*)(pa.counters + groups);
-                pa.G = G; pa.groups = groups; pa.cols = cols; pa.batch = batch; pa.n_iter = n_iter;
-                pa.twice = d_iter ? 1 : 0;
-                pa.bufA = bufA; pa.bufB = bufB;
-                MSM_HIP(ctx, hipMemsetAsync(pa.counters, 0, (size_t)groups * sizeof(unsigned) + sizeof(int), ctx->stream));
-                const size_t lds = ((size_t)n_max * (cols | 1) + (size_t)n_max * (p | 1) + (size_t)cols * p) * sizeof(double);
-                MSM_HIP(ctx, hipFuncSetAttribute((const void*)spec_persist_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)lds));
-                // Residency: the barriers need every workgroup of the grid on a CU at once.  The grid is at most one
-                // workgroup per CU (checked here against the occupancy the runtime reports), the stream is in order, and a
-                // barrier that is not met within ~1 s raises the error flag instead of spinning on; a plain launch is
-                // used because rocprofv3 crashes at exit of a process that made a cooperative launch (MSM_SPEC_COOP=1
-                // asks for hipLaunchCooperativeKernel all the same).
-                const unsigned grid = (unsigned)(slots * G * 8);
-                int per_cu = 0;
-                hipError_t le = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)spec_persist_kernel,
-                                                                             kSolveThreads, lds);
-                if (le == hipSuccess && (per_cu < 1 || grid > (unsigned)ctx->n_cu)) le = hipErrorCooperativeLaunchTooLarge;
-                if (le == hipSuccess) {
-                    const char* coop = getenv("MSM_SPEC_COOP");
-                    if (coop && coop[0] == '1') {
-                        void* kargs[] = {(void*)&ar_it, (void*)&pa};
-                        le = hipLaunchCooperativeKernel((const void*)spec_persist_kernel, dim3(grid), dim3(kSolveThreads), kargs,
-                                                        (unsigned)lds, ctx->stream);
-                    } else {
-                        hipLaunchKernelGGL(spec_persist_kernel, dim3(grid), dim3(kSolveThreads), lds, ctx->stream, ar_it, pa);
-                        le = hipGetLastError();
-                    }
-                }
-                if (getenv("MSM_SPEC_DEBUG"))
-                    fprintf(stderr, "msm_spectrum: persistent launch n=%d p=%d cols=%d G=%d groups=%d lds=%zu -> %s\n", n_max, p,
-                            cols, G, groups, lds, hipGetErrorString(le));
-                if (le == hipSuccess) {
-                    persisted = true;
-                    ar.persist_error = pa.error;
-                } else {
-                    (void)hipGetLastError();     // not resident together on this device / in this state: the launch loop below
-                }
-            }
+        const PersistPlan pl = plan_persist(n_max, p, batch, ctx->n_cu);
+        if (getenv("MSM_SPEC_DEBUG")) fprintf(stderr, "msm_spectrum: n=%d p=%d first cols=%d\n", n_max, p, pl.first_cols);
+        if (pl.groups >= 1) {
+            msm_status rs = launch_persist(ctx, pl, ar_it, n_max, p, batch, n_iter, d_iter != nullptr, bufA, bufB, &ar.persist_error);
+            if (rs != MSM_OK) return rs;
         }
     }
     // (Tried: the iterations of a large batch sub-batch by sub-batch, so that a sub-batch's matrices stay in the 256 MB
     // memory-side cache between iterations -- the product reads 1.6 GB per iteration at C4.  Slower at every sub-batch
     // size: 623 / 592 / 567 ms at 256 / 512 / 1024 matrices against 531 ms for whole-batch launches.)
-    // invariant at the top of an iteration: the current basis is in `cur`
-    double* cur = bufA;
-    double* other = bufB;
+    // Otherwise a launch pair per iteration.  Every application is followed by an orthogonalisation: Cholesky-QR
+    // squares the condition number of W, and a metastable T damps the fast directions by lambda^q -- already q = 6
+    // un-orthogonalised applications broke the factorisation.
+    const bool persisted = ar.persist_error != nullptr;
     for (int it = 0; it < (persisted ? 0 : n_iter); ++it) {
-        apply(cur, ar_it);
-        const bool ortho = (it % kOrthoEvery) == kOrthoEvery - 1 || it == n_iter - 1;
-        const int mode = ortho ? (kStepOrtho | (d_iter && it == n_iter - 1 ? kStepTwice : 0)) : 0;
-        step(mode, cur, other);   // sum -> other; ortho: orth(other) -> cur
-        if (!ortho) std::swap(cur, other);
+        apply(ar_it);
+        step(kStepOrtho | (d_iter && it == n_iter - 1 ? kStepTwice : 0));
         MSM_CHECK_LAUNCH(ctx);
     }
-    if (cur != bufA) {  // keep the persistent basis in bufA
-        MSM_HIP(ctx, hipMemcpyAsync(bufA, cur, zw * batch * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-        cur = bufA; other = bufB;
-    }
-    apply(cur, ar);
-    step(kStepFinish, cur, other);
+    apply(ar);
+    step(kStepFinish);
     MSM_CHECK_LAUNCH(ctx);
     return MSM_OK;
 }

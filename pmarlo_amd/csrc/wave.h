@@ -1,4 +1,5 @@
-// Cross-lane and workgroup reductions shared by every kernel of libmsmhip.so.  Device-only; include after common.h.
+// Cross-lane and workgroup reductions shared by every kernel of libmsmhip.so, and two workgroup idioms more than one
+// file uses (rank_order, mfma_tile_acc).  Device-only; include after common.h.
 //
 // What all of it rests on:
 //   * a wave is 64 lanes (gfx9); "lane" is threadIdx.x & 63, "wave" is threadIdx.x >> 6, and every lane of the wave
@@ -140,6 +141,36 @@ __device__ __forceinline__ double block_max_bcast(double v, double* red, double*
     return block_reduce_bcast(v, red, bc, -INFINITY, op_max{});
 }
 
+// Rank by counting: order[r] = the index whose key(i) is the r-th largest (descending) or smallest, equal keys in
+// index order (stable).  Index i is ranked by thread i, i + blockDim.x, ...: the result is a function of the keys
+// alone.  No barrier: the caller synchronises before `order` is read.
+template <bool descending, typename Key>
+__device__ __forceinline__ void rank_order(int n, int* order, Key key) {
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const double a = key(i);
+        int rank = 0;
+        for (int j = 0; j < n; ++j) {
+            const double b = key(j);
+            rank += (descending ? b > a : b < a) || (b == a && j < i);
+        }
+        order[rank] = i;
+    }
+}
+// The same with equal keys ordered by tie(i) in the same direction first, then by index.
+template <bool descending, typename Key, typename Tie>
+__device__ __forceinline__ void rank_order(int n, int* order, Key key, Tie tie) {
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const double a = key(i), ta = tie(i);
+        int rank = 0;
+        for (int j = 0; j < n; ++j) {
+            const double b = key(j), tb = tie(j);
+            rank += (descending ? b > a : b < a) ||
+                    (b == a && ((descending ? tb > ta : tb < ta) || (tb == ta && j < i)));
+        }
+        order[rank] = i;
+    }
+}
+
 // VALU-only reductions: DPP moves inside the rows of 16 lanes, then the two row swaps of gfx950.  No LDS crossbar:
 // a step is one v_mov_dpp (two for a 64-bit payload) plus the combiner.  Every lane ends with the result; for a sum
 // all lanes hold the same bits (both partners of a step add the same two values).  T has 4 or 8 bytes.
@@ -212,4 +243,30 @@ __device__ __forceinline__ double readlane_f64(double v, int lane) {
     const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)b, lane);
     const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(b >> 32), lane);
     return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+
+typedef double v4f64 __attribute__((ext_vector_type(4)));   // accumulator of v_mfma_f64_16x16x4_f64
+
+// One 16 x 16 tile of C = opA opB on the fp64 matrix cores by one wave: lane (j, g) = (lane & 15, lane >> 4) supplies
+// a(k) = opA(i0 + j, k) and b(k) = opB(k, c0 + j), k < inner, through loadA(k) / loadB(k), which read clamped
+// (in-range) addresses; aok / bok say whether the lane's row of opA / column of opB lies inside the matrix, and what
+// lies outside is fed as zero.  acc[r] ends up as entry (i0 + g + 4 r, c0 + j) of the tile.
+template <typename LoadA, typename LoadB>
+__device__ __forceinline__ v4f64 mfma_tile_acc(int inner, int g, bool aok, bool bok, LoadA loadA, LoadB loadB) {
+    v4f64 acc = {0.0, 0.0, 0.0, 0.0};
+    for (int k0 = 0; k0 < inner; k0 += 16) {   // four instructions per trip: their operand reads go out together
+        double a[4], b[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const bool kok = k0 + 4 * u + g < inner;
+            const int k = kok ? k0 + 4 * u + g : 0;
+            a[u] = loadA(k);
+            b[u] = loadB(k);
+            if (!(aok && kok)) a[u] = 0.0;
+            if (!(bok && kok)) b[u] = 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u], b[u], acc, 0, 0, 0);
+    }
+    return acc;
 }

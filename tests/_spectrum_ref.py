@@ -3,8 +3,8 @@
 Reversible chains T = D^-1 C (C symmetric, D = diag of its row sums) have everything the solver reports in closed
 form or through a backward-stable symmetric eigensolve: pi = rowsum / total, the eigenvalues of T are those of
 D^-1/2 C D^-1/2, and the left eigenvectors are x = D^1/2 u for its eigenvectors u.  `spectrum_path` restates which
-code path `spectrum_impl` (pmarlo_amd/csrc/msm.hip) and its finishing step take for a shape; the GPU tests check it
-against the library's MSM_SPEC_DEBUG lines."""
+code path `plan_persist` / `spectrum_impl` (pmarlo_amd/csrc/msm.hip) and the finishing step take for a shape; the GPU
+tests check it against the library's MSM_SPEC_DEBUG lines."""
 
 from __future__ import annotations
 
@@ -15,7 +15,7 @@ import numpy as np
 from oracle import npport
 
 # ---------------------------------------------------------------------------------------------------------------
-# the launch-path rule (spectrum_impl and the kStepFinish branch of spec_step_kernel)
+# the launch-path rule (plan_persist and spectrum_impl; side_by_side: the finish of spec_step_kernel)
 # ---------------------------------------------------------------------------------------------------------------
 K_MAX_P = 32
 LDS_W_BYTES = 96 * 1024                              # W of the loop's step kernel in LDS up to here
