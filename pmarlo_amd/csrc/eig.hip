@@ -485,10 +485,10 @@ struct TriShared {
     double scale, gl, gu;
     double red[kEigThreads / 64];
     int bad;
-    double part[16][kTriMax];  // partial products of the tridiagonalisation, one row per wave (the LDL' phase uses rows 0-7)
+    double part[16][kTriMax];  // partial products of the tridiagonalisation, one row per wave (the LDL' phase keeps its pivot rows there)
     union {                    // the two register-resident phases never overlap
         double2 vw[8][kTriMax];                 // tridiagonalisation: {v_j, w_j} of the column in flight, one copy per A wave
-        alignas(16) double lv[16][kTriMax];     // LDL': multipliers of the column in flight, one copy per working wave
+        alignas(16) double lv[16][kTriMax];     // unused since the LDL' phase went to the matrix cores: keeps sizeof (tests/_eig_ref.py)
     };
     double vpub[2][kTriMax];   // tridiagonalisation: the reflector of column k for the Q' waves, slot k & 1
     double taupub[2];
@@ -746,89 +746,127 @@ __device__ __forceinline__ void householder_phase(double* A, double* QT, int n, 
     }
 }
 
-// Whitening of a full-rank C00 in registers, the pattern of householder_phase: an LDL' elimination with X = L^-1 carried
-// along, one barrier per column.  Waves 0-7 hold the rows i = w (mod 8) of C00, waves 8-15 the same rows of X (= identity
-// at the start); lane = column; 8 doubles per lane, compile-time indices only.
-// Column j: the owner of row j has left it in the LDS.  The trailing matrix is symmetric, so that row is also column j:
-// lane i of (row j) / d_j IS the multiplier l_i; every wave parks the multipliers in its own LDS copy, ordered so that
-// those of its eight rows come back as four 16-byte broadcast reads.  Row i of C00 or X then takes one fma (l_i = 0 up
-// to row j: finished rows stay); the owner of row j + 1 leaves it in the LDS for the next column.  A wave issues about
-// one instruction per 10 cycles, so the column's chain is kept short by dealing the rows over all sixteen waves.
-// On success W = (D^-1/2 L^-1)' (upper triangular, W' C00 W = I) is written to `W`; false (uniformly) as soon as a pivot
-// is not positive.  C is left as it was.  blockDim.x == 1024.
+// Whitening of a full-rank C00: an LDL' elimination of [C00 | I] (X = L^-1 grows out of the identity), four pivots per
+// barrier, both matrices in matrix-core accumulators from start to end.  Wave w holds the 16 x 16 tile (I, J) =
+// (w / 4, w % 4) of C00 and the same tile of X; one v_mfma_f64_16x16x4_f64 is exactly the rank-4 update of a tile.
+// Block b, pivots j0 = 4 b .. j0 + 3: the waves of the row tile that holds rows j0 .. j0 + 3 have left them in the LDS
+// (entry (g + 4 r, j) of a tile sits in acc[r] of lane (j, g): the four rows are one accumulator register of the
+// tile's 64 lanes).  The trailing matrix is symmetric, so those rows are also the panel's columns.  Every lane
+// eliminates the four pivots one after the other, as the unblocked elimination does, on the 4 x 4 diagonal block
+// (the same numbers in every lane: the pivots d_c and the multipliers among the four rows) and on the two columns
+// it feeds to the matrix core: row i0 + j of the multipliers l_ic = u_c[i] / d_c, zero up to the pivot's own row so
+// that finished rows stay, and column c0 + j of the eliminated pivot rows u_c of C00 and of X.  Then one instruction
+// per tile, and the owners of the next four rows leave them for the next block.
+// On success W = (D^-1/2 L^-1)' (upper triangular, W' C00 W = I) is written to `W`; false (uniformly) as soon as a
+// pivot is not positive, whichever of a block's four it is.  C is left as it was.  blockDim.x == 1024.
 // mode 1: C00 and X (the caller certifies full rank from W, see tica_solve_kernel);
-// mode 2: the probe C00 - epsilon I alone (waves 0-7), nothing is written to W.
+// mode 2: the probe C00 - epsilon I alone, nothing is written to W.
 __device__ __forceinline__ bool ldl_whiten_registers(const double* C, double* W, int n, double epsilon, TriShared* ts,
                                                      int mode) {
-    static_assert(kEigThreads == 1024, "ldl_whiten_registers deals the rows over sixteen waves");
+    static_assert(kEigThreads == 1024 && kTriMax == 64, "ldl_whiten_registers deals 4 x 4 tiles of 16 x 16 over sixteen waves");
     constexpr int ld = kTriLd;
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const bool in = lane < n;
-    // 0: C00, 1: X, 2: probe, 3: nothing
-    const int what = mode == 2 ? (wave < 8 ? 2 : 3) : (wave < 8 ? 0 : 1);
-    const int src = mode == 2 ? 2 : 0;   // the matrix the multipliers come from: its published rows sit in part[par + src]
-    const int sub = wave & 7;
-    double m[8];
+    const int jj = lane & 15, g = lane >> 4;
+    const int I = wave >> 2, J = wave & 3, i0 = 16 * I, c0 = 16 * J;
+    const bool with_x = mode == 1;
+    const bool live = i0 < n && c0 < n;   // the tile holds entries of the matrix
+    v4f64 ac, ax;
 #pragma unroll
-    for (int t = 0; t < 8; ++t) {
-        const int i = sub + 8 * t;
-        if (what == 1) m[t] = lane == i ? 1.0 : 0.0;
-        else m[t] = (what < 3 && in && i < n) ? C[i * ld + lane] - (what == 2 && lane == i ? epsilon : 0.0) : 0.0;
+    for (int r = 0; r < 4; ++r) {
+        const int row = i0 + g + 4 * r, col = c0 + jj;
+        const bool ok = row < n && col < n;
+        const double c = C[ok ? row * ld + col : 0];
+        ac[r] = ok ? c - (mode == 2 && row == col ? epsilon : 0.0) : 0.0;
+        ax[r] = ok && row == col ? 1.0 : 0.0;
     }
-    if (sub == 0 && what < 3) ts->part[what][lane] = m[0];   // row 0 for column 0
+    // pivot rows of block b: part[8 (b & 1) + g] of C00, part[8 (b & 1) + 4 + g] of X
+    if (I == 0) {
+        ts->part[g][c0 + jj] = ac[0];
+        ts->part[4 + g][c0 + jj] = ax[0];
+    }
     __syncthreads();
     LSTAMP_INIT
-    for (int j = 0; j < n; ++j) {
-        const int par = (j & 1) * 4;
-        if (what < 3) {
-            // row j of the matrix the multipliers come from and of the matrix this wave updates
-            const double rowM = ts->part[par + src][lane];
-            const double row = what == 1 ? ts->part[par + 1][lane] : rowM;
-            const double d = readlane_f64(rowM, j);
-            LSTAMP(13);
-            if (!(d > 0.0)) return false;   // uniform over the workgroup (see below for the idle waves)
-            {
-                // multipliers of the live rows (zero up to row j: finished rows stay as they are), dealt out so that
-                // the eight of this wave's rows lie side by side in its LDS copy: l_i at (i mod 8) * 8 + i / 8
-                const double lvec = lane > j ? rowM * nr_rcp(d) : 0.0;
-                double* lv = ts->lv[wave];
-                lv[(lane & 7) * 8 + (lane >> 3)] = lvec;
-                const double2* mine = reinterpret_cast<const double2*>(lv + sub * 8);
+    for (int I0 = 0; I0 < 4; ++I0) {
 #pragma unroll
-                for (int t2 = 0; t2 < 4; ++t2) {
-                    const double2 l = mine[t2];
-                    m[2 * t2] = fma(-l.x, row, m[2 * t2]);
-                    m[2 * t2 + 1] = fma(-l.y, row, m[2 * t2 + 1]);
+        for (int r = 0; r < 4; ++r) {
+            const int j0 = 16 * I0 + 4 * r;
+            if (j0 >= n) break;   // uniform
+            const double* pc = ts->part[8 * (r & 1)];   // 16 I0 + 4 r: the block's parity is r's
+            const double* px = pc + 4 * kTriMax;
+            // ---- the 4 x 4 diagonal block: pivots, their reciprocals, the multipliers among the four rows
+            double2 blk[4][2];
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+#pragma unroll
+                for (int h = 0; h < 2; ++h) blk[c][h] = *reinterpret_cast<const double2*>(pc + c * kTriMax + j0 + 2 * h);
+            const bool ok1 = j0 + 1 < n, ok2 = j0 + 2 < n, ok3 = j0 + 3 < n;   // pivots past n: rows of zeros, no test
+            const double d0 = blk[0][0].x;
+            bool bad = !(d0 > 0.0);
+            const double r0 = nr_rcp(d0);
+            const double l10 = blk[0][0].y * r0, l20 = blk[0][1].x * r0, l30 = blk[0][1].y * r0;
+            const double b11 = fma(-l10, blk[0][0].y, blk[1][0].y), b12 = fma(-l10, blk[0][1].x, blk[1][1].x);
+            const double b13 = fma(-l10, blk[0][1].y, blk[1][1].y);
+            const double d1 = ok1 ? b11 : 1.0;
+            bad = bad || !(d1 > 0.0);
+            const double r1 = nr_rcp(d1);
+            const double l21 = b12 * r1, l31 = b13 * r1;
+            const double b22 = fma(-l21, b12, fma(-l20, blk[0][1].x, blk[2][1].x));
+            const double b23 = fma(-l21, b13, fma(-l20, blk[0][1].y, blk[2][1].y));
+            const double d2 = ok2 ? b22 : 1.0;
+            bad = bad || !(d2 > 0.0);
+            const double r2 = nr_rcp(d2);
+            const double l32 = b23 * r2;
+            const double b33 = fma(-l32, b23, fma(-l31, b13, fma(-l30, blk[0][1].y, blk[3][1].y)));
+            const double d3 = ok3 ? b33 : 1.0;
+            bad = bad || !(d3 > 0.0);
+            const double r3 = nr_rcp(d3);
+            LSTAMP(13);
+            if (__builtin_amdgcn_readfirstlane((int)bad)) return false;   // the same numbers in every lane of every wave
+            if (with_x && wave == 0 && lane < 4 && j0 + lane < n)
+                ts->inv[j0 + lane] = nr_rsqrt(lane == 0 ? d0 : (lane == 1 ? d1 : (lane == 2 ? d2 : d3)));
+            // column `col` of the four pivot rows, eliminated one after the other
+            auto eliminate = [&](const double* rows, int col, double (&u)[4]) {
+                const double p0 = rows[col], p1 = rows[kTriMax + col], p2 = rows[2 * kTriMax + col], p3 = rows[3 * kTriMax + col];
+                u[0] = p0;
+                u[1] = fma(-l10, u[0], p1);
+                u[2] = fma(-l21, u[1], fma(-l20, u[0], p2));
+                u[3] = fma(-l32, u[2], fma(-l31, u[1], fma(-l30, u[0], p3)));
+            };
+            if (live && I >= I0) {   // uniform; row tiles above the pivots are finished
+                double ua[4];
+                eliminate(pc, i0 + jj, ua);
+                // multiplier of row i0 + jj for pivot j0 + g (zero up to the pivot's own row), pivot row g at column c0 + jj
+                const double mg = g == 0 ? ua[0] * r0 : (g == 1 ? ua[1] * r1 : (g == 2 ? ua[2] * r2 : ua[3] * r3));
+                const double a = i0 + jj > j0 + g ? -mg : 0.0;
+                if (J >= I) {   // pivot rows are only ever read to the right of the pivot: the tiles below the diagonal are never used
+                    double ub[4];
+                    eliminate(pc, c0 + jj, ub);
+                    const double b = g == 0 ? ub[0] : (g == 1 ? ub[1] : (g == 2 ? ub[2] : ub[3]));
+                    ac = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, ac, 0, 0, 0);
                 }
-                if (((j + 1 - sub) & 7) == 0) {   // this wave owns row j + 1: leave it for the next column
-                    double* dst = ts->part[(par ^ 4) + what] + lane;
-                    switch ((j + 1 - sub) >> 3) {
-                        case 0: *dst = m[0]; break;   case 1: *dst = m[1]; break;   case 2: *dst = m[2]; break;
-                        case 3: *dst = m[3]; break;   case 4: *dst = m[4]; break;   case 5: *dst = m[5]; break;
-                        case 6: *dst = m[6]; break;   case 7: *dst = m[7]; break;   default: break;
-                    }
+                if (with_x && J <= I) {   // X is lower triangular: the tiles above the diagonal stay zero
+                    double ux[4];
+                    eliminate(px, c0 + jj, ux);
+                    const double bx = g == 0 ? ux[0] : (g == 1 ? ux[1] : (g == 2 ? ux[2] : ux[3]));
+                    ax = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bx, ax, 0, 0, 0);
+                }
+                // the next four rows for the next block
+                if (j0 + 4 < n && I == (r < 3 ? I0 : I0 + 1)) {
+                    double* nc = ts->part[8 * ((r + 1) & 1)];
+                    nc[g * kTriMax + c0 + jj] = ac[r < 3 ? r + 1 : 0];
+                    nc[(4 + g) * kTriMax + c0 + jj] = ax[r < 3 ? r + 1 : 0];
                 }
             }
-        } else {   // waves without rows: the same pivot, the same decision
-            const double dP = ts->part[par + src][j];
-            if (!(dP > 0.0)) return false;
+            LSTAMP(14);
+            __syncthreads();
+            LSTAMP(15);
         }
-        LSTAMP(14);
-        __syncthreads();
-        LSTAMP(15);
     }
-    // d_i sits in lane i of row i of the C00 waves (row i was final after column i - 1): hand D^-1/2 to the X waves
-    if (what == 0) {
+    if (with_x && live) {
 #pragma unroll
-        for (int t = 0; t < 8; ++t)
-            if (lane == sub + 8 * t && lane < n) ts->inv[lane] = nr_rsqrt(m[t]);
-    }
-    __syncthreads();
-    if (what == 1 && in) {
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            const int i = sub + 8 * t;
-            if (i < n) W[lane * ld + i] = m[t] * ts->inv[i];   // X is lower triangular: zeros above the diagonal of W'
+        for (int r = 0; r < 4; ++r) {
+            const int row = i0 + g + 4 * r, col = c0 + jj;
+            if (row < n && col < n) W[col * ld + row] = ax[r] * ts->inv[row];   // X is lower triangular: zeros above the diagonal of W'
         }
     }
     __syncthreads();
@@ -1227,12 +1265,12 @@ __global__ __launch_bounds__(kEigThreads) void tica_solve_kernel(
     // the TICA eigenpairs do not depend on which whitening is used -- they solve
     // C0t r = lambda C00 r -- so L = chol(C00)^-T replaces the first eigensolve.
     // Rank-deficient C00 takes the eigen path below, as before.
-    constexpr bool kFused = lds_mats == 4;   // fused LDL' + inverse (one barrier per column) and the tridiagonal solver
+    constexpr bool kFused = lds_mats == 4;   // fused LDL' + inverse (one barrier per four columns) and the tridiagonal solver
     bool full_rank;
     if (kFused && n <= kTriMax) {
         // B2 = whitening W (upper triangular, W' C00 W = I); C00 stays in A.  C00^-1 = W W', so lambda_min(C00) >=
         // 1 / trace(W W') = 1 / ||W||_F^2: when that already clears epsilon every eigen-direction is kept and the
-        // elimination of the probe C00 - epsilon I (a third of the phase's instructions) is not needed
+        // elimination of the probe C00 - epsilon I (a second pass of the same length) is not needed
         full_rank = ldl_whiten_registers(A, B2, n, epsilon, &ts, 1);
         if (full_rank) {
             double s = 0.0;

@@ -10,7 +10,7 @@
 static const char* names[24] = {"init Q", "Householder columns", "barrier", "extract d, e, bounds",
                                 "multisection", "twisted factorisation vectors", "residual + orthogonality check", "Z = Q X",
                                 "tica: covariances from moments", "tica: LDL' + inverse (or eigen path)", "tica: Ct = L' C0t L",
-                                "tica: eigensolve (sum of the rows above)", "tica: sort, R = L Z, signs, output", "  ldl: pivots, reciprocals", "  ldl: updates", "  ldl: barrier",
+                                "tica: eigensolve (sum of the rows above)", "tica: sort, R = L Z, signs, output", "  ldl: 4 x 4 block: pivots, multipliers", "  ldl: columns, rank-4 update, next rows", "  ldl: barrier",
                                 "  hh: loop top", "  hh: barrier 2, rank-2 update + next reflector", "  hh: partial p = A v", "  hh: barrier 1", "  hh: sum partials, p.v, w", "  hh: row k+1 published", "", ""};
 static void report(const char* what, float ms) {
     unsigned long long st[24];
