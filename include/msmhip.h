@@ -398,6 +398,34 @@ msm_status msm_autocorr_lagscan(msm_ctx* ctx, const void* d_x, msm_dtype dtype, 
 msm_status msm_hstack_f64(msm_ctx* ctx, const void* d_a, msm_dtype dtype_a, int pa, int64_t lda, const void* d_b,
                           msm_dtype dtype_b, int pb, int64_t ldb, int64_t n, double* d_out);
 
+/* Forward pass of a trained DeepTICA network in evaluation mode, all frames in one launch: what
+ * DeepTICAModel.transform does before the output whitening (S/features/deeptica/_full.py:283-292), for the network
+ * that override_core_mlp and PrePostWrapper build (S/features/deeptica/core/model.py:72-107, 355-368).
+ *   Z = (x - mean) / scale in fp64 (sklearn's StandardScaler), ROUNDED TO FP32 as the reference's
+ *       torch.as_tensor(Z, dtype=float32) does (_full.py:289); d_mean = d_scale = NULL: Z = x rounded to fp32;
+ *   ln_in: LayerNorm over the F entries of the row (model.py:360; eps 1e-5, biased variance, affine);
+ *   for each of the n_linear Linear layers of widths h_widths[0] = F, ..., h_widths[n_linear] = n_out:
+ *       x <- x W' + b with W [out, in]; then, unless it is the last one, LayerNorm(out) when ln_hidden, and the
+ *       activation (model.py:95-103); after the last one the activation when head_activation is set
+ *       (model.py:104-105: linear_head false).  Dropout is the identity in evaluation.
+ *   activation (resolve_activation_module, model.py:36-50): 0 tanh, 1 gelu (exact, erf), 2 relu, 3 elu (alpha 1),
+ *       4 selu, 5 leaky_relu (slope 0.01).
+ * The parameters are the fp32 values of the bundle, widened exactly; every product (v_mfma_f64_16x16x4_f64), sum,
+ * LayerNorm (two-pass) and activation is fp64.  d_params, n_params floats, packed in this order:
+ *   [gamma [F], beta [F]] of the input LayerNorm if ln_in;
+ *   then for each Linear: W [out, in] row-major, b [out], and [gamma [out], beta [out]] if ln_hidden and it is not
+ *   the last Linear.
+ * n_params must equal what the widths need (MSM_ERR_INVALID otherwise).
+ * A frame's outputs depend on that frame alone: the same bits whatever n is and wherever the frame sits.  A frame
+ * with a non-finite Z (a NaN or Inf input, or one that overflows fp32) gets NaN in all its outputs.
+ * d_x [n, ld] f32 / f64, ld >= F; d_out [n, ldo] f64, ldo >= n_out, columns from n_out on untouched.
+ * Every width <= 256, n_out <= 64, 1 <= n_linear <= 8: MSM_ERR_UNSUPPORTED beyond, naming the number.
+ * One plain launch on the context's stream, capturable. */
+msm_status msm_mlp_forward(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n, int F, int64_t ld,
+                           const double* d_mean, const double* d_scale, int n_linear, const int32_t* h_widths,
+                           int activation, int ln_in, int ln_hidden, int head_activation, const float* d_params,
+                           size_t n_params, double* d_out, int64_t ldo);
+
 /* ------------------------------------------------------------------ */
 /* k-means                                                              */
 /* ------------------------------------------------------------------ */

@@ -28,6 +28,8 @@ REP_SELECT_SMALLEST, REP_SELECT_DIVERSE = 0, 1
 SIL_SEG_LEN, SIL_TILE_I = 1024, 128
 # trajectory bootstrap (MSM_COMBINE_MAX_SEG, MSM_FLUX_LDS_MAX_N in include/msmhip.h)
 COMBINE_MAX_SEG, FLUX_LDS_MAX_N = 32, 127
+# msm_mlp_forward's envelope: widest layer, most outputs, most Linear layers
+MLP_MAX_WIDTH, MLP_MAX_OUT, MLP_MAX_LINEAR = 256, 64, 8
 
 
 class MsmError(RuntimeError):
@@ -94,6 +96,8 @@ _PROTOTYPES: dict[str, tuple] = {
     "msm_eigh": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp]),
     "msm_autocorr_lagscan": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _vp, _i32, _vp, _i32, _f64, _vp, _vp]),
     "msm_hstack_f64": (_i32, [_vp, _vp, _i32, _i32, _i64, _vp, _i32, _i32, _i64, _i64, _vp]),
+    "msm_mlp_forward": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _sz,
+                               _vp, _i64]),
     "msm_kmeans_assign": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _i32, _vp, _vp, _vp, _vp]),
     "msm_kmeans_fit": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _vp, _i32, C.c_uint64, _i32, _i32, _f64, _vp, _vp]),
     "msm_kmeans_fit_begin": (

@@ -54,12 +54,8 @@ def _coerce_bool_flag(value: Any) -> bool:
     raise TypeError("already_applied flag must be a boolean, numeric, or string scalar")
 
 
-def apply_output_transform(Y, mean: Any, W: Any, already_applied) -> np.ndarray:
-    """(Y - mean) W, re-centred, then whitened against the batch covariance (when there are more frames than
-    CVs) and re-centred again; returned unchanged when the flag says the transform was applied before."""
-    arr = np.asarray(Y, dtype=np.float64)
-    if _coerce_bool_flag(already_applied):
-        return arr
+def _output_transform_metadata(shape, mean: Any, W: Any) -> Tuple[np.ndarray, np.ndarray]:
+    """(mean [d], transform [d, m]) as float64 after the reference's consistency checks against outputs of `shape`."""
     if mean is None or W is None:
         raise ValueError("Whitening metadata is incomplete: both mean and transform are required")
     mu = np.asarray(mean, dtype=np.float64)
@@ -70,24 +66,30 @@ def apply_output_transform(Y, mean: Any, W: Any, already_applied) -> np.ndarray:
         raise ValueError("output transform must be a 2D matrix")
     if mu.shape[0] != T.shape[0]:
         raise ValueError(f"output mean and transform dimension mismatch: {mu.shape[0]} vs {T.shape[0]}")
-    if arr.ndim != 2 or arr.shape[1] != mu.shape[0]:
-        raise ValueError(f"projection has incompatible shape for whitening: expected (..., {mu.shape[0]}), got {arr.shape}")
-    n, d = arr.shape
-    m = T.shape[1]
-    if n == 0:
-        return np.zeros((0, m))
+    if len(shape) != 2 or shape[1] != mu.shape[0]:
+        raise ValueError(f"projection has incompatible shape for whitening: expected (..., {mu.shape[0]}), got {tuple(shape)}")
+    return mu, T
+
+
+def _check_cv_count(d: int, m: int) -> None:
     if d > 64 or m > 64:
         raise NotImplementedError("output whitening supports up to 64 collective variables")
-    eng = get_engine()
-    xd = eng.to_device(np.ascontiguousarray(arr))
+
+
+def output_transform_device(eng, xd, mu: np.ndarray, T: np.ndarray):
+    """The frame passes of apply_output_transform on outputs that already live on the device: xd [n, d] float64
+    (n >= 1), checked metadata (mu [d], T [d, m]).  -> (v [n, m], drift [m]) device arrays; the whitened outputs
+    are v - drift, which the caller forms where it wants them (host, or one more projection on the device)."""
+    n, d = xd.shape
+    m = T.shape[1]
+    _check_cv_count(d, m)
     ones = eng.to_device(np.ones(d))
     Wfull = np.zeros((d, max(d, m)))
     Wfull[:, :m] = T
     u = eng.project(xd, eng.to_device(mu), ones, eng.to_device(Wfull), m)                 # (Y - mean) W
     drift, _, _ = eng.column_moments(u, ddof=0)
-    drift_h = drift.to_host()
     if n <= m:
-        return u.to_host() - drift_h[None, :]
+        return u, drift
     mom = eng.lagged_moments(u, 0, drift, assume_finite=True).to_host()                    # sum (u - drift)(u - drift)'
     cov = 0.5 * mom[:m * m].reshape(m, m) / float(n)
     try:
@@ -98,7 +100,22 @@ def apply_output_transform(Y, mean: Any, W: Any, already_applied) -> np.ndarray:
     M = np.linalg.solve(L.T, np.eye(m)).T
     v = eng.project(u, drift, eng.to_device(np.ones(m)), eng.to_device(np.ascontiguousarray(M)), m)
     last, _, _ = eng.column_moments(v, ddof=0)
-    return v.to_host() - last.to_host()[None, :]
+    return v, last
+
+
+def apply_output_transform(Y, mean: Any, W: Any, already_applied) -> np.ndarray:
+    """(Y - mean) W, re-centred, then whitened against the batch covariance (when there are more frames than
+    CVs) and re-centred again; returned unchanged when the flag says the transform was applied before."""
+    arr = np.asarray(Y, dtype=np.float64)
+    if _coerce_bool_flag(already_applied):
+        return arr
+    mu, T = _output_transform_metadata(arr.shape, mean, W)
+    if arr.shape[0] == 0:
+        return np.zeros((0, T.shape[1]))
+    _check_cv_count(arr.shape[1], T.shape[1])
+    eng = get_engine()
+    v, drift = output_transform_device(eng, eng.to_device(np.ascontiguousarray(arr)), mu, T)
+    return v.to_host() - drift.to_host()[None, :]
 
 
 def apply_whitening_from_metadata(values, metadata) -> Tuple[np.ndarray, bool]:

@@ -613,6 +613,29 @@ class Engine:
                  out.shape[1], absmax.ptr if absmax is not None else None), self.handle)
         return out
 
+    def mlp_forward(self, x: DeviceArray, spec, out: DeviceArray | None = None, ld: int | None = None) -> DeviceArray:
+        """Outputs [n, n_out] f64 of the network `spec` describes (features.deeptica.MLPSpec: widths, activation
+        code, flags, packed fp32 parameters, scaler) for the frames x [n, F], f32 or f64 (msm_mlp_forward).
+        The parameters are uploaded on the first call with a spec and kept with it, so later calls, and calls under
+        graph capture, launch the kernel and nothing else.  `out`: preallocated, any width >= n_out.
+        ``ld``: row stride in elements when x is a wider buffer's left block."""
+        n, F = x.shape
+        widths = np.ascontiguousarray(spec.widths, np.int32)
+        dev = getattr(spec, "_dev", None)
+        if dev is None or dev[0] is not self:
+            params = self.to_device(np.ascontiguousarray(spec.params, np.float32).reshape(-1))
+            mean = self.to_device(spec.mean, np.float64) if spec.mean is not None else None
+            scale = self.to_device(spec.scale, np.float64) if spec.scale is not None else None
+            dev = spec._dev = (self, params, mean, scale)
+        _, params, mean, scale = dev
+        out = out if out is not None else self.empty((n, int(widths[-1])), np.float64)
+        check(lib.msm_mlp_forward(self.handle, x.ptr, _dtype_code(x.dtype), n, F, int(F if ld is None else ld),
+                                  mean.ptr if mean is not None else None, scale.ptr if scale is not None else None,
+                                  len(widths) - 1, widths.ctypes.data, int(spec.activation), int(bool(spec.ln_in)),
+                                  int(bool(spec.ln_hidden)), int(bool(spec.head_activation)), params.ptr, params.size,
+                                  out.ptr, out.shape[1]), self.handle)
+        return out
+
     def eigh(self, a: DeviceArray, want_vectors: bool = True):
         n = a.shape[0]
         w = self.empty((n,), np.float64)

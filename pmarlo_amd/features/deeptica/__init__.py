@@ -1,3 +1,8 @@
-"""DeepTICA helpers that sit on the TICA path (mirror of pmarlo.features.deeptica): only the
-numpy-level eigenvalue estimator of the trainer is built here; the neural CV model itself stays
-PyTorch in the reference and is out of scope."""
+"""DeepTICA on the device (mirror of pmarlo.features.deeptica): inference with a trained network -- load the
+reference's bundle, forward pass and output whitening without the frames leaving the device (model.py) -- and the
+numpy-level eigenvalue estimator of the trainer (core/).  Training stays PyTorch in the reference and is out of
+scope."""
+
+from .model import DeepTICAModel, MLPSpec
+
+__all__ = ["DeepTICAModel", "MLPSpec"]
