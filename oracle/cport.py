@@ -42,6 +42,8 @@ def _load():
             C.c_void_p, C.c_void_p]
         _lib.oracle_gemm_fma.restype = None
         _lib.oracle_gemm_fma.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
+        _lib.oracle_lu_solve_fma.restype = C.c_int
+        _lib.oracle_lu_solve_fma.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         _lib.oracle_kmeans_fit.restype = C.c_int
         _lib.oracle_kmeans_fit.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_double,
                                            C.c_double, C.c_void_p, C.c_void_p]
@@ -122,3 +124,15 @@ def gemm_fma(A, B):
     Cm = np.empty((m, n), np.float64)
     _load().oracle_gemm_fma(A.ctypes.data, B.ctypes.data, Cm.ctypes.data, m, n, k)
     return Cm
+
+
+def lu_solve_fma(A, B):
+    """A X = B in msm_solve_f64's arithmetic (first maximal pivot, one fma per update) -> (LU, X, info).
+    info is 0 or the 1-based column without a pivot; LU and X then hold the state at that column."""
+    LU = np.array(A, dtype=np.float64, order="C")
+    X = np.array(B, dtype=np.float64, order="C")
+    n = LU.shape[0]
+    assert LU.shape == (n, n) and X.shape[0] == n and X.ndim in (1, 2)
+    nrhs = 1 if X.ndim == 1 else X.shape[1]
+    info = _load().oracle_lu_solve_fma(LU.ctypes.data, X.ctypes.data, n, nrhs)
+    return LU, X, int(info)

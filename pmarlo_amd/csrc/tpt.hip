@@ -284,8 +284,10 @@ msm_status msm_lump_macro(msm_ctx* ctx, const double* d_T, int64_t ldt, const do
     msm_status rs = msm_reserve_scratch(ctx, (size_t)n * n_macro * sizeof(double));
     if (rs != MSM_OK) return rs;
     double* rowflux = (double*)ctx->scratch;
-    hipLaunchKernelGGL(lump_rows_kernel, dim3(n), dim3(256), (size_t)4 * n_macro * sizeof(double), ctx->stream, d_T, ldt,
-                       d_pi, d_macro, n, n_macro, rowflux);
+    const size_t lds = (size_t)4 * n_macro * sizeof(double);   // one row of macro bins per wave: 128 KB at n_macro = 4096
+    if (lds > 48 * 1024)
+        MSM_HIP(ctx, hipFuncSetAttribute((const void*)lump_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(lump_rows_kernel, dim3(n), dim3(256), lds, ctx->stream, d_T, ldt, d_pi, d_macro, n, n_macro, rowflux);
     hipLaunchKernelGGL(lump_finish_kernel, dim3(n_macro), dim3(64), 0, ctx->stream, rowflux, d_pi, d_macro, n, n_macro,
                        d_T_macro, d_pi_macro);
     hipLaunchKernelGGL(normalise_vec_kernel, dim3(1), dim3(64), 0, ctx->stream, d_pi_macro, n_macro);
