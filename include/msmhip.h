@@ -299,7 +299,8 @@ msm_status msm_lagged_moments_onesided(msm_ctx* ctx, const void* d_x, msm_dtype 
  *   C0 = (M00 - sx sx'/T)/max(1, T-1), Ct = (M0t - sx sy'/T)/max(1, T-1);
  *   eigh(sym C0) with eigenvalues clipped at `clip` (the reference's NUMERIC_MIN_POSITIVE = 1e-12);
  *   S = C0^-1/2;  d_eigvals [F] = eigvalsh(sym(S Ct S')) in DESCENDING order (the caller takes the top n_out).
- * One launch, no host round trip; F <= 256. */
+ * No host round trip.  F <= 256: one launch; 256 < F <= 2048: the same steps on the device-wide block Jacobi (see
+ * msm_eigh); F > 2048: MSM_ERR_UNSUPPORTED. */
 msm_status msm_onesided_tica_eigenvalues(msm_ctx* ctx, const double* d_moments, int F, double clip,
                                          double* d_eigvals);
 
@@ -322,7 +323,10 @@ msm_status msm_moments_from_lagged(msm_ctx* ctx, const void* d_x, msm_dtype dtyp
  *   kinetic_map != 0: column i of R scaled by eigenvalue i.
  * Outputs: d_eigvals [F] (0 beyond rank), d_coeffs [F, F] row-major with column i
  * = i-th TICA component (0 beyond rank), d_mean [F] = symmetric mean in
- * standardised coordinates, d_rank int32 [1].  One launch, no host sync. */
+ * standardised coordinates, d_rank int32 [1].  No host sync.  F <= 256: one launch (a full-rank C00 is whitened by
+ * a Cholesky / LDL' factor instead of the first eigensolve, which gives the same eigenpairs).  256 < F <= 2048: the steps
+ * above, each spread over the device (block Jacobi eigensolves as in msm_eigh, multi-workgroup fp64 matrix-core
+ * products); the rank stays in device memory.  F > 2048: MSM_ERR_UNSUPPORTED. */
 msm_status msm_tica_solve(msm_ctx* ctx, const double* d_moments, const double* d_scale, int F,
                           double epsilon, int kinetic_map, double* d_eigvals, double* d_coeffs,
                           double* d_mean, int* d_rank);
@@ -338,7 +342,7 @@ msm_status msm_tica_solve(msm_ctx* ctx, const double* d_moments, const double* d
  * when any of its rank vectors fails the residual or orthogonality test; a failure that involves a vector this
  * entry does not form goes unseen here, the tridiagonal result is kept, and the kept pairs agree with
  * msm_tica_solve to solver accuracy (the bounds both meet), not bit for bit.
- * Every other case (F > 64, the Jacobi paths, 2 (n_lead + 2) >= rank, a tie in |eigenvalue| at the cut, an
+ * Every other case (F > 64 -- orders above 256 included --, the Jacobi paths, 2 (n_lead + 2) >= rank, a tie in |eigenvalue| at the cut, an
  * eigenvalue within 1e-6 of the norm of the vectors formed) computes all pairs and truncates: bits always equal. */
 msm_status msm_tica_solve_leading(msm_ctx* ctx, const double* d_moments, const double* d_scale, int F,
                                   double epsilon, int kinetic_map, double* d_eigvals, double* d_coeffs,
@@ -361,8 +365,12 @@ msm_status msm_project_finite(msm_ctx* ctx, const void* d_x, msm_dtype dtype, in
                               const double* d_mu, const double* d_inv_sigma, const double* d_mean2,
                               const double* d_w, int d, int64_t ldw, double* d_y, int64_t ldy, double* d_absmax);
 
-/* Symmetric eigendecomposition by parallel cyclic Jacobi (n <= 256), ascending
+/* Symmetric eigendecomposition by parallel cyclic Jacobi, ascending
  * eigenvalues d_w [n], eigenvectors in the columns of d_v [n, n] (may be NULL).
+ * Only the symmetric part of d_a is used.  n <= 256: one workgroup, one launch.  256 < n <= 2048: block Jacobi over
+ * the whole device (blocks of 32, 2 + 3 (ceil(n / 32) - 1) stream-ordered launches per sweep, convergence flag in
+ * device memory, no host sync; same results bit for bit on every call).  n > 2048: MSM_ERR_UNSUPPORTED.
+ * d_sweeps reports the sweeps taken (40: the iteration ran out).
  * Replaces np.linalg.eigh on the path (e.g. _estimate_top_eigenvalues,
  * S/features/deeptica/core/trainer_api.py:646-651). d_sweeps int32 [1] may be NULL. */
 msm_status msm_eigh(msm_ctx* ctx, const double* d_a, int n, double* d_w, double* d_v, int* d_sweeps);

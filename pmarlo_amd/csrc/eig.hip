@@ -1,8 +1,10 @@
 // Dense symmetric eigensolver (parallel cyclic Jacobi, one workgroup) and the
-// TICA solve built on it.  The matrices are F x F with F <= 256: this stage is
+// TICA solve built on it.  Up to F = 256 the matrices are small: this stage is
 // latency-bound, not bandwidth- or flop-bound, so the design
 // goal is "stay on the device, one launch": no host round trip sits between
-// the covariance pass and the projection pass.
+// the covariance pass and the projection pass.  Orders 257 .. 2048 are spread over
+// the whole device instead (block Jacobi, eig_large.h); the three entries at the end
+// of this file dispatch on the order.
 //
 // Jacobi: the n(n-1)/2 pivots of a sweep are visited in n-1 rounds of n/2
 // disjoint pairs (round-robin tournament).  Within a round all rotations are
@@ -1551,6 +1553,8 @@ msm_status launch_single_workgroup(msm_ctx* ctx, void (*kern)(Params...), size_t
 
 }  // namespace
 
+#include "eig_large.h"   // orders 257 .. 2048: the device-wide block Jacobi and the solves built on it
+
 extern "C" {
 
 msm_status msm_tica_solve(msm_ctx* ctx, const double* d_moments, const double* d_scale, int F, double epsilon,
@@ -1562,9 +1566,14 @@ msm_status msm_tica_solve_leading(msm_ctx* ctx, const double* d_moments, const d
                                   int kinetic_map, double* d_eigvals, double* d_coeffs, double* d_mean, int* d_rank,
                                   int n_lead) {
     if (!ctx) return MSM_ERR_INVALID;
-    MSM_REQUIRE(ctx, F >= 1 && F <= 2 * kMaxPairs, "msm_tica_solve: need 1 <= F <= %d (got %d)", 2 * kMaxPairs, F);
+    MSM_REQUIRE(ctx, F >= 1, "msm_tica_solve: need F >= 1 (got %d)", F);
+    if (F > kBjMaxOrder)
+        return msm_fail(ctx, MSM_ERR_UNSUPPORTED, "msm_tica_solve: F = %d exceeds the largest supported order %d", F, kBjMaxOrder);
     MSM_REQUIRE(ctx, epsilon >= 0.0, "msm_tica_solve: epsilon must be >= 0");
     MSM_REQUIRE(ctx, d_moments && d_eigvals && d_coeffs && d_mean && d_rank, "msm_tica_solve: NULL pointer");
+    if (F > 2 * kMaxPairs)
+        return bj_tica_solve(ctx, d_moments, d_scale, F, epsilon, kinetic_map, d_eigvals, d_coeffs, d_mean, d_rank,
+                             n_lead > 0 && n_lead < F ? n_lead : 0);
     const int ld = eig_ld(F);
     const size_t mat = (size_t)F * ld;
     const size_t need = (4 * mat + 3 * F) * sizeof(double) + (size_t)F * sizeof(int) + 64;
@@ -1586,9 +1595,12 @@ msm_status msm_tica_solve_leading(msm_ctx* ctx, const double* d_moments, const d
 
 msm_status msm_onesided_tica_eigenvalues(msm_ctx* ctx, const double* d_moments, int F, double clip, double* d_eigvals) {
     if (!ctx) return MSM_ERR_INVALID;
-    MSM_REQUIRE(ctx, F >= 1 && F <= 2 * kMaxPairs, "msm_onesided_tica_eigenvalues: need 1 <= F <= %d (got %d)",
-                2 * kMaxPairs, F);
+    MSM_REQUIRE(ctx, F >= 1, "msm_onesided_tica_eigenvalues: need F >= 1 (got %d)", F);
+    if (F > kBjMaxOrder)
+        return msm_fail(ctx, MSM_ERR_UNSUPPORTED, "msm_onesided_tica_eigenvalues: F = %d exceeds the largest supported order %d",
+                        F, kBjMaxOrder);
     MSM_REQUIRE(ctx, d_moments && d_eigvals && clip > 0.0, "msm_onesided_tica_eigenvalues: bad arguments");
+    if (F > 2 * kMaxPairs) return bj_onesided(ctx, d_moments, F, clip, d_eigvals);
     const int ld = eig_ld(F);
     const size_t mat = (size_t)F * ld;
     const size_t lds = 4 * mat * sizeof(double);
@@ -1606,8 +1618,11 @@ msm_status msm_onesided_tica_eigenvalues(msm_ctx* ctx, const double* d_moments, 
 
 msm_status msm_eigh(msm_ctx* ctx, const double* d_a, int n, double* d_w, double* d_v, int* d_sweeps) {
     if (!ctx) return MSM_ERR_INVALID;
-    MSM_REQUIRE(ctx, n >= 1 && n <= 2 * kMaxPairs, "msm_eigh: need 1 <= n <= %d (got %d)", 2 * kMaxPairs, n);
+    MSM_REQUIRE(ctx, n >= 1, "msm_eigh: need n >= 1 (got %d)", n);
+    if (n > kBjMaxOrder)
+        return msm_fail(ctx, MSM_ERR_UNSUPPORTED, "msm_eigh: n = %d exceeds the largest supported order %d", n, kBjMaxOrder);
     MSM_REQUIRE(ctx, d_a && d_w, "msm_eigh: NULL pointer");
+    if (n > 2 * kMaxPairs) return bj_eigh(ctx, d_a, n, d_w, d_v, d_sweeps);
     const int ld = eig_ld(n);
     const size_t mat = (size_t)n * ld;
     msm_status rs = msm_reserve_scratch(ctx, 2 * mat * sizeof(double) + (size_t)n * sizeof(int) + 64);

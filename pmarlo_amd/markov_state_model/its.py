@@ -157,14 +157,14 @@ def deterministic_its_from_counts(counts: np.ndarray, lag: int, n_timescales: in
     LAPACK then reads the lower triangle only.  The quirk's values are therefore the eigenvalues of the symmetric
     matrix built from the lower triangle of T, ordered by decreasing magnitude (deeptime), the reported
     eigenvalues re-sorted by decreasing real part (:763) while the timescales keep deeptime's order (:778-787).
-    Solved by msm_eigh (k <= 256)."""
+    Solved by msm_eigh (k <= 2048)."""
     C = np.asarray(counts, dtype=np.float64)
     n = int(n_timescales)
     ev, ts = np.zeros(n), np.full(n, np.nan)
     k = C.shape[0]
     if n > 0 and k > 0 and reference_quirk:
-        if k > 256:
-            raise NotImplementedError("reference_quirk=True solves a dense k x k symmetric problem on the device: k <= 256")
+        if k > 2048:
+            raise NotImplementedError("reference_quirk=True solves a dense k x k symmetric problem on the device: k <= 2048")
         eng = get_engine()
         Crev = 0.5 * (C + C.T)
         row = Crev.sum(axis=1, keepdims=True)
