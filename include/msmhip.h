@@ -669,6 +669,50 @@ msm_status msm_spectrum_powered(msm_ctx* ctx, const double* d_T, const double* d
 msm_status msm_reversible_mle(msm_ctx* ctx, const double* d_counts, int n, int ld, double maxerr, int maxiter,
                               double* d_T, int ldt, double* d_pi, int* h_iterations, double* h_err);
 
+/* The same estimate for `batch` matrices of RAW resampled counts in one launch, each with its own active set and its
+ * own iteration count: what KineticImportanceScore._rebuild_msm (S/conformations/kinetic_importance.py:278-315) does
+ * per bootstrap sample -- ensure_connected_counts (S/utils/msm_utils.py:129-167), then deeptime's
+ * MaximumLikelihoodMSM(reversible=True), absent here (parity unpinned).  No host round trip; plain launch on the
+ * context's stream, capturable once the scratch has been reserved by an eager call of the same shape.
+ *   d_counts     int64 [batch, k, k], msm_combine_counts' output
+ *   alpha        prior added to every cell of the active block (ensure_connected_counts: 1e-3), >= 0
+ * Per matrix: the active set is {i : rowsum_i + colsum_i > 1e-12} in ascending order (n of them); the iteration of
+ * msm_reversible_mle runs on C[active, active] + alpha from the row sums of C + C', normalised every step, and stops
+ * at the FIRST iteration with max_i |x_i - x_i'| / ((x_i + x_i')/2) <= maxerr, or at maxiter (checked every
+ * iteration, not in blocks as msm_reversible_mle does).
+ *   d_T          f64, matrix b at d_T + b*t_stride with row stride ld >= k: the n x n estimate packed in the top-left
+ *                corner, zeros in the rest of the k x k slot (the layout msm_spectrum takes with d_n = d_n_active)
+ *   d_pi         f64 [batch, k]: the first n entries, 0 after them
+ *   d_active     int32 [batch, k]: packed index -> state for the first n entries, -1 after them
+ *   d_n_active   int32 [batch]
+ *   d_iterations int32 [batch]
+ *   d_err        f64 [batch]: the stopping measure of the last iteration
+ * A matrix with an empty active set reports n = 0, 0 iterations, err = 0 and a zero slot.  A matrix that holds a
+ * negative count, or whose iterate turns NaN, reports err = +inf (with a negative count: 0 iterations, zero slot and
+ * zero pi); the other matrices of the batch are unaffected.
+ * One workgroup of 1024 threads per matrix; all sums run in an order fixed by the matrix alone, so a matrix has the
+ * same bits in any batch.  k <= msm_reversible_mle_batched_lds_max_n() keeps the symmetrised block in LDS; above,
+ * it is streamed from slab b of the context scratch (msm_reversible_mle_batched_scratch_bytes tells the caller how
+ * much a batch takes, so that it can split one).  k <= 2048 (MSM_ERR_UNSUPPORTED above). */
+int msm_reversible_mle_batched_lds_max_n(void);
+size_t msm_reversible_mle_batched_scratch_bytes(int k, int batch);
+msm_status msm_reversible_mle_batched(msm_ctx* ctx, const int64_t* d_counts, int k, int batch, double alpha,
+                                      double maxerr, int maxiter, double* d_T, int64_t t_stride, int ld, double* d_pi,
+                                      int32_t* d_active, int32_t* d_n_active, int32_t* d_iterations, double* d_err);
+
+/* Kinetic importance scores of a batch: KIS(i) = pi_i * sum_{m=1..k_slow} phi_m(i)^2 over the slow left eigenvectors
+ * (KineticImportanceScore.compute, S/conformations/kinetic_importance.py:76-80), scattered back to the full state
+ * space.
+ *   d_vecs     f64 [batch, n_vecs, k]: msm_spectrum's d_vecs (row 0 the stationary vector), n_vecs >= k_slow + 1
+ *   d_pi       f64 [batch, k], d_active int32 [batch, k], d_n_active int32 [batch]: packed as
+ *              msm_reversible_mle_batched writes them
+ *   d_scores   f64 [batch, k] OVERWRITTEN: scores[active[a]] = pi[a] * sum_m vecs[m][a]^2, 0 at inactive states
+ *   d_info     int32 [batch] OVERWRITTEN: 0; 1 when n_active <= k_slow (all scores 0); 2 when a needed vector row
+ *              holds NaN (a complex pair; the scores of such entries stay 0) */
+msm_status msm_kis_scores(msm_ctx* ctx, const double* d_vecs, int n_vecs, int k, int batch, const double* d_pi,
+                          const int32_t* d_active, const int32_t* d_n_active, int k_slow, double* d_scores,
+                          int32_t* d_info);
+
 /* Posterior samples of a mode-1 estimate for the implied-timescale confidence intervals
  * (ITSMixin._its_compute_for_single_lag, S/markov_state_model/_its.py:272-357, which asks
  * deeptime's BayesianMSM for n_samples matrices; that sampler's stream is not reproducible, so

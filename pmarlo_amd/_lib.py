@@ -143,6 +143,11 @@ _PROTOTYPES: dict[str, tuple] = {
                                                          _vp, _i64, _i32, _vp]),
     "msm_active_counts": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _f64, _vp]),
     "msm_reversible_mle": (_i32, [_vp, _vp, _i32, _i32, _f64, _i32, _vp, _i32, _vp, _vp, _vp]),
+    "msm_reversible_mle_batched_lds_max_n": (_i32, []),
+    "msm_reversible_mle_batched_scratch_bytes": (_sz, [_i32, _i32]),
+    "msm_reversible_mle_batched": (_i32, [_vp, _vp, _i32, _i32, _f64, _f64, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _vp,
+                                          _vp]),
+    "msm_kis_scores": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp]),
     "msm_philox4x32": (_i32, [_vp, C.c_uint64, _vp, _vp]),
     "msm_gemm_f64": (_i32, [_vp, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _i64]),
     "msm_diff_norms": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _i32, _vp]),

@@ -1,5 +1,6 @@
-"""pmarlo.conformations on the MI355X engine: representative frames of conformational states and
-trajectory-bootstrap error bars."""
+"""pmarlo.conformations on the MI355X engine: representative frames of conformational states,
+trajectory-bootstrap error bars and kinetic importance scores."""
+from .kinetic_importance import KineticImportanceScore, KISResult  # noqa: F401
 from .representative_picker import (  # noqa: F401
     FrameIndexLookup,
     RepresentativeFrame,

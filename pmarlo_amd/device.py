@@ -1092,6 +1092,21 @@ class Engine:
         Neither the per-trajectory counts nor the resampled counts need fit at once: both are walked in chunks of
         at most chunk_bytes (at least one matrix), the resamples on the outside, so that with several chunks of
         both the trajectories are counted again per chunk of resamples."""
+        n_boot = np.shape(mult)[0] if np.ndim(mult) == 2 else 0
+        T = rowsum = None
+        for b, nb, counts in self.bootstrap_counts(labels, starts, stops, k, lag, mult, chunk_bytes=chunk_bytes):
+            if T is None:
+                T = self.empty((n_boot, k, k), np.float64)
+                rowsum = self.empty((n_boot, k), np.int64)
+            self.row_normalise_batched(counts, T.view((nb, k, k), offset_elems=b * k * k),
+                                       rowsum.view((nb, k), offset_elems=b * k))
+        return T, rowsum
+
+    def bootstrap_counts(self, labels: DeviceArray, starts, stops, k: int, lag: int, mult: np.ndarray, *,
+                         chunk_bytes: int = 1 << 28):
+        """The resampled transition counts behind bootstrap_transition_matrices, a chunk of resamples at a time:
+        yields (b, nb, counts) with counts int64 [nb, k, k] the counts of samples b .. b + nb - 1.  The array is
+        reused for the next chunk: consume it before advancing."""
         starts, stops = self._seg_ptrs(starts, stops)
         mult = np.ascontiguousarray(mult, np.int32)
         n_seg = len(starts)
@@ -1101,8 +1116,6 @@ class Engine:
         seg_step = max(1, min(n_seg, int(chunk_bytes) // mat))
         boot_step = max(1, min(n_boot, int(chunk_bytes) // mat))
         mult_d = self.to_device(mult)
-        T = self.empty((n_boot, k, k), np.float64)
-        rowsum = self.empty((n_boot, k), np.int64)
         seg_counts = self.empty((seg_step, k, k), np.int64)
         counts = self.empty((boot_step, k, k), np.int64)
         counted = None                       # the chunk of trajectories seg_counts holds
@@ -1117,9 +1130,7 @@ class Engine:
                     counted = s
                 self.combine_counts(seg_counts.view((ns, k, k)), mult_d.view((nb, n_seg), offset_elems=b * n_seg),
                                     seg0=s, out=counts.view((nb, k, k)), accumulate=s > 0)
-            self.row_normalise_batched(counts.view((nb, k, k)), T.view((nb, k, k), offset_elems=b * k * k),
-                                       rowsum.view((nb, k), offset_elems=b * k))
-        return T, rowsum
+            yield b, nb, counts.view((nb, k, k))
 
     # -- free-energy surfaces ---------------------------------------------------
     def weighted_stats(self, x: DeviceArray, col: int = 0, weights: DeviceArray | None = None) -> np.ndarray:
@@ -1398,6 +1409,46 @@ class Engine:
         check(lib.msm_reversible_mle(self.handle, counts.ptr, n, counts.shape[1], float(maxerr), int(maxiter), T.ptr, n,
                                      pi.ptr, ctypes.byref(it), ctypes.byref(err)), self.handle)
         return {"T": T, "pi": pi, "iterations": it.value, "err": err.value}
+
+    def reversible_mle_batched(self, counts: DeviceArray, *, alpha: float = 1e-3, maxerr: float = 1e-8,
+                               maxiter: int = 1_000_000, chunk_bytes: int = 1 << 30) -> dict:
+        """msm_reversible_mle_batched on raw int64 counts [batch, k, k]: per matrix the active set, the reversible
+        estimate of counts[active, active] + alpha and its stationary vector.  On the device: T f64 [batch, k, k]
+        (the n_active x n_active block packed top-left, zeros around it: what spectrum() takes with n=n_active),
+        pi f64 [batch, k], active int32 [batch, k] (-1 padding), n_active int32 [batch]; on the host: iterations
+        int32 [batch] and err f64 [batch] (inf: a negative count or a NaN iterate).  Above the LDS boundary the batch
+        is split so that the scratch stays within chunk_bytes; the results do not depend on the split."""
+        if counts.dtype != np.int64 or len(counts.shape) != 3 or counts.shape[1] != counts.shape[2]:
+            raise TypeError("counts must be int64 [batch, k, k]")
+        batch, k = counts.shape[0], counts.shape[-1]
+        T, pi = self.empty((batch, k, k), np.float64), self.empty((batch, k), np.float64)
+        active, n_active = self.empty((batch, k), np.int32), self.empty((batch,), np.int32)
+        its, err = self.empty((batch,), np.int32), self.empty((batch,), np.float64)
+        per_sample = int(lib.msm_reversible_mle_batched_scratch_bytes(k, 1))
+        step = batch if per_sample == 0 else max(1, min(batch, int(chunk_bytes) // per_sample))
+        for b in range(0, batch, step):
+            m = min(step, batch - b)
+            check(lib.msm_reversible_mle_batched(self.handle, counts.ptr + 8 * b * k * k, k, m, float(alpha), float(maxerr),
+                                                 int(maxiter), T.ptr + 8 * b * k * k, k * k, k, pi.ptr + 8 * b * k,
+                                                 active.ptr + 4 * b * k, n_active.ptr + 4 * b, its.ptr + 4 * b,
+                                                 err.ptr + 8 * b), self.handle)
+        return {"T": T, "pi": pi, "active": active, "n_active": n_active, "iterations": its.to_host(),
+                "err": err.to_host()}
+
+    def kis_scores(self, vecs: DeviceArray, pi: DeviceArray, active: DeviceArray, n_active: DeviceArray,
+                   k_slow: int) -> tuple[DeviceArray, np.ndarray]:
+        """msm_kis_scores: scores f64 [batch, k] on the device (pi * sum of squares of the left eigenvectors
+        1 .. k_slow of spectrum()'s vecs [batch, n_vecs, k], scattered through active; 0 at inactive states) and
+        info int32 [batch] on the host (1: n_active <= k_slow, 2: a needed vector is a complex pair)."""
+        batch, n_vecs, k = vecs.shape
+        if tuple(pi.shape) != (batch, k) or tuple(active.shape) != (batch, k) or n_active.size != batch:
+            raise ValueError("kis_scores: pi and active must be [batch, k] and n_active [batch]")
+        if active.dtype != np.int32 or n_active.dtype != np.int32:
+            raise TypeError("active and n_active must be int32")
+        scores, info = self.empty((batch, k), np.float64), self.empty((batch,), np.int32)
+        check(lib.msm_kis_scores(self.handle, vecs.ptr, n_vecs, k, batch, pi.ptr, active.ptr, n_active.ptr, int(k_slow),
+                                 scores.ptr, info.ptr), self.handle)
+        return scores, info.to_host()
 
     def active_counts(self, counts: DeviceArray, active: DeviceArray, n_active: DeviceArray, n: int, *,
                       alpha: float) -> DeviceArray:
