@@ -860,6 +860,51 @@ msm_status msm_lump_macro(msm_ctx* ctx, const double* d_T, int64_t ldt, const do
 msm_status msm_macro_mfpt(msm_ctx* ctx, const double* d_T, int64_t ldt, int n, double* d_mfpt,
                           int32_t* d_info);
 
+/* ---- dominant reactive pathways through the net flux (csrc/pathways.hip) ----------------------------
+ * Replaces the host walk behind flux.pathways(fraction, maxiter) in TPTAnalysis.analyze
+ * (S/conformations/tpt_analysis.py:122-135) and TPTMixin.pathway_decomposition (S/markov_state_model/
+ * _tpt.py:162-211); the rule is that of pmarlo_amd/markov_state_model/tpt.py::pathway_decomposition / _widest_path.
+ *
+ * Work matrix G of order N = n + 2: G[:n, :n] = d_net (f64 [n, ldn], finite and >= 0); the virtual source n has
+ * G[n][a] = sum_j net[a][j] for every source a (d_role[a] == 1), the virtual sink n + 1 has G[b][n+1] =
+ * sum_i net[i][b] for every sink b (d_role[b] == 2); total = sum_a G[n][a].  Each of the three sums is ONE
+ * sequential fp64 chain in ascending index.
+ * One path is a max-min Dijkstra from n to n + 1: width[n] = +inf, every other width 0; pop the not-done node i of
+ * largest width, the lowest index on equal widths; no path when that width is 0; stop when n + 1 is popped;
+ * otherwise, for every not-done j with min(width[i], G[i][j]) > width[j] (strictly), set width[j] to it and
+ * prev[j] = i.  cap = width[n+1].  The decomposition ends with status NO_PATH when there is no path or
+ * cap <= 1e-14 * total.  Otherwise G[a][b] = max(0.0, G[a][b] - cap) along the path, the path without its virtual
+ * ends is appended, got += cap, and the loop continues while
+ *     n_paths < maxiter  &&  total > 0  &&  got < fraction * total * (1.0 - 1e-14)      (products left to right);
+ * when it does not, the status is NO_PATH for total <= 0, else FRACTION for the collected share, else MAXITER.
+ * Only min, max, compares, one subtraction and one addition touch the data: results are fixed bit for bit.
+ *
+ * The entry is resumable, so that no launch runs long: the state (G, got, total, path count, status) lives in
+ * d_work (msm_reactive_pathways_work_bytes(n) bytes, 64-byte header + G).
+ *   msm_reactive_pathways_begin builds G and the header and clears the outputs; header.bad != 0 afterwards
+ *     means d_net holds a negative, infinite or NaN entry (the caller must not run then).
+ *   msm_reactive_pathways_run is ONE launch of ONE workgroup that takes at most launch_paths paths (0: the default
+ *     msm_reactive_pathways_launch_paths(n) = MSM_PATHWAYS_LAUNCH_POPS / (n + 2), at least 1: a search pops at
+ *     most n + 2 nodes) and returns; the caller reads the first 32 bytes of d_work, {f64 got, f64 total,
+ *     i32 n_paths, i32 status, i32 bad, i32 pad}, and calls again while status == MSM_PATHWAYS_RUNNING, with the
+ *     same fraction / maxiter / keep and outputs.
+ * Outputs: d_caps f64 [maxiter], entry p the capacity of path p, for all paths found; d_paths int32 [keep, n] and
+ * d_len int32 [keep]: the nodes of the first `keep` paths, padded with -1 (a path visits a node at most once).
+ * n <= MSM_PATHWAYS_MAX_N, above: MSM_ERR_UNSUPPORTED naming both numbers. */
+#define MSM_PATHWAYS_MAX_N 2048
+#define MSM_PATHWAYS_LAUNCH_POPS 131072   /* node pops a launch may take at most */
+#define MSM_PATHWAYS_RUNNING 0
+#define MSM_PATHWAYS_FRACTION 1           /* the requested share of the total flux is collected */
+#define MSM_PATHWAYS_NO_PATH 2            /* no path left, or its capacity is under the floor */
+#define MSM_PATHWAYS_MAXITER 3            /* maxiter paths were taken */
+size_t msm_reactive_pathways_work_bytes(int n);
+int msm_reactive_pathways_launch_paths(int n);
+msm_status msm_reactive_pathways_begin(msm_ctx* ctx, const double* d_net, int64_t ldn, const int32_t* d_role, int n,
+                                       int maxiter, int keep, void* d_work, double* d_caps, int32_t* d_paths,
+                                       int32_t* d_len);
+msm_status msm_reactive_pathways_run(msm_ctx* ctx, void* d_work, int n, double fraction, int maxiter, int keep,
+                                     int launch_paths, double* d_caps, int32_t* d_paths, int32_t* d_len);
+
 /* ---- trajectory bootstrap in batch (csrc/bootstrap.hip) ----------------------------------------
  * The device side of UncertaintyQuantifier (S/conformations/uncertainty.py:31-261): every bootstrap sample
  * resamples whole trajectories with replacement and rebuilds the MSM (_rebuild_msm, :506-530).  Counts are

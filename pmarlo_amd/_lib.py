@@ -28,6 +28,9 @@ REP_SELECT_SMALLEST, REP_SELECT_DIVERSE = 0, 1
 SIL_SEG_LEN, SIL_TILE_I = 1024, 128
 # trajectory bootstrap (MSM_COMBINE_MAX_SEG, MSM_FLUX_LDS_MAX_N in include/msmhip.h)
 COMBINE_MAX_SEG, FLUX_LDS_MAX_N = 32, 127
+# reactive pathways (MSM_PATHWAYS_* in include/msmhip.h): most states, the status words of the resumable entry
+PATHWAYS_MAX_N = 2048
+PATHWAYS_RUNNING, PATHWAYS_FRACTION, PATHWAYS_NO_PATH, PATHWAYS_MAXITER = range(4)
 # msm_mlp_forward's envelope: widest layer, most outputs, most Linear layers
 MLP_MAX_WIDTH, MLP_MAX_OUT, MLP_MAX_LINEAR = 256, 64, 8
 
@@ -164,6 +167,10 @@ _PROTOTYPES: dict[str, tuple] = {
     "msm_reactive_flux": (_i32, [_vp, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "msm_lump_macro": (_i32, [_vp, _vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp]),
     "msm_macro_mfpt": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp]),
+    "msm_reactive_pathways_work_bytes": (_sz, [_i32]),
+    "msm_reactive_pathways_launch_paths": (_i32, [_i32]),
+    "msm_reactive_pathways_begin": (_i32, [_vp, _vp, _i64, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "msm_reactive_pathways_run": (_i32, [_vp, _vp, _i32, _f64, _i32, _i32, _i32, _vp, _vp, _vp]),
     "msm_combine_counts": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i64, _vp, _i32]),
     "msm_row_normalise_batched": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp]),
     "msm_reactive_flux_batched_scratch_bytes": (_sz, [_i32, _i32, _i32]),

@@ -35,7 +35,8 @@ scipy's eigs; neither is present, so parity with the reference's own output is u
 a numpy restatement of the rules above.
 
 Not ported: hyperparameter_ensemble_stability and _recluster (they re-cluster with scikit-learn's
-MiniBatchKMeans(random_state=42), whose stream cannot be reproduced); finder.py and state_detection.py."""
+MiniBatchKMeans(random_state=42), whose stream cannot be reproduced).  finder.py and state_detection.py are ported
+(finder.py, state_detection.py of this package)."""
 
 from __future__ import annotations
 

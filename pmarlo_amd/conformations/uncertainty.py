@@ -27,7 +27,8 @@ parity with the reference's own output is unpinned.  The tests hold this module 
 above.
 
 Not ported: hyperparameter_ensemble (reclusters with scikit-learn), chapman_kolmogorov_validation (the engine's
-markov_state_model.ck covers its numerics) and the helpers only they use (_recluster, _coarse_grain_T); finder.py."""
+markov_state_model.ck covers its numerics) and the helpers only they use (_recluster, _coarse_grain_T).  finder.py,
+which drives bootstrap_tpt and bootstrap_free_energies, is ported (finder.py of this package)."""
 
 from __future__ import annotations
 

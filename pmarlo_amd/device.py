@@ -162,6 +162,7 @@ class Engine:
         self._pool: dict[int, list[int]] = {}
         self._pool_bytes = 0
         self._pool_cap = int(os.environ.get("MSM_POOL_BYTES", str(16 << 30)))
+        self.last_pathway_launches = 0      # launches the latest reactive_pathways call took
 
     # -- plumbing -----------------------------------------------------------
     @staticmethod
@@ -1014,6 +1015,53 @@ class Engine:
                                     gross.ptr if gross is not None else None, net.ptr if net is not None else None,
                                     tot.ptr if tot is not None else None, info.ptr), self.handle)
         return {"qplus": qp, "qminus": qm, "gross": gross, "net": net, "totals": tot, "info": info.to_host()}
+
+    def reactive_pathways(self, net: DeviceArray, role, *, fraction: float = 0.99, maxiter: int = 10_000, keep: int = 5,
+                          launch_paths: int | None = None):
+        """Dominant reactive pathways through the net flux `net` f64 [n, n] on the device (reactive_flux's
+        out["net"], or any finite non-negative matrix); role[i] = 0 intermediate, 1 source, 2 sink.  Returns
+        (paths, caps, status): the node lists of the first `keep` paths, the capacities f64 of ALL paths found and
+        one of _lib.PATHWAYS_FRACTION / PATHWAYS_NO_PATH / PATHWAYS_MAXITER (msm_reactive_pathways_* in
+        include/msmhip.h has the rule).  The walk is a chain of bounded launches, at most `launch_paths` paths each
+        (None: the library's default for this n); the result does not depend on that number.  last_pathway_launches
+        holds the number of launches taken."""
+        if len(net.shape) != 2 or net.shape[0] != net.shape[1] or net.dtype != np.float64:
+            raise ValueError(f"the net flux must be a square float64 matrix, got {net.dtype} {net.shape}")
+        n = net.shape[0]
+        role = np.ascontiguousarray(role, np.int32).ravel()
+        if role.size != n or np.any((role < 0) | (role > 2)):
+            raise ValueError(f"role must hold {n} entries from {{0, 1, 2}}")
+        if not np.any(role == 1) or not np.any(role == 2):
+            raise ValueError("Source and sink must each contain at least one state")
+        fraction, maxiter, keep = float(fraction), int(maxiter), int(keep)
+        if not 0.0 < fraction <= 1.0:
+            raise ValueError("fraction must be in (0, 1]")
+        if maxiter < 0 or keep < 0 or (launch_paths is not None and int(launch_paths) < 1):
+            raise ValueError("maxiter and keep must not be negative, launch_paths at least 1")
+        work = self.empty((int(lib.msm_reactive_pathways_work_bytes(n)) // 8,), np.float64)
+        caps = self.empty((max(maxiter, 1),), np.float64)
+        paths, lens = self.empty((max(keep, 1), n), np.int32), self.empty((max(keep, 1),), np.int32)
+        rd = self.to_device(role)
+        check(lib.msm_reactive_pathways_begin(self.handle, net.ptr, n, rd.ptr, n, maxiter, keep, work.ptr, caps.ptr,
+                                              paths.ptr, lens.ptr), self.handle)
+
+        def header():
+            h = work.view((32,), np.uint8).to_host()
+            return int(h[16:20].view(np.int32)[0]), int(h[20:24].view(np.int32)[0]), int(h[24:28].view(np.int32)[0])
+
+        n_paths, status, bad = header()
+        if bad:
+            raise ValueError("the net flux holds a negative, infinite or NaN entry")
+        self.last_pathway_launches = 0
+        while status == _lib.PATHWAYS_RUNNING:
+            check(lib.msm_reactive_pathways_run(self.handle, work.ptr, n, fraction, maxiter, keep,
+                                                0 if launch_paths is None else int(launch_paths), caps.ptr, paths.ptr,
+                                                lens.ptr), self.handle)
+            self.last_pathway_launches += 1
+            n_paths, status, _ = header()
+        kept = min(keep, n_paths)
+        nodes, length = paths.to_host(), lens.to_host()
+        return ([nodes[p, :length[p]].tolist() for p in range(kept)], caps.to_host()[:n_paths].copy(), status)
 
     def lump_macro(self, T: DeviceArray, pi: DeviceArray, macro: np.ndarray, n_macro: int):
         n = T.shape[0]
