@@ -434,8 +434,80 @@ msm_status msm_mlp_forward(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64
                            int activation, int ln_in, int ln_hidden, int head_activation, const float* d_params,
                            size_t n_params, double* d_out, int64_t ldo);
 
+/* ---- DeepTICA training: one step of the reference's curriculum trainer (S/ml/deeptica/trainer.py:1020-1070) ----
+ *
+ * VAMP-2 loss of VAMP2Loss.forward (S/features/deeptica/losses.py) with uniform weights 1/m, the only case the
+ * trainer uses, and its closed-form gradient with respect to the outputs.  d_y0, d_yt [m, ld] f64: the network's
+ * outputs at the t and the tau frames, n_out <= 64 columns each.
+ *   C00, Ctt, C0t: centred covariances of the outputs, correction 0;
+ *   A = sym((1 - alpha) C00 + (alpha mu + max(mu eps, mu eps_abs)) I), mu = max(tr C00, 1e-12) / n_out; B likewise
+ *       from Ctt; alpha is clamped to [0, 1], eps_abs and cond_reg to >= 0;
+ *   cond A = max(l_max, 1e-12) / max(l_min, 1e-12) from the spectrum of A (cyclic Jacobi);
+ *   A = L_A L_A' by Cholesky with the reference's jitter ladder (A + total I; total 0, then 1e-8, growth 10, five
+ *       tries); score = |L_A^-1 C0t L_B^-T|_F^2; penalty = cond_reg (log max(1, cond A) + log max(1, cond B));
+ *       loss = -score + penalty.
+ * Gradient, with Ai, Bi the inverses of the factorised A, B and C = C0t:
+ *   G_A = Ai C Bi C' Ai + cond_reg (v_max v_max' / l_max - v_min v_min' / l_min), G_B likewise, G_0t = -2 Ai C Bi,
+ *   G_00 = (1 - alpha) G_A + (c / n_out) tr(G_A) I, c = alpha + max(eps, eps_abs); G_tt likewise;
+ *   dloss/dZ0 = (2 Y0 G_00 + Yt G_0t') / m, dloss/dZt = (2 Yt G_tt + Y0 G_0t) / m with centred Y0, Yt.
+ *   The penalty's part is absent when cond <= 1 (n_out = 1, and the clamp at 1) and, per eigenvalue, on the 1e-12
+ *   floor; the trace part is absent when the trace sits on its floor.
+ * d_stats [MSM_VAMP2_STATS] f64: [0] loss, [1] score, [2] penalty, [3] cond_C00, [4] cond_Ctt, [5] eig_C00_min,
+ *   [6] eig_C00_max, [7] eig_Ctt_min, [8] eig_Ctt_max, [9] 1 when a Cholesky factorisation failed after the five
+ *   tries (the reference raises; loss and score are then NaN), [10..15] zero; then var_z0, var_zt, mean_z0, mean_zt,
+ *   64 entries each, the first n_out of each written.
+ * d_grad0, d_gradt [m, ldg] f64 or both NULL.  d_work: msm_vamp2_workspace(m, n_out) bytes (0: outside the
+ * envelope).  Moments are summed per chunk of 256 frames on the matrix cores and the chunks added in ascending
+ * order, the dense algebra runs in one workgroup: equal inputs give equal bits.  Plain launches on the context's
+ * stream, no host synchronisation. */
+#define MSM_VAMP2_STATS 272
+size_t msm_vamp2_workspace(int64_t m, int n_out);
+msm_status msm_vamp2_loss(msm_ctx* ctx, const double* d_y0, const double* d_yt, int64_t m, int n_out, int64_t ld,
+                          double eps, double eps_abs, double alpha, double cond_reg, double* d_work,
+                          double* d_stats, double* d_grad0, double* d_gradt, int64_t ldg);
+
+/* Loss and parameter gradient of one batch of lagged pairs.  The network, its packed parameters and the scaler
+ * are msm_mlp_forward's; d_x [n, ld] is the resident frame array, and the batch is 2m slots: slot s < m is row
+ * d_idx_t[s], slot m + s is row d_idx_tau[s] (int64; a row outside [0, n) is not read and makes the loss NaN).
+ * Training mode (model.py:72-107, 355-368): Z, input LayerNorm, input dropout; per Linear: Linear, LayerNorm,
+ * activation, hidden dropout; the head gets the activation when head_activation is set and no dropout.
+ * Everything after the fp32 rounding of Z is fp64.
+ * Dropout: h_dropout [n_linear] (host): probability of site 0 (the inputs) and of site i (after the activation of
+ *   Linear i - 1); NULL: evaluation mode.  0 <= p < 1, MSM_ERR_INVALID otherwise.  An element (site, slot, column) is
+ *   kept iff word (column & 3) of Philox4x32-10 with key = seed and counter = {step, site, slot, column >> 2} is
+ *   >= floor(p 2^32); every element is multiplied by 1 / (1 - p) if kept and by 0 otherwise, in fp64.  step < 2^32.
+ *   The stream is not torch's.
+ * With dropout off the outputs are bit-identical to msm_mlp_forward on the gathered rows.
+ * d_stats as msm_vamp2_loss.  d_grad [n_params] f64 or NULL (no backward pass): dloss/dparameter in the packed
+ * order, by the usual adjoints.  d_out [2m, ldo] f64 or NULL: the outputs by slot.  d_work: at least
+ * msm_mlp_train_workspace(...) bytes (0: outside the envelope), given in work_bytes.
+ * Parameter gradients are summed over the slots per chunk of 256 on the matrix cores, the chunks added in
+ * ascending order; no floating-point atomics: equal inputs give equal bits.
+ * Envelope: msm_mlp_forward's, and 2 <= m <= 2^24; MSM_ERR_UNSUPPORTED beyond, naming the number. */
+size_t msm_mlp_train_workspace(int64_t m, int n_linear, const int32_t* h_widths, int ln_in, int ln_hidden,
+                               int head_activation);
+msm_status msm_mlp_loss_grad(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n, int F, int64_t ld,
+                             const double* d_mean, const double* d_scale, int n_linear, const int32_t* h_widths,
+                             int activation, int ln_in, int ln_hidden, int head_activation, const float* d_params,
+                             size_t n_params, const int64_t* d_idx_t, const int64_t* d_idx_tau, int64_t m,
+                             const double* h_dropout, uint64_t seed, uint64_t step, double eps, double eps_abs,
+                             double alpha, double cond_reg, double* d_work, size_t work_bytes, double* d_stats,
+                             double* d_grad, double* d_out, int64_t ldo);
+
+/* Gradient clip (trainer.py:1048-1060, torch's clip_grad_norm_) and one step of torch's AdamW with a single
+ * parameter group, all in fp64:
+ *   norm = |g|_2; clip > 0: g <- g min(1, clip / (norm + 1e-6)); clip <= 0: none;
+ *   p <- p (1 - lr wd); m <- beta1 m + (1 - beta1) g; v <- beta2 v + (1 - beta2) g^2;
+ *   p <- p - (lr / (1 - beta1^step)) m / (sqrt(v) / sqrt(1 - beta2^step) + eps); step counts from 1.
+ * d_params [n] f32 is rounded once; d_m, d_v [n] f64.  d_out [4] f64: norm, norm after the clip, 1 when the norm
+ * is not finite, the clip coefficient.  Divergence from the reference: a non-finite norm skips the update (p, m, v
+ * untouched) and raises the flag; the reference would poison the parameters. */
+msm_status msm_adamw_step(msm_ctx* ctx, float* d_params, const double* d_grad, double* d_m, double* d_v, int64_t n,
+                          int64_t step, double lr, double beta1, double beta2, double eps, double weight_decay,
+                          double clip, double* d_out);
+
 /* ------------------------------------------------------------------ */
-/* k-means                                                              */
+/* k-means                                                          */
 /* ------------------------------------------------------------------ */
 
 /* Assign every frame to its nearest centre.

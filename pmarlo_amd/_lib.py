@@ -33,6 +33,8 @@ PATHWAYS_MAX_N = 2048
 PATHWAYS_RUNNING, PATHWAYS_FRACTION, PATHWAYS_NO_PATH, PATHWAYS_MAXITER = range(4)
 # msm_mlp_forward's envelope: widest layer, most outputs, most Linear layers
 MLP_MAX_WIDTH, MLP_MAX_OUT, MLP_MAX_LINEAR = 256, 64, 8
+# msm_vamp2_loss's stats block (MSM_VAMP2_STATS): 16 scalars, then var_z0, var_zt, mean_z0, mean_zt of 64 entries
+VAMP2_STATS = 16 + 4 * MLP_MAX_OUT
 
 
 class MsmError(RuntimeError):
@@ -101,6 +103,13 @@ _PROTOTYPES: dict[str, tuple] = {
     "msm_hstack_f64": (_i32, [_vp, _vp, _i32, _i32, _i64, _vp, _i32, _i32, _i64, _i64, _vp]),
     "msm_mlp_forward": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _sz,
                                _vp, _i64]),
+    "msm_vamp2_workspace": (_sz, [_i64, _i32]),
+    "msm_vamp2_loss": (_i32, [_vp, _vp, _vp, _i64, _i32, _i64, _f64, _f64, _f64, _f64, _vp, _vp, _vp, _vp, _i64]),
+    "msm_mlp_train_workspace": (_sz, [_i64, _i32, _vp, _i32, _i32, _i32]),
+    "msm_mlp_loss_grad": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _sz,
+                                 _vp, _vp, _i64, _vp, C.c_uint64, C.c_uint64, _f64, _f64, _f64, _f64, _vp, _sz, _vp,
+                                 _vp, _vp, _i64]),
+    "msm_adamw_step": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _f64, _f64, _f64, _f64, _f64, _f64, _vp]),
     "msm_kmeans_assign": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _i32, _vp, _vp, _vp, _vp]),
     "msm_kmeans_fit": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _vp, _i32, C.c_uint64, _i32, _i32, _f64, _vp, _vp]),
     "msm_kmeans_fit_begin": (

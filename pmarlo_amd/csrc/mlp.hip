@@ -7,7 +7,7 @@
 // per frame.  As many waves as the LDS holds images for are resident per CU, and while one is in its LayerNorm and
 // activation phase another has the matrix cores.
 //
-// A Linear layer is out' (16 columns x 16 frames) = W (16 x K) . act' (K x 16 frames) per tile of 16 output
+// A Linear layer (mlp_linear, mlp_common.h) is out' (16 columns x 16 frames) = W (16 x K) . act' (K x 16 frames) per tile of 16 output
 // columns, v_mfma_f64_16x16x4_f64, four tiles (64 columns) in flight per pass over K so that one LDS read of the
 // activations feeds four independent accumulator chains.  The weights come from global memory: every wave reads
 // the same few hundred KB, which stay in the caches.  Operand layout as in project_mfma_kernel
@@ -21,64 +21,9 @@
 // row, and no sum depends on the launch geometry: a frame's outputs are a function of that frame's inputs, bit for
 // bit.  There is no barrier: a wave's LDS traffic is ordered by the hardware and WAVE_SYNC keeps the compiler from
 // reordering it.
-#include <algorithm>
-#include <cfloat>
-
-#include "common.h"
-#include "wave.h"
+#include "mlp_common.h"
 
 namespace {
-
-constexpr int kMlpMaxWidth = 256;   // F, hidden widths
-constexpr int kMlpMaxOut = 64;      // apply_output_transform's limit
-constexpr int kMlpMaxLinear = 8;
-
-enum { kActTanh = 0, kActGelu = 1, kActRelu = 2, kActElu = 3, kActSelu = 4, kActLeakyRelu = 5, kActCount = 6 };
-
-// where everything lies in the packed parameters (float offsets; -1: absent); travels by value
-struct MlpPlan {
-    int n_linear;
-    int width[kMlpMaxLinear + 1];
-    int w_off[kMlpMaxLinear], b_off[kMlpMaxLinear], ln_off[kMlpMaxLinear];
-    int ln_in_off;
-    int activation, head_activation;
-    int stride[2];   // LDS row strides in doubles of the two images: widest width held, rounded up to 16, plus 2
-};
-
-#define WAVE_SYNC() __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier()
-
-struct op_or {
-    __device__ __forceinline__ int operator()(int a, int b) const { return a | b; }
-};
-
-// comparisons that are false for a NaN keep it (torch's relu and leaky_relu do)
-__device__ __forceinline__ double mlp_activate(double x, int kind) {
-    switch (kind) {
-        case kActGelu: return 0.5 * x * (1.0 + erf(x * 0.70710678118654752440));
-        case kActRelu: return x < 0.0 ? 0.0 : x;
-        case kActElu: return x > 0.0 ? x : expm1(x);
-        case kActSelu: return 1.0507009873554804934193349852946 * (x > 0.0 ? x : 1.6732632423543772848170429916717 * expm1(x));
-        case kActLeakyRelu: return x < 0.0 ? 0.01 * x : x;
-        default: return tanh(x);
-    }
-}
-
-// LayerNorm of frame j's row of `w` entries, by its four lanes (j, g): lane g owns entries g, g + 4, ...; two-pass
-// mean and biased variance, eps = 1e-5 inside the root.  The four partial sums meet through the row swaps, which
-// leave the same bits in all four lanes.
-__device__ __forceinline__ void mlp_layer_norm(double* row, int g, int w, const float* __restrict__ gamma_beta) {
-    double s = 0.0;
-    for (int f = g; f < w; f += 4) s += row[f];
-    const double mean = xrow_reduce(s, op_sum{}) / (double)w;
-    double q = 0.0;
-    for (int f = g; f < w; f += 4) {
-        const double c = row[f] - mean;
-        q += c * c;
-    }
-    const double rstd = 1.0 / sqrt(xrow_reduce(q, op_sum{}) / (double)w + 1e-5);
-    for (int f = g; f < w; f += 4)
-        row[f] = (row[f] - mean) * rstd * (double)gamma_beta[f] + (double)gamma_beta[w + f];
-}
 
 template <typename T>
 __global__ __launch_bounds__(64) void mlp_forward_kernel(
@@ -123,62 +68,7 @@ __global__ __launch_bounds__(64) void mlp_forward_kernel(
             const float* __restrict__ W = params + p.w_off[l];
             const float* __restrict__ bias = params + p.b_off[l];
             WAVE_SYNC();   // the rows of `cur` are complete: every lane reads entries other lanes wrote
-            for (int n0 = 0; n0 < N; n0 += 64) {
-                v4f64 acc[4];
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int c = n0 + 16 * t + g + 4 * r;
-                        acc[t][r] = c < N ? (double)bias[c] : 0.0;
-                    }
-                // rows of W at or past N are clamped onto row N - 1: they reach only accumulator entries that are never
-                // stored
-                const float* wrow[4];
-#pragma unroll
-                for (int t = 0; t < 4; ++t) wrow[t] = W + (size_t)min(n0 + 16 * t + j, N - 1) * K;
-                const int K16 = K & ~15;
-                for (int k0 = 0; k0 < K16; k0 += 16) {   // whole chunks: no masks, 16-byte reads of both operands
-                    const int kb = k0 + 4 * g;
-                    const double2 b01 = *reinterpret_cast<const double2*>(cur + kb);
-                    const double2 b23 = *reinterpret_cast<const double2*>(cur + kb + 2);
-                    const double b[4] = {b01.x, b01.y, b23.x, b23.y};
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) {
-                        if (n0 + 16 * t < N) {   // wave-uniform
-                            float w[4];
-                            __builtin_memcpy(w, wrow[t] + kb, sizeof(w));   // 4-byte aligned: the compiler picks the width
-#pragma unroll
-                            for (int u = 0; u < 4; ++u)
-                                acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)w[u], b[u], acc[t], 0, 0, 0);
-                        }
-                    }
-                }
-                if (K16 < K) {   // the last, partial chunk: both operands zero past K
-                    const int kb = K16 + 4 * g;
-                    double b[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) b[u] = kb + u < K ? cur[kb + u] : 0.0;   // kb + u < stride always
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) {
-                        if (n0 + 16 * t < N) {
-                            double a[4];
-#pragma unroll
-                            for (int u = 0; u < 4; ++u) a[u] = kb + u < K ? (double)wrow[t][kb + u] : 0.0;
-#pragma unroll
-                            for (int u = 0; u < 4; ++u)
-                                acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u], b[u], acc[t], 0, 0, 0);
-                        }
-                    }
-                }
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int c = n0 + 16 * t + g + 4 * r;
-                        if (c < N) nxt[c] = acc[t][r];
-                    }
-            }
+            mlp_linear(cur, nxt, W, bias, K, N, j, g);
             // lane (j, g) wrote the entries c = g mod 4 of its row and is the one that normalises and activates them
             const bool last = l == p.n_linear - 1;
             if (!last && p.ln_off[l] >= 0) mlp_layer_norm(nxt, g, N, params + p.ln_off[l]);
@@ -205,56 +95,17 @@ msm_status msm_mlp_forward(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64
                            size_t n_params, double* d_out, int64_t ldo) {
     if (!ctx) return MSM_ERR_INVALID;
     MSM_REQUIRE(ctx, dtype == MSM_F32 || dtype == MSM_F64, "msm_mlp_forward: bad dtype");
-    MSM_REQUIRE(ctx, h_widths, "msm_mlp_forward: NULL widths");
-    if (n_linear < 1 || n_linear > kMlpMaxLinear)
-        return msm_fail(ctx, MSM_ERR_UNSUPPORTED, "msm_mlp_forward: %d Linear layers (1 to %d are supported)", n_linear,
-                        kMlpMaxLinear);
-    MSM_REQUIRE(ctx, activation >= 0 && activation < kActCount, "msm_mlp_forward: unknown activation code %d", activation);
-    MSM_REQUIRE(ctx, h_widths[0] == F, "msm_mlp_forward: widths[0] = %d but F = %d", (int)h_widths[0], F);
     MlpPlan p;
-    p.n_linear = n_linear;
-    p.activation = activation;
-    p.head_activation = head_activation ? 1 : 0;
-    for (int i = 0; i <= n_linear; ++i) {
-        const int w = h_widths[i];
-        MSM_REQUIRE(ctx, w >= 1, "msm_mlp_forward: width %d of layer %d", w, i);
-        if (w > kMlpMaxWidth)
-            return msm_fail(ctx, MSM_ERR_UNSUPPORTED, "msm_mlp_forward: width %d of layer %d (at most %d is supported)", w,
-                            i, kMlpMaxWidth);
-        p.width[i] = w;
-    }
+    if (msm_status st = mlp_make_plan(ctx, "msm_mlp_forward", F, n_linear, h_widths, activation, ln_in, ln_hidden,
+                                      head_activation, n_params, &p))
+        return st;
     const int n_out = p.width[n_linear];
-    if (n_out > kMlpMaxOut)
-        return msm_fail(ctx, MSM_ERR_UNSUPPORTED, "msm_mlp_forward: %d outputs (at most %d are supported)", n_out,
-                        kMlpMaxOut);
-    size_t off = 0;
-    p.ln_in_off = -1;
-    if (ln_in) {
-        p.ln_in_off = 0;
-        off = 2 * (size_t)F;
-    }
-    for (int l = 0; l < n_linear; ++l) {
-        const size_t in = p.width[l], o = p.width[l + 1];
-        p.w_off[l] = (int)off;
-        off += in * o;
-        p.b_off[l] = (int)off;
-        off += o;
-        p.ln_off[l] = -1;
-        if (ln_hidden && l + 1 < n_linear) {
-            p.ln_off[l] = (int)off;
-            off += 2 * o;
-        }
-    }
-    MSM_REQUIRE(ctx, n_params == off, "msm_mlp_forward: %zu parameters given, the widths need %zu", n_params, off);
     MSM_REQUIRE(ctx, n >= 0 && ld >= F && ldo >= n_out, "msm_mlp_forward: bad shape (n = %lld, ld = %lld, ldo = %lld)",
                 (long long)n, (long long)ld, (long long)ldo);
     MSM_REQUIRE(ctx, (d_mean == nullptr) == (d_scale == nullptr), "msm_mlp_forward: scaler mean and scale go together");
     if (n == 0) return MSM_OK;
     MSM_REQUIRE(ctx, d_x && d_params && d_out, "msm_mlp_forward: NULL pointer");
 
-    int held[2] = {0, 0};   // layer l reads image l & 1 and writes the other
-    for (int i = 0; i <= n_linear; ++i) held[i & 1] = std::max(held[i & 1], p.width[i]);
-    for (int i = 0; i < 2; ++i) p.stride[i] = ((held[i] + 15) & ~15) + 2;
     const size_t lds = (size_t)16 * (p.stride[0] + p.stride[1]) * sizeof(double);   // <= 66 KiB
     const int64_t n_groups = (n + 15) / 16;
 #define MSM_MLP(T)                                                                                                  \

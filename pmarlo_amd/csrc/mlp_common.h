@@ -1,0 +1,195 @@
+// What the DeepTICA network kernels share: the inference pass (mlp.hip) and the training passes (mlp_train.hip).
+// Device code plus the host-side plan builder; include after common.h.
+//
+// A wave owns 16 frames; lane (j, g) = (lane & 15, lane >> 4) works on frame j.  Activation rows sit in LDS as fp64
+// [16][stride].  mlp_linear is the Linear layer of both forward kernels: because the inference and the training
+// forward run the very same instruction sequence per frame, their outputs agree bit for bit.
+#pragma once
+#include <algorithm>
+#include <cfloat>
+
+#include "common.h"
+#include "wave.h"
+
+namespace {
+
+constexpr int kMlpMaxWidth = 256;   // F, hidden widths
+constexpr int kMlpMaxOut = 64;      // apply_output_transform's limit
+constexpr int kMlpMaxLinear = 8;
+
+enum { kActTanh = 0, kActGelu = 1, kActRelu = 2, kActElu = 3, kActSelu = 4, kActLeakyRelu = 5, kActCount = 6 };
+
+// where everything lies in the packed parameters (float offsets; -1: absent); travels by value
+struct MlpPlan {
+    int n_linear;
+    int width[kMlpMaxLinear + 1];
+    int w_off[kMlpMaxLinear], b_off[kMlpMaxLinear], ln_off[kMlpMaxLinear];
+    int ln_in_off;
+    int activation, head_activation;
+    int stride[2];   // LDS row strides in doubles of the two images: widest width held, rounded up to 16, plus 2
+};
+
+#define WAVE_SYNC() __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier()
+
+struct op_or {
+    __device__ __forceinline__ int operator()(int a, int b) const { return a | b; }
+};
+
+constexpr double kSeluScale = 1.0507009873554804934193349852946;
+constexpr double kSeluAlpha = 1.6732632423543772848170429916717;
+
+// comparisons that are false for a NaN keep it (torch's relu and leaky_relu do)
+__device__ __forceinline__ double mlp_activate(double x, int kind) {
+    switch (kind) {
+        case kActGelu: return 0.5 * x * (1.0 + erf(x * 0.70710678118654752440));
+        case kActRelu: return x < 0.0 ? 0.0 : x;
+        case kActElu: return x > 0.0 ? x : expm1(x);
+        case kActSelu: return 1.0507009873554804934193349852946 * (x > 0.0 ? x : 1.6732632423543772848170429916717 * expm1(x));
+        case kActLeakyRelu: return x < 0.0 ? 0.01 * x : x;
+        default: return tanh(x);
+    }
+}
+
+// LayerNorm of frame j's row of `w` entries, by its four lanes (j, g): lane g owns entries g, g + 4, ...; two-pass
+// mean and biased variance, eps = 1e-5 inside the root.  The four partial sums meet through the row swaps, which
+// leave the same bits in all four lanes.
+__device__ __forceinline__ void mlp_layer_norm(double* row, int g, int w, const float* __restrict__ gamma_beta) {
+    double s = 0.0;
+    for (int f = g; f < w; f += 4) s += row[f];
+    const double mean = xrow_reduce(s, op_sum{}) / (double)w;
+    double q = 0.0;
+    for (int f = g; f < w; f += 4) {
+        const double c = row[f] - mean;
+        q += c * c;
+    }
+    const double rstd = 1.0 / sqrt(xrow_reduce(q, op_sum{}) / (double)w + 1e-5);
+    for (int f = g; f < w; f += 4)
+        row[f] = (row[f] - mean) * rstd * (double)gamma_beta[f] + (double)gamma_beta[w + f];
+}
+
+// nxt[c] = bias[c] + sum_k W[c][k] cur[k], c < N, for the wave's 16 frames: out' (16 columns x 16 frames) =
+// W (16 x K) . act' (K x 16 frames) per tile of 16 output columns, v_mfma_f64_16x16x4_f64, four tiles (64 columns)
+// in flight per pass over K.  Lane (j, g) supplies W[c0 + j][k] and act[frame j][k] for the same k, and acc[r] is
+// output column c0 + g + 4 r of frame j; k-step u of a chunk of 16 takes k = k0 + 4 g + u.  The last, partial chunk
+// of K feeds zeros (both operands: a stale LDS word next to a zero weight could be a NaN), and output columns past
+// N are computed from a clamped row of W and never stored.  cur / nxt: frame j's rows; the caller has made the rows
+// of `cur` complete (WAVE_SYNC) before the call.
+__device__ __forceinline__ void mlp_linear(const double* cur, double* nxt, const float* __restrict__ W,
+                                           const float* __restrict__ bias, int K, int N, int j, int g) {
+    for (int n0 = 0; n0 < N; n0 += 64) {
+        v4f64 acc[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int c = n0 + 16 * t + g + 4 * r;
+                acc[t][r] = c < N ? (double)bias[c] : 0.0;
+            }
+        // rows of W at or past N are clamped onto row N - 1: they reach only accumulator entries that are never
+        // stored
+        const float* wrow[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) wrow[t] = W + (size_t)min(n0 + 16 * t + j, N - 1) * K;
+        const int K16 = K & ~15;
+        for (int k0 = 0; k0 < K16; k0 += 16) {   // whole chunks: no masks, 16-byte reads of both operands
+            const int kb = k0 + 4 * g;
+            const double2 b01 = *reinterpret_cast<const double2*>(cur + kb);
+            const double2 b23 = *reinterpret_cast<const double2*>(cur + kb + 2);
+            const double b[4] = {b01.x, b01.y, b23.x, b23.y};
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                if (n0 + 16 * t < N) {   // wave-uniform
+                    float w[4];
+                    __builtin_memcpy(w, wrow[t] + kb, sizeof(w));   // 4-byte aligned: the compiler picks the width
+#pragma unroll
+                    for (int u = 0; u < 4; ++u)
+                        acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)w[u], b[u], acc[t], 0, 0, 0);
+                }
+            }
+        }
+        if (K16 < K) {   // the last, partial chunk: both operands zero past K
+            const int kb = K16 + 4 * g;
+            double b[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) b[u] = kb + u < K ? cur[kb + u] : 0.0;   // kb + u < stride always
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                if (n0 + 16 * t < N) {
+                    double a[4];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) a[u] = kb + u < K ? (double)wrow[t][kb + u] : 0.0;
+#pragma unroll
+                    for (int u = 0; u < 4; ++u)
+                        acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u], b[u], acc[t], 0, 0, 0);
+                }
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int c = n0 + 16 * t + g + 4 * r;
+                if (c < N) nxt[c] = acc[t][r];
+            }
+    }
+}
+
+constexpr size_t kMlpAnyParams = ~(size_t)0;   // mlp_make_plan: do not check the parameter count
+
+// The plan of a network from the arguments every entry point takes; `fn` names the entry in the messages.  Checks
+// the envelope (MSM_ERR_UNSUPPORTED beyond it, naming the number) and the parameter count, which `needed` receives.
+inline msm_status mlp_make_plan(msm_ctx* ctx, const char* fn, int F, int n_linear, const int32_t* h_widths,
+                                int activation, int ln_in, int ln_hidden, int head_activation, size_t n_params,
+                                MlpPlan* out, size_t* needed = nullptr) {
+    MSM_REQUIRE(ctx, h_widths, "%s: NULL widths", fn);
+    if (n_linear < 1 || n_linear > kMlpMaxLinear)
+        return msm_fail(ctx, MSM_ERR_UNSUPPORTED, "%s: %d Linear layers (1 to %d are supported)", fn, n_linear,
+                        kMlpMaxLinear);
+    MSM_REQUIRE(ctx, activation >= 0 && activation < kActCount, "%s: unknown activation code %d", fn, activation);
+    MSM_REQUIRE(ctx, h_widths[0] == F, "%s: widths[0] = %d but F = %d", fn, (int)h_widths[0], F);
+    MlpPlan p;
+    p.n_linear = n_linear;
+    p.activation = activation;
+    p.head_activation = head_activation ? 1 : 0;
+    for (int i = 0; i <= kMlpMaxLinear; ++i) p.width[i] = 0;
+    for (int i = 0; i < kMlpMaxLinear; ++i) p.w_off[i] = p.b_off[i] = p.ln_off[i] = -1;
+    for (int i = 0; i <= n_linear; ++i) {
+        const int w = h_widths[i];
+        MSM_REQUIRE(ctx, w >= 1, "%s: width %d of layer %d", fn, w, i);
+        if (w > kMlpMaxWidth)
+            return msm_fail(ctx, MSM_ERR_UNSUPPORTED, "%s: width %d of layer %d (at most %d is supported)", fn, w, i,
+                            kMlpMaxWidth);
+        p.width[i] = w;
+    }
+    const int n_out = p.width[n_linear];
+    if (n_out > kMlpMaxOut)
+        return msm_fail(ctx, MSM_ERR_UNSUPPORTED, "%s: %d outputs (at most %d are supported)", fn, n_out, kMlpMaxOut);
+    size_t off = 0;
+    p.ln_in_off = -1;
+    if (ln_in) {
+        p.ln_in_off = 0;
+        off = 2 * (size_t)F;
+    }
+    for (int l = 0; l < n_linear; ++l) {
+        const size_t in = p.width[l], o = p.width[l + 1];
+        p.w_off[l] = (int)off;
+        off += in * o;
+        p.b_off[l] = (int)off;
+        off += o;
+        p.ln_off[l] = -1;
+        if (ln_hidden && l + 1 < n_linear) {
+            p.ln_off[l] = (int)off;
+            off += 2 * o;
+        }
+    }
+    MSM_REQUIRE(ctx, n_params == off || n_params == kMlpAnyParams, "%s: %zu parameters given, the widths need %zu", fn,
+                n_params, off);
+    if (needed) *needed = off;
+    int held[2] = {0, 0};   // layer l reads image l & 1 and writes the other
+    for (int i = 0; i <= n_linear; ++i) held[i & 1] = std::max(held[i & 1], p.width[i]);
+    for (int i = 0; i < 2; ++i) p.stride[i] = ((held[i] + 15) & ~15) + 2;
+    *out = p;
+    return MSM_OK;
+}
+
+}  // namespace

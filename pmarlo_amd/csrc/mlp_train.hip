@@ -1,0 +1,987 @@
+// One training step of a DeepTICA network on the device: the forward pass in training mode, the VAMP-2 loss with
+// its closed-form output gradient, the backward pass, and clip + AdamW.  The law: include/msmhip.h
+// (msm_vamp2_loss, msm_mlp_loss_grad, msm_adamw_step).
+//
+// Frames are addressed by slot: slots 0 .. m-1 are the t frames of the batch (rows idx_t of the resident array),
+// slots m .. 2m-1 the tau frames (rows idx_tau).  As in mlp.hip a workgroup is one wave that owns 16 slots, whose
+// rows sit in two LDS images the layers ping-pong between.
+//
+// What the forward pass leaves in the workspace, per layer l (all fp64, [2m, width]):
+//   a[l]  the input of Linear l (after LayerNorm, activation and dropout of the layer before): dW_l = du_l' a[l];
+//   u[l]  the output of Linear l when a LayerNorm follows: its adjoint needs the row mean, the root and xhat, which
+//         are recomputed from u (three cheap passes over a cached row) rather than stored;
+//   h[l]  the value the activation is applied to: act'(h).  Storing h instead of recomputing it from u saves a
+//         second LayerNorm per row in the backward pass and costs one row of doubles;
+//   z     the scaled inputs when an input LayerNorm follows, for the same reason as u.
+// Dropout masks are never stored: a mask bit is a pure function of (seed, step, layer, slot, column), and the
+// backward pass draws it again from Philox.
+//
+// The backward pass works per 16-slot group: dA = du . W on the matrix cores (out' (K x 16 slots) = W' (K x N) .
+// du' (N x 16 slots)), then the dropout, activation and LayerNorm adjoints row by row; du_l (and, where a LayerNorm
+// has parameters, dh and dh * xhat) go to the workspace.  Parameter gradients are contractions over the 2m slots:
+// the slots are cut into chunks of kChunk = 256 (a constant, so the summation order depends on m alone), one wave
+// sums one 16 x 16 tile of dW (or 64 entries of a bias / gamma / beta gradient) over one chunk on the matrix cores,
+// and a second kernel adds the chunks in ascending order.  No atomics anywhere: equal inputs give equal bits.
+#include "mlp_common.h"
+#include "philox.h"
+
+namespace {
+
+constexpr int kChunk = 256;             // slots per partial sum of a parameter gradient / of a moment
+constexpr int kStatsHead = 16;          // scalars in front of the four vectors of the stats block
+constexpr int kSolveThreads = 256;
+
+// where everything lies in the training workspace (offsets in doubles; -1: absent); travels by value
+struct TrainLayout {
+    long long z, dz, dzx;
+    long long a[kMlpMaxLinear], h[kMlpMaxLinear], u[kMlpMaxLinear];
+    long long du[kMlpMaxLinear], dh[kMlpMaxLinear], dhx[kMlpMaxLinear];
+    long long y, dy, partial, loss, total;
+};
+
+// per dropout site (0: inputs, i + 1: after the activation of Linear i): keep iff word >= thr; kept values times scale
+struct DropPlan {
+    int on;
+    unsigned thr[kMlpMaxLinear + 1];
+    double scale[kMlpMaxLinear + 1];
+    unsigned k0, k1, step;
+};
+
+__device__ __forceinline__ double mlp_activate_grad(double x, int kind) {
+    switch (kind) {
+        case kActGelu:
+            return 0.5 * (1.0 + erf(x * 0.70710678118654752440)) + x * exp(-0.5 * x * x) * 0.39894228040143267794;
+        case kActRelu: return x <= 0.0 ? 0.0 : 1.0;
+        case kActElu: return x > 0.0 ? 1.0 : exp(x);
+        case kActSelu: return kSeluScale * (x > 0.0 ? 1.0 : kSeluAlpha * exp(x));
+        case kActLeakyRelu: return x > 0.0 ? 1.0 : 0.01;
+        default: {
+            const double t = tanh(x);
+            return 1.0 - t * t;
+        }
+    }
+}
+
+// Dropout of frame j's row (slot `slot`) at site `site`, forward and adjoint alike: row[f] *= keep ? scale : 0.
+// Lane g takes the column blocks g, g + 4, ... of four columns, one Philox call each; the caller synchronises
+// the wave before and after (the lanes of a row own other entries outside this function).
+__device__ __forceinline__ void mlp_dropout(double* row, int g, int w, const DropPlan& d, int site, unsigned slot) {
+    const Philox rng{d.k0, d.k1};
+    const unsigned thr = d.thr[site];
+    const double scale = d.scale[site];
+    for (int cb = g; 4 * cb < w; cb += 4) {
+        uint32_t c[4] = {d.step, (uint32_t)site, slot, (uint32_t)cb};
+        rng(c);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int f = 4 * cb + u;
+            if (f < w) row[f] = row[f] * (c[u] >= thr ? scale : 0.0);
+        }
+    }
+}
+
+// src[0] + src[stride] + ... (nr terms), added in ascending order; the loads of eight terms go out together, the
+// additions keep their order, so the bits are those of the plain loop
+__device__ __forceinline__ double ordered_sum(const double* __restrict__ src, size_t stride, int nr) {
+    double s = 0.0;
+    int r = 0;
+    for (; r + 8 <= nr; r += 8) {
+        double v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = src[(size_t)(r + u) * stride];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) s += v[u];
+    }
+    for (; r < nr; ++r) s += src[(size_t)r * stride];
+    return s;
+}
+
+// rows 0 .. rows-1 of an LDS image (row stride S, w entries each) to / from global rows of w doubles, coalesced
+__device__ __forceinline__ void save_rows(const double* img, int S, int w, int rows, double* __restrict__ dst, int lane) {
+    for (int r = 0; r < rows; ++r)
+        for (int f = lane; f < w; f += 64) dst[(size_t)r * w + f] = img[r * S + f];
+}
+
+template <typename T>
+__global__ __launch_bounds__(64) void mlp_train_forward_kernel(
+    const T* __restrict__ x, int64_t n, int64_t ld, const double* __restrict__ sc_mean,
+    const double* __restrict__ sc_scale, const float* __restrict__ params, MlpPlan p,
+    const int64_t* __restrict__ idx_t, const int64_t* __restrict__ idx_tau, int m, DropPlan drop, TrainLayout lay,
+    double* __restrict__ ws) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char mlp_smem[];
+    const int lane = threadIdx.x;
+    const int j = lane & 15, g = lane >> 4;
+    double* img[2];
+    img[0] = reinterpret_cast<double*>(mlp_smem);
+    img[1] = img[0] + 16 * p.stride[0];
+    const int F = p.width[0];
+    const int n_out = p.width[p.n_linear];
+    const int S2 = 2 * m;
+    const int n_groups = (S2 + 15) / 16;
+    for (int grp = blockIdx.x; grp < n_groups; grp += gridDim.x) {
+        const int s0 = grp * 16;
+        const int rows = min(16, S2 - s0);
+        WAVE_SYNC();   // the previous group's rows have been read
+        // Z as in mlp_forward_kernel, of the row the slot names; a slot past 2m, or one whose index lies outside
+        // [0, n), is not read: the first enters as zeros, the second as NaN (all its outputs are NaN)
+        const int S = p.stride[0];
+        for (int r = 0; r < 16; ++r) {
+            int64_t row = -1;
+            if (r < rows) {
+                const int s = s0 + r;
+                row = s < m ? idx_t[s] : idx_tau[s - m];
+            }
+            const bool inside = row >= 0 && row < n;
+            for (int f = lane; f < F; f += 64) {
+                double z = 0.0;
+                if (inside) {
+                    z = (double)x[row * ld + f];
+                    if (sc_mean) z = (z - sc_mean[f]) / sc_scale[f];
+                    z = (double)(float)z;
+                } else if (r < rows) {
+                    z = __longlong_as_double(0x7ff8000000000000ll);
+                }
+                img[0][r * S + f] = z;
+            }
+        }
+        WAVE_SYNC();
+        if (lay.z >= 0) save_rows(img[0], S, F, rows, ws + lay.z + (size_t)s0 * F, lane);
+        double* cur = img[0] + j * S;   // frame j's row, current and next layer
+        double* nxt = img[1] + j * p.stride[1];
+        int bad = 0;                    // a non-finite Z anywhere in the frame: all its outputs are NaN
+        for (int f = g; f < F; f += 4) bad |= !(fabs(cur[f]) <= DBL_MAX);
+        bad = xrow_reduce(bad, op_or{});
+        if (p.ln_in_off >= 0) mlp_layer_norm(cur, g, F, params + p.ln_in_off);
+        if (drop.on && drop.thr[0]) {
+            WAVE_SYNC();
+            mlp_dropout(cur, g, F, drop, 0, (unsigned)(s0 + j));
+        }
+        WAVE_SYNC();
+        save_rows(img[0], S, F, rows, ws + lay.a[0] + (size_t)s0 * F, lane);
+
+        for (int l = 0; l < p.n_linear; ++l) {
+            const int K = p.width[l], N = p.width[l + 1];
+            const int Sn = p.stride[(l + 1) & 1];
+            double* image = img[(l + 1) & 1];
+            WAVE_SYNC();   // the rows of `cur` are complete: every lane reads entries other lanes wrote
+            mlp_linear(cur, nxt, params + p.w_off[l], params + p.b_off[l], K, N, j, g);
+            const bool last = l == p.n_linear - 1;
+            if (!last && p.ln_off[l] >= 0) {
+                WAVE_SYNC();
+                save_rows(image, Sn, N, rows, ws + lay.u[l] + (size_t)s0 * N, lane);
+                mlp_layer_norm(nxt, g, N, params + p.ln_off[l]);
+            }
+            if (!last || p.head_activation) {
+                WAVE_SYNC();
+                save_rows(image, Sn, N, rows, ws + lay.h[l] + (size_t)s0 * N, lane);
+                for (int f = g; f < N; f += 4) nxt[f] = mlp_activate(nxt[f], p.activation);
+            }
+            if (!last) {
+                if (drop.on && drop.thr[l + 1]) {
+                    WAVE_SYNC();
+                    mlp_dropout(nxt, g, N, drop, l + 1, (unsigned)(s0 + j));
+                }
+                WAVE_SYNC();
+                save_rows(image, Sn, N, rows, ws + lay.a[l + 1] + (size_t)s0 * N, lane);
+            }
+            double* swap = cur;
+            cur = nxt;
+            nxt = swap;
+        }
+        if (j < rows) {
+            const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+            for (int c = g; c < n_out; c += 4) ws[lay.y + (size_t)(s0 + j) * n_out + c] = bad ? qnan : cur[c];
+        }
+    }
+}
+
+// LayerNorm adjoint of frame j's row: `grow` holds dL/d(LN output) on entry and dL/d(LN input) on exit; `xin` is
+// the row the LayerNorm was applied to (global).  dL/d(output) and dL/d(output) * xhat go to dh / dhx (the beta and
+// gamma gradients are their column sums).  Lane g owns entries g, g + 4, ...; `store`: the slot exists.
+__device__ __forceinline__ void mlp_layer_norm_adjoint(double* grow, int g, int w, const double* __restrict__ xin,
+                                                       const float* __restrict__ gamma, double* __restrict__ dh,
+                                                       double* __restrict__ dhx, bool store) {
+    double s = 0.0;
+    for (int f = g; f < w; f += 4) s += xin[f];
+    const double mean = xrow_reduce(s, op_sum{}) / (double)w;
+    double q = 0.0;
+    for (int f = g; f < w; f += 4) {
+        const double c = xin[f] - mean;
+        q += c * c;
+    }
+    const double rstd = 1.0 / sqrt(xrow_reduce(q, op_sum{}) / (double)w + 1e-5);
+    double s1 = 0.0, s2 = 0.0;
+    for (int f = g; f < w; f += 4) {
+        const double xhat = (xin[f] - mean) * rstd;
+        const double d = grow[f];
+        if (store) {
+            dh[f] = d;
+            dhx[f] = d * xhat;
+        }
+        const double dxhat = d * (double)gamma[f];
+        grow[f] = dxhat;
+        s1 += dxhat;
+        s2 += dxhat * xhat;
+    }
+    s1 = xrow_reduce(s1, op_sum{}) / (double)w;
+    s2 = xrow_reduce(s2, op_sum{}) / (double)w;
+    for (int f = g; f < w; f += 4) {
+        const double xhat = (xin[f] - mean) * rstd;
+        grow[f] = rstd * (grow[f] - s1 - xhat * s2);
+    }
+}
+
+__global__ __launch_bounds__(64) void mlp_train_backward_kernel(const float* __restrict__ params, MlpPlan p, int m,
+                                                                DropPlan drop, TrainLayout lay,
+                                                                double* __restrict__ ws) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char mlp_smem[];
+    const int lane = threadIdx.x;
+    const int j = lane & 15, g = lane >> 4;
+    double* img[2];
+    img[0] = reinterpret_cast<double*>(mlp_smem);
+    img[1] = img[0] + 16 * p.stride[0];
+    const int L = p.n_linear;
+    const int n_out = p.width[L];
+    const int S2 = 2 * m;
+    const int n_groups = (S2 + 15) / 16;
+    for (int grp = blockIdx.x; grp < n_groups; grp += gridDim.x) {
+        const int s0 = grp * 16;
+        const int rows = min(16, S2 - s0);
+        const bool mine = j < rows;                          // frame j's slot exists
+        const size_t slot = (size_t)min(s0 + j, S2 - 1);     // reads of a slot past 2m are clamped, its writes dropped
+        WAVE_SYNC();
+        {   // dL/dY of the group; slots past 2m enter as zeros
+            const int So = p.stride[L & 1];
+            for (int r = 0; r < 16; ++r)
+                for (int f = lane; f < n_out; f += 64)
+                    img[L & 1][r * So + f] = r < rows ? ws[lay.dy + (size_t)(s0 + r) * n_out + f] : 0.0;
+        }
+        for (int l = L - 1; l >= 0; --l) {
+            const int K = p.width[l], N = p.width[l + 1];
+            const int So = p.stride[(l + 1) & 1];
+            double* gout = img[(l + 1) & 1] + j * So;        // dL/d(output of layer l), then du_l
+            double* gin = img[l & 1] + j * p.stride[l & 1];  // dL/d(input of layer l)
+            const bool last = l == L - 1;
+            if (!last && drop.on && drop.thr[l + 1]) {
+                WAVE_SYNC();
+                mlp_dropout(gout, g, N, drop, l + 1, (unsigned)(s0 + j));
+            }
+            WAVE_SYNC();
+            if (!last || p.head_activation) {
+                const double* __restrict__ h = ws + lay.h[l] + slot * N;
+                for (int f = g; f < N; f += 4) gout[f] = gout[f] * mlp_activate_grad(h[f], p.activation);
+            }
+            if (!last && p.ln_off[l] >= 0)
+                mlp_layer_norm_adjoint(gout, g, N, ws + lay.u[l] + slot * N, params + p.ln_off[l],
+                                       ws + lay.dh[l] + slot * N, ws + lay.dhx[l] + slot * N, mine);
+            WAVE_SYNC();
+            save_rows(img[(l + 1) & 1], So, N, rows, ws + lay.du[l] + (size_t)s0 * N, lane);
+            if (l == 0 && p.ln_in_off < 0) break;            // nothing upstream of the first Linear has parameters
+            // dL/d(input) = du . W: entry (k, frame j) = sum_n W[n][k] du[frame j][n]
+            const float* __restrict__ W = params + p.w_off[l];
+            for (int k0 = 0; k0 < K; k0 += 16) {
+                const int kc = min(k0 + j, K - 1);
+                const v4f64 acc = mfma_tile_acc(
+                    N, g, k0 + j < K, true, [&](int nn) { return (double)W[(size_t)nn * K + kc]; },
+                    [&](int nn) { return gout[nn]; });
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int k = k0 + g + 4 * r;
+                    if (k < K) gin[k] = acc[r];
+                }
+            }
+        }
+        if (p.ln_in_off >= 0) {
+            const int F = p.width[0];
+            double* gin = img[0] + j * p.stride[0];
+            if (drop.on && drop.thr[0]) {
+                WAVE_SYNC();
+                mlp_dropout(gin, g, F, drop, 0, (unsigned)(s0 + j));
+            }
+            WAVE_SYNC();
+            mlp_layer_norm_adjoint(gin, g, F, ws + lay.z + slot * F, params + p.ln_in_off, ws + lay.dz + slot * F,
+                                   ws + lay.dzx + slot * F, mine);
+        }
+    }
+}
+
+// One chunk's share of every parameter gradient: blockIdx.y is the chunk, blockIdx.x the job.  Jobs, in the packed
+// order of the parameters: [gamma, beta of the input LayerNorm in blocks of 64 entries;] per Linear its 16 x 16
+// tiles of dW, its bias in blocks of 64, [gamma, beta in blocks of 64].  partial [chunks][n_params].
+__global__ __launch_bounds__(64) void mlp_train_param_partial_kernel(MlpPlan p, int m, TrainLayout lay, int n_params,
+                                                                     const double* __restrict__ ws,
+                                                                     double* __restrict__ partial) {
+    const int lane = threadIdx.x;
+    const int j = lane & 15, g = lane >> 4;
+    const int S2 = 2 * m;
+    const int r0 = blockIdx.y * kChunk;
+    const int nr = min(kChunk, S2 - r0);
+    double* __restrict__ out = partial + (size_t)blockIdx.y * n_params;
+    int job = blockIdx.x;
+    // a column sum: out[off + c] = sum over the chunk's slots of src[slot][c], c in block `cb` of 64 entries
+    auto colsum = [&](long long src_off, int w, int off, int cb) {
+        const int c = cb * 64 + lane;
+        if (c < w) {
+            out[off + c] = ordered_sum(ws + src_off + (size_t)r0 * w + c, w, nr);
+        }
+    };
+    if (p.ln_in_off >= 0) {
+        const int F = p.width[0], nb = (F + 63) / 64;
+        if (job < nb) return colsum(lay.dzx, F, p.ln_in_off, job);
+        job -= nb;
+        if (job < nb) return colsum(lay.dz, F, p.ln_in_off + F, job);
+        job -= nb;
+    }
+    for (int l = 0; l < p.n_linear; ++l) {
+        const int K = p.width[l], N = p.width[l + 1];
+        const int tk = (K + 15) / 16, tn = (N + 15) / 16, nb = (N + 63) / 64;
+        if (job < tn * tk) {   // dW[n][k] = sum over slots of du[slot][n] a[slot][k]
+            const int n0 = (job / tk) * 16, k0 = (job % tk) * 16;
+            const double* __restrict__ du = ws + lay.du[l] + (size_t)r0 * N + min(n0 + j, N - 1);
+            const double* __restrict__ a = ws + lay.a[l] + (size_t)r0 * K + min(k0 + j, K - 1);
+            const v4f64 acc = mfma_tile_acc(
+                nr, g, n0 + j < N, k0 + j < K, [&](int r) { return du[(size_t)r * N]; },
+                [&](int r) { return a[(size_t)r * K]; });
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int nn = n0 + g + 4 * r;
+                if (nn < N && k0 + j < K) out[p.w_off[l] + nn * K + k0 + j] = acc[r];
+            }
+            return;
+        }
+        job -= tn * tk;
+        if (job < nb) return colsum(lay.du[l], N, p.b_off[l], job);
+        job -= nb;
+        if (p.ln_off[l] >= 0) {
+            if (job < nb) return colsum(lay.dhx[l], N, p.ln_off[l], job);
+            job -= nb;
+            if (job < nb) return colsum(lay.dh[l], N, p.ln_off[l] + N, job);
+            job -= nb;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void mlp_train_param_reduce_kernel(const double* __restrict__ partial, int chunks,
+                                                                     int n_params, double* __restrict__ grad) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n_params) return;
+    double s = 0.0;
+    for (int c = 0; c < chunks; ++c) s += partial[(size_t)c * n_params + e];
+    grad[e] = s;
+}
+
+// ---- VAMP-2 loss -------------------------------------------------------------------------------------------------
+// work (doubles): psum [chunks][2 d], pmom [chunks][3][d d], G [3][d d] (G00, Gtt, G0t), mean [2 d],
+// then ten d x d matrices for the solve.
+struct VampWork {
+    long long psum, pmom, G, mean, mats, total;
+    int chunks;
+};
+
+inline VampWork vamp_work(int m, int d) {
+    VampWork w;
+    w.chunks = (m + kChunk - 1) / kChunk;
+    const long long dd = (long long)d * d;
+    w.psum = 0;
+    w.pmom = w.psum + (long long)w.chunks * 2 * d;
+    w.G = w.pmom + (long long)w.chunks * 3 * dd;
+    w.mean = w.G + 3 * dd;
+    w.mats = w.mean + 2 * d;
+    w.total = w.mats + 10 * dd;
+    return w;
+}
+
+// column sums of Y0 (entries 0 .. d-1) and Yt (d .. 2d-1) over one chunk of frames
+__global__ __launch_bounds__(128) void vamp2_colsum_kernel(const double* __restrict__ y0, const double* __restrict__ yt,
+                                                           int m, int d, int64_t ld, double* __restrict__ psum) {
+    const int c = threadIdx.x;
+    if (c >= 2 * d) return;
+    const int r0 = blockIdx.x * kChunk, nr = min(kChunk, m - r0);
+    const double* __restrict__ src = (c < d ? y0 + c : yt + (c - d)) + (size_t)r0 * ld;
+    psum[(size_t)blockIdx.x * 2 * d + c] = ordered_sum(src, ld, nr);
+}
+
+// the mean of column c (0 .. 2d-1): the chunks' sums in ascending order, over m
+__device__ __forceinline__ double vamp_mean(const double* __restrict__ psum, int chunks, int d, int m, int c) {
+    double s = 0.0;
+    for (int k = 0; k < chunks; ++k) s += psum[(size_t)k * 2 * d + c];
+    return s / (double)m;
+}
+
+// one 16 x 16 tile of the centred second moments of one chunk: matrix q = 0: Y0'Y0, 1: Yt'Yt, 2: Y0'Yt
+__global__ __launch_bounds__(64) void vamp2_moments_kernel(const double* __restrict__ y0, const double* __restrict__ yt,
+                                                           int m, int d, int64_t ld, const double* __restrict__ psum,
+                                                           int chunks, double* __restrict__ pmom) {
+    const int lane = threadIdx.x;
+    const int j = lane & 15, g = lane >> 4;
+    const int T = (d + 15) / 16;
+    const int q = blockIdx.x / (T * T), tile = blockIdx.x % (T * T);
+    const int i0 = (tile / T) * 16, c0 = (tile % T) * 16;
+    const int r0 = blockIdx.y * kChunk, nr = min(kChunk, m - r0);
+    const int ia = min(i0 + j, d - 1), ib = min(c0 + j, d - 1);
+    const bool a_tau = q == 1, b_tau = q != 0;
+    const double ma = vamp_mean(psum, chunks, d, m, ia + (a_tau ? d : 0));
+    const double mb = vamp_mean(psum, chunks, d, m, ib + (b_tau ? d : 0));
+    const double* __restrict__ A = (a_tau ? yt : y0) + (size_t)r0 * ld + ia;
+    const double* __restrict__ B = (b_tau ? yt : y0) + (size_t)r0 * ld + ib;
+    const v4f64 acc = mfma_tile_acc(
+        nr, g, i0 + j < d, c0 + j < d, [&](int r) { return A[(size_t)r * ld] - ma; },
+        [&](int r) { return B[(size_t)r * ld] - mb; });
+    double* __restrict__ out = pmom + ((size_t)blockIdx.y * 3 + q) * d * d;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int i = i0 + g + 4 * r;
+        if (i < d && c0 + j < d) out[i * d + c0 + j] = acc[r];
+    }
+}
+
+// C (d x d, row-major, global) = op(A) op(B), every thread of the workgroup; barrier at the end
+template <bool TA, bool TB>
+__device__ __forceinline__ void solve_mm(double* __restrict__ C, const double* A, const double* B, int d, double scale) {
+    for (int e = threadIdx.x; e < d * d; e += blockDim.x) {
+        const int i = e / d, c = e - i * d;
+        double s = 0.0;
+        for (int k = 0; k < d; ++k) s += (TA ? A[k * d + i] : A[i * d + k]) * (TB ? B[c * d + k] : B[k * d + c]);
+        C[e] = scale * s;
+    }
+    __syncthreads();
+}
+
+// Cyclic Jacobi by the first wave of the workgroup on LDS copies: A (destroyed; its diagonal ends as the
+// eigenvalues) and V (eigenvectors in columns), row stride d.  A rotation is skipped when |a_pq| is below 1e-17 of
+// the geometric mean of the two diagonal entries; a sweep without a rotation ends the iteration.
+__device__ void solve_jacobi(double* A, double* V, int d) {
+    const int lane = threadIdx.x;
+    if (threadIdx.x < 64) {
+        for (int e = lane; e < d * d; e += 64) V[e] = (e / d == e % d) ? 1.0 : 0.0;
+        WAVE_SYNC();
+        for (int sweep = 0; sweep < 40; ++sweep) {
+            int rotated = 0;
+            for (int pp = 0; pp < d - 1; ++pp)
+                for (int qq = pp + 1; qq < d; ++qq) {
+                    const double app = A[pp * d + pp], aqq = A[qq * d + qq], apq = A[pp * d + qq];
+                    if (!(fabs(apq) > 1e-17 * sqrt(fabs(app * aqq))) ) continue;   // wave-uniform
+                    ++rotated;
+                    const double theta = (aqq - app) / (2.0 * apq);
+                    const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+                    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+                    WAVE_SYNC();
+                    if (lane < d) {   // columns p and q
+                        const double akp = A[lane * d + pp], akq = A[lane * d + qq];
+                        A[lane * d + pp] = c * akp - s * akq;
+                        A[lane * d + qq] = s * akp + c * akq;
+                        const double vkp = V[lane * d + pp], vkq = V[lane * d + qq];
+                        V[lane * d + pp] = c * vkp - s * vkq;
+                        V[lane * d + qq] = s * vkp + c * vkq;
+                    }
+                    WAVE_SYNC();
+                    if (lane < d) {   // rows p and q
+                        const double apk = A[pp * d + lane], aqk = A[qq * d + lane];
+                        A[pp * d + lane] = c * apk - s * aqk;
+                        A[qq * d + lane] = s * apk + c * aqk;
+                    }
+                    WAVE_SYNC();
+                    if (lane == 0) A[pp * d + qq] = A[qq * d + pp] = 0.0;
+                    WAVE_SYNC();
+                }
+            if (!rotated) break;
+        }
+    }
+    __syncthreads();
+}
+
+// In-place lower Cholesky factor of the LDS matrix M (row stride d), every thread; *ok = 0 when a pivot is not
+// positive (LAPACK's potrf criterion, a NaN included).  The strict upper triangle is left as it was.
+__device__ void solve_cholesky(double* M, int d, int* ok) {
+    if (threadIdx.x == 0) *ok = 1;
+    __syncthreads();
+    for (int k = 0; k < d; ++k) {
+        const double piv = M[k * d + k];
+        __syncthreads();
+        if (!(piv > 0.0)) {
+            if (threadIdx.x == 0) *ok = 0;
+            break;   // uniform: every thread read the same pivot
+        }
+        const double lkk = sqrt(piv);
+        for (int i = k + threadIdx.x; i < d; i += blockDim.x) M[i * d + k] = i == k ? lkk : M[i * d + k] / lkk;
+        __syncthreads();
+        const int rem = d - k - 1;
+        for (int e = threadIdx.x; e < rem * rem; e += blockDim.x) {
+            const int i = k + 1 + e / rem, c = k + 1 + e % rem;
+            if (c <= i) M[i * d + c] -= M[i * d + k] * M[c * d + k];
+        }
+        __syncthreads();
+    }
+    __syncthreads();
+}
+
+// X (LDS, row stride d) = inverse of the lower factor in L (LDS): thread c solves L x = e_c; barrier at the end
+__device__ void solve_lower_inverse(const double* L, double* X, int d) {
+    for (int c = threadIdx.x; c < d; c += blockDim.x)
+        for (int i = 0; i < d; ++i) {
+            double s = i == c ? 1.0 : 0.0;
+            for (int k = c; k < i; ++k) s -= L[i * d + k] * X[k * d + c];
+            X[i * d + c] = i < c ? 0.0 : s / L[i * d + i];
+        }
+    __syncthreads();
+}
+
+struct VampOpts {
+    double eps, eps_abs, alpha, cond_reg;
+};
+
+// Regularised matrix, spectrum, penalty direction and inverse Cholesky factor of one side (q = 0: C00, 1: Ctt).
+//   Cq: the covariance (global, overwritten with the regularised matrix), Li: receives the inverse factor (global),
+//   P: receives cond_reg (v_max v_max' / l_max - v_min v_min' / l_min), or zeros (global).
+// Returns through sh[]: 0 cond, 1 eig min, 2 eig max (clamped), 3 ridge factor c (0 when the trace clamp holds),
+// 4 status (0 fine, 1 Cholesky failed after the ladder).
+__device__ void solve_side(double* Cq, double* Li, double* P, int d, const VampOpts& o, double* lds, double* sh,
+                           int* flag) {
+    const double floor_ = 1e-12;
+    double* LA = lds;            // d x d
+    double* LV = lds + d * d;    // d x d
+    if (threadIdx.x == 0) {
+        double tr = 0.0;
+        for (int i = 0; i < d; ++i) tr += Cq[i * d + i];
+        const bool clamped = !(tr >= floor_);
+        const double trc = clamped ? floor_ : tr;
+        const double mu = trc / (double)d;
+        const double ridge = fmax(mu * o.eps, mu * o.eps_abs);   // the diagonal's mean is the trace over d
+        sh[5] = o.alpha * mu + ridge;
+        sh[3] = clamped ? 0.0 : o.alpha + ridge / mu;
+    }
+    __syncthreads();
+    const double shift = sh[5];
+    for (int e = threadIdx.x; e < d * d; e += blockDim.x) {
+        const int i = e / d, c = e - i * d;
+        const double v = 0.5 * (((1.0 - o.alpha) * Cq[i * d + c] + (i == c ? shift : 0.0)) +
+                                ((1.0 - o.alpha) * Cq[c * d + i] + (i == c ? shift : 0.0)));
+        LA[e] = v;
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < d * d; e += blockDim.x) Cq[e] = LA[e];
+    __syncthreads();
+    solve_jacobi(LA, LV, d);
+    if (threadIdx.x == 0) {
+        int imin = 0, imax = 0;
+        for (int i = 1; i < d; ++i) {
+            if (LA[i * d + i] < LA[imin * d + imin]) imin = i;
+            if (LA[i * d + i] > LA[imax * d + imax]) imax = i;
+        }
+        const double lmin = LA[imin * d + imin], lmax = LA[imax * d + imax];
+        sh[1] = fmax(lmin, floor_);
+        sh[2] = fmax(lmax, floor_);
+        sh[0] = sh[2] / sh[1];
+        // the penalty's direction: absent when cond <= 1 (the clamp at 1, and d = 1), each half absent when its
+        // eigenvalue sits on the floor
+        sh[6] = (sh[0] > 1.0 && lmax > floor_) ? o.cond_reg / lmax : 0.0;
+        sh[7] = (sh[0] > 1.0 && lmin > floor_) ? o.cond_reg / lmin : 0.0;
+        flag[1] = imin;
+        flag[2] = imax;
+    }
+    __syncthreads();
+    {
+        const int imin = flag[1], imax = flag[2];
+        const double wmax = sh[6], wmin = sh[7];
+        for (int e = threadIdx.x; e < d * d; e += blockDim.x) {
+            const int i = e / d, c = e - i * d;
+            P[e] = wmax * LV[i * d + imax] * LV[c * d + imax] - wmin * LV[i * d + imin] * LV[c * d + imin];
+        }
+    }
+    __syncthreads();
+    // the jitter ladder of _stable_cholesky: 1e-8, growth 10, five tries
+    double total = 0.0, jitter = 1e-8;
+    int ok = 0;
+    for (int attempt = 0; attempt < 5 && !ok; ++attempt) {
+        for (int e = threadIdx.x; e < d * d; e += blockDim.x) LA[e] = Cq[e] + ((e / d == e % d) ? total : 0.0);
+        __syncthreads();
+        solve_cholesky(LA, d, flag);
+        ok = flag[0];
+        __syncthreads();
+        if (!ok) {
+            total += jitter;
+            jitter *= 10.0;
+        }
+    }
+    if (threadIdx.x == 0) sh[4] = ok ? 0.0 : 1.0;
+    solve_lower_inverse(LA, LV, d);
+    for (int e = threadIdx.x; e < d * d; e += blockDim.x) Li[e] = LV[e];
+    __syncthreads();
+}
+
+// The small dense algebra of the loss in one workgroup: moments from the chunks' partial sums, both sides'
+// regularisation, spectra and inverse Cholesky factors, K = La^-1 C0t Lb^-T, score, penalty, and the three
+// gradient matrices G00, Gtt, G0t.  stats: see MSM_VAMP2_* in include/msmhip.h.
+__global__ __launch_bounds__(kSolveThreads) void vamp2_solve_kernel(int m, int d, VampOpts o, VampWork w,
+                                                                   double* __restrict__ work,
+                                                                   double* __restrict__ stats) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char vamp_smem[];
+    double* lds = reinterpret_cast<double*>(vamp_smem);   // two d x d matrices
+    __shared__ double shA[8], shB[8], red[kSolveThreads / 64];
+    __shared__ int flag[4];
+    const long long dd = (long long)d * d;
+    double* M = work + w.mats;
+    double* C00 = M, *Ctt = M + dd, *C0t = M + 2 * dd, *LAi = M + 3 * dd, *LBi = M + 4 * dd, *PA = M + 5 * dd,
+            *PB = M + 6 * dd, *K = M + 7 * dd, *T1 = M + 8 * dd, *T2 = M + 9 * dd;
+    double* G00 = work + w.G, *Gtt = G00 + dd, *G0t = Gtt + dd;
+    const double* psum = work + w.psum;
+    const double* pmom = work + w.pmom;
+    for (int e = threadIdx.x; e < 3 * dd; e += blockDim.x) {
+        double s = 0.0;
+        for (int k = 0; k < w.chunks; ++k) s += pmom[(size_t)k * 3 * dd + e];
+        M[e] = s / (double)m;
+    }
+    for (int c = threadIdx.x; c < 2 * d; c += blockDim.x) {
+        const double mu = vamp_mean(psum, w.chunks, d, m, c);
+        work[w.mean + c] = mu;
+        stats[kStatsHead + 2 * kMlpMaxOut + (c < d ? c : kMlpMaxOut + c - d)] = mu;
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < d; c += blockDim.x) {
+        stats[kStatsHead + c] = C00[c * d + c];
+        stats[kStatsHead + kMlpMaxOut + c] = Ctt[c * d + c];
+    }
+    __syncthreads();
+    solve_side(C00, LAi, PA, d, o, lds, shA, flag);
+    solve_side(Ctt, LBi, PB, d, o, lds, shB, flag);
+    solve_mm<false, false>(T1, LAi, C0t, d, 1.0);
+    solve_mm<false, true>(K, T1, LBi, d, 1.0);       // K = La^-1 C0t Lb^-T
+    double part = 0.0;
+    for (int e = threadIdx.x; e < dd; e += blockDim.x) part += K[e] * K[e];
+    const double score = block_sum_lane0(part, red);
+    // G_A = La^-T K K' La^-1 + penalty direction
+    solve_mm<false, true>(T1, K, K, d, 1.0);
+    solve_mm<true, false>(T2, LAi, T1, d, 1.0);
+    solve_mm<false, false>(T1, T2, LAi, d, 1.0);
+    for (int e = threadIdx.x; e < dd; e += blockDim.x) PA[e] += T1[e];
+    __syncthreads();
+    // G_B = Lb^-T K' K Lb^-1 + penalty direction
+    solve_mm<true, false>(T1, K, K, d, 1.0);
+    solve_mm<true, false>(T2, LBi, T1, d, 1.0);
+    solve_mm<false, false>(T1, T2, LBi, d, 1.0);
+    for (int e = threadIdx.x; e < dd; e += blockDim.x) PB[e] += T1[e];
+    __syncthreads();
+    // G0t = -2 La^-T K Lb^-1
+    solve_mm<true, false>(T1, LAi, K, d, 1.0);
+    solve_mm<false, false>(G0t, T1, LBi, d, -2.0);
+    if (threadIdx.x == 0) {
+        double ta = 0.0, tb = 0.0;
+        for (int i = 0; i < d; ++i) {
+            ta += PA[i * d + i];
+            tb += PB[i * d + i];
+        }
+        shA[5] = shA[3] / (double)d * ta;
+        shB[5] = shB[3] / (double)d * tb;
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < dd; e += blockDim.x) {
+        const bool diag = e / d == e % d;
+        G00[e] = (1.0 - o.alpha) * PA[e] + (diag ? shA[5] : 0.0);
+        Gtt[e] = (1.0 - o.alpha) * PB[e] + (diag ? shB[5] : 0.0);
+    }
+    if (threadIdx.x == 0) {
+        double penalty = 0.0;
+        if (o.cond_reg > 0.0) penalty = o.cond_reg * (log(fmax(shA[0], 1.0)) + log(fmax(shB[0], 1.0)));
+        const bool failed = shA[4] != 0.0 || shB[4] != 0.0;
+        const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+        stats[0] = failed ? qnan : -score + penalty;
+        stats[1] = failed ? qnan : score;
+        stats[2] = penalty;
+        stats[3] = shA[0];
+        stats[4] = shB[0];
+        stats[5] = shA[1];
+        stats[6] = shA[2];
+        stats[7] = shB[1];
+        stats[8] = shB[2];
+        stats[9] = failed ? 1.0 : 0.0;
+        for (int i = 10; i < kStatsHead; ++i) stats[i] = 0.0;
+    }
+}
+
+// dL/dZ0 = (2 Y0c G00 + Ytc G0t') / m, dL/dZt = (2 Ytc Gtt + Y0c G0t) / m with centred outputs; one thread per entry
+__global__ __launch_bounds__(256) void vamp2_grad_kernel(const double* __restrict__ y0, const double* __restrict__ yt,
+                                                         int m, int d, int64_t ld, const double* __restrict__ G,
+                                                         const double* __restrict__ mean, double* __restrict__ g0,
+                                                         double* __restrict__ gt, int64_t ldg) {
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (long long)m * d) return;
+    const int64_t s = e / d;
+    const int c = (int)(e - s * d);
+    const long long dd = (long long)d * d;
+    const double* G00 = G, *Gtt = G + dd, *G0t = G + 2 * dd;
+    double a0 = 0.0, b0 = 0.0, at = 0.0, bt = 0.0;
+    for (int k = 0; k < d; ++k) {
+        const double v0 = y0[s * ld + k] - mean[k], vt = yt[s * ld + k] - mean[d + k];
+        a0 += v0 * G00[k * d + c];
+        b0 += vt * G0t[c * d + k];
+        at += vt * Gtt[k * d + c];
+        bt += v0 * G0t[k * d + c];
+    }
+    g0[s * ldg + c] = (2.0 * a0 + b0) / (double)m;
+    gt[s * ldg + c] = (2.0 * at + bt) / (double)m;
+}
+
+msm_status vamp2_launch(msm_ctx* ctx, const double* y0, const double* yt, int m, int d, int64_t ld, const VampOpts& o,
+                        double* work, double* stats, double* g0, double* gt, int64_t ldg) {
+    const VampWork w = vamp_work(m, d);
+    const int T = (d + 15) / 16;
+    hipLaunchKernelGGL(vamp2_colsum_kernel, dim3(w.chunks), dim3(128), 0, ctx->stream, y0, yt, m, d, ld, work + w.psum);
+    hipLaunchKernelGGL(vamp2_moments_kernel, dim3(3 * T * T, w.chunks), dim3(64), 0, ctx->stream, y0, yt, m, d, ld,
+                       work + w.psum, w.chunks, work + w.pmom);
+    const size_t lds = (size_t)2 * d * d * sizeof(double);   // <= 64 KiB
+    if (lds > 48 * 1024)
+        MSM_HIP(ctx, hipFuncSetAttribute((const void*)vamp2_solve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         (int)lds));
+    hipLaunchKernelGGL(vamp2_solve_kernel, dim3(1), dim3(kSolveThreads), lds, ctx->stream, m, d, o, w, work, stats);
+    if (g0) {
+        const long long total = (long long)m * d;
+        hipLaunchKernelGGL(vamp2_grad_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, y0, yt,
+                           m, d, ld, work + w.G, work + w.mean, g0, gt, ldg);
+    }
+    MSM_CHECK_LAUNCH(ctx);
+    return MSM_OK;
+}
+
+TrainLayout train_layout(const MlpPlan& p, int m, size_t n_params) {
+    TrainLayout t;
+    const long long S2 = 2LL * m;
+    long long off = 0;
+    auto take = [&](long long w) {
+        const long long at = off;
+        off += S2 * w;
+        return at;
+    };
+    const int F = p.width[0], L = p.n_linear;
+    t.z = t.dz = t.dzx = -1;
+    if (p.ln_in_off >= 0) {
+        t.z = take(F);
+        t.dz = take(F);
+        t.dzx = take(F);
+    }
+    for (int l = 0; l < kMlpMaxLinear; ++l) t.a[l] = t.h[l] = t.u[l] = t.du[l] = t.dh[l] = t.dhx[l] = -1;
+    for (int l = 0; l < L; ++l) {
+        const int K = p.width[l], N = p.width[l + 1];
+        const bool last = l == L - 1;
+        t.a[l] = take(K);
+        t.du[l] = take(N);
+        if (!last || p.head_activation) t.h[l] = take(N);
+        if (!last && p.ln_off[l] >= 0) {
+            t.u[l] = take(N);
+            t.dh[l] = take(N);
+            t.dhx[l] = take(N);
+        }
+    }
+    t.y = take(p.width[L]);
+    t.dy = take(p.width[L]);
+    t.partial = off;
+    off += (long long)((S2 + kChunk - 1) / kChunk) * (long long)n_params;
+    t.loss = off;
+    off += vamp_work(m, p.width[L]).total;
+    t.total = off;
+    return t;
+}
+
+// ---- clip + AdamW ------------------------------------------------------------------------------------------------
+// out[0] = |g|, out[1] = |g| after the clip, out[2] = 1 when |g| is not finite (the update is then skipped),
+// out[3] = the clip coefficient.  One workgroup: thread t sums entries t, t + 1024, ... in ascending order, the
+// threads' sums meet in a fixed tree, so the norm depends on n alone.
+__global__ __launch_bounds__(1024) void adamw_norm_kernel(const double* __restrict__ grad, int64_t n, double clip,
+                                                          double* __restrict__ out) {
+    __shared__ double red[16];
+    double s = 0.0;
+    for (int64_t e = threadIdx.x; e < n; e += 1024) s += grad[e] * grad[e];
+    const double total = block_sum_lane0(s, red);
+    if (threadIdx.x == 0) {
+        const double norm = sqrt(total);
+        const bool finite = fabs(norm) <= DBL_MAX;
+        const double coef = clip > 0.0 ? fmin(1.0, clip / (norm + 1e-6)) : 1.0;
+        out[0] = norm;
+        out[1] = norm * coef;
+        out[2] = finite ? 0.0 : 1.0;
+        out[3] = coef;
+    }
+}
+
+struct AdamOpts {
+    double lr, beta1, beta2, eps, wd, bc1, bc2_sqrt;
+};
+
+__global__ __launch_bounds__(256) void adamw_update_kernel(float* __restrict__ prm, const double* __restrict__ grad,
+                                                           double* __restrict__ mom, double* __restrict__ var, int64_t n,
+                                                           AdamOpts o, const double* __restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n || out[2] != 0.0) return;
+    const double g = grad[e] * out[3];
+    const double mm = o.beta1 * mom[e] + (1.0 - o.beta1) * g;
+    const double vv = o.beta2 * var[e] + (1.0 - o.beta2) * (g * g);
+    double w = (double)prm[e] * (1.0 - o.lr * o.wd);
+    w = w - (o.lr / o.bc1) * (mm / (sqrt(vv) / o.bc2_sqrt + o.eps));
+    mom[e] = mm;
+    var[e] = vv;
+    prm[e] = (float)w;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t msm_vamp2_workspace(int64_t m, int n_out) {
+    if (m < 1 || n_out < 1 || n_out > kMlpMaxOut || m > (1 << 29)) return 0;
+    return (size_t)vamp_work((int)m, n_out).total * sizeof(double);
+}
+
+msm_status msm_vamp2_loss(msm_ctx* ctx, const double* d_y0, const double* d_yt, int64_t m, int n_out, int64_t ld,
+                          double eps, double eps_abs, double alpha, double cond_reg, double* d_work,
+                          double* d_stats, double* d_grad0, double* d_gradt, int64_t ldg) {
+    if (!ctx) return MSM_ERR_INVALID;
+    MSM_REQUIRE(ctx, m >= 1 && m <= (1 << 29), "msm_vamp2_loss: %lld frame pairs", (long long)m);
+    MSM_REQUIRE(ctx, n_out >= 1, "msm_vamp2_loss: %d outputs", n_out);
+    if (n_out > kMlpMaxOut)
+        return msm_fail(ctx, MSM_ERR_UNSUPPORTED, "msm_vamp2_loss: %d outputs (at most %d are supported)", n_out,
+                        kMlpMaxOut);
+    MSM_REQUIRE(ctx, ld >= n_out, "msm_vamp2_loss: row stride %lld for %d outputs", (long long)ld, n_out);
+    MSM_REQUIRE(ctx, d_y0 && d_yt && d_work && d_stats, "msm_vamp2_loss: NULL pointer");
+    MSM_REQUIRE(ctx, (d_grad0 == nullptr) == (d_gradt == nullptr), "msm_vamp2_loss: the two gradients go together");
+    MSM_REQUIRE(ctx, !d_grad0 || ldg >= n_out, "msm_vamp2_loss: gradient row stride %lld for %d outputs",
+                (long long)ldg, n_out);
+    const VampOpts o = {eps, std::max(eps_abs, 0.0), std::min(std::max(alpha, 0.0), 1.0), std::max(cond_reg, 0.0)};
+    return vamp2_launch(ctx, d_y0, d_yt, (int)m, n_out, ld, o, d_work, d_stats, d_grad0, d_gradt, ldg);
+}
+
+size_t msm_mlp_train_workspace(int64_t m, int n_linear, const int32_t* h_widths, int ln_in, int ln_hidden,
+                               int head_activation) {
+    if (!h_widths || m < 2 || m > (1 << 24)) return 0;
+    MlpPlan p;
+    size_t n_params = 0;   // a refusal has nowhere to leave its message (no context): it is reported as 0
+    if (mlp_make_plan(nullptr, "msm_mlp_train_workspace", h_widths[0], n_linear, h_widths, 0, ln_in, ln_hidden,
+                      head_activation, kMlpAnyParams, &p, &n_params))
+        return 0;
+    return (size_t)train_layout(p, (int)m, n_params).total * sizeof(double);
+}
+
+msm_status msm_mlp_loss_grad(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n, int F, int64_t ld,
+                             const double* d_mean, const double* d_scale, int n_linear, const int32_t* h_widths,
+                             int activation, int ln_in, int ln_hidden, int head_activation, const float* d_params,
+                             size_t n_params, const int64_t* d_idx_t, const int64_t* d_idx_tau, int64_t m,
+                             const double* h_dropout, uint64_t seed, uint64_t step, double eps, double eps_abs,
+                             double alpha, double cond_reg, double* d_work, size_t work_bytes, double* d_stats,
+                             double* d_grad, double* d_out, int64_t ldo) {
+    if (!ctx) return MSM_ERR_INVALID;
+    MSM_REQUIRE(ctx, dtype == MSM_F32 || dtype == MSM_F64, "msm_mlp_loss_grad: bad dtype");
+    MlpPlan p;
+    if (msm_status st = mlp_make_plan(ctx, "msm_mlp_loss_grad", F, n_linear, h_widths, activation, ln_in, ln_hidden,
+                                      head_activation, n_params, &p))
+        return st;
+    const int n_out = p.width[n_linear];
+    if (m < 2 || m > (1 << 24))
+        return msm_fail(ctx, m < 2 ? MSM_ERR_INVALID : MSM_ERR_UNSUPPORTED,
+                        "msm_mlp_loss_grad: %lld frame pairs (2 to %d are supported)", (long long)m, 1 << 24);
+    MSM_REQUIRE(ctx, n >= 1 && ld >= F, "msm_mlp_loss_grad: bad shape (n = %lld, ld = %lld)", (long long)n,
+                (long long)ld);
+    MSM_REQUIRE(ctx, (d_mean == nullptr) == (d_scale == nullptr), "msm_mlp_loss_grad: scaler mean and scale go together");
+    MSM_REQUIRE(ctx, d_x && d_params && d_idx_t && d_idx_tau && d_work && d_stats, "msm_mlp_loss_grad: NULL pointer");
+    MSM_REQUIRE(ctx, !d_out || ldo >= n_out, "msm_mlp_loss_grad: output row stride %lld for %d outputs",
+                (long long)ldo, n_out);
+    MSM_REQUIRE(ctx, step <= 0xffffffffull, "msm_mlp_loss_grad: step %llu does not fit the 32-bit counter word",
+                (unsigned long long)step);
+    DropPlan drop;
+    drop.on = 0;
+    drop.k0 = (unsigned)seed;
+    drop.k1 = (unsigned)(seed >> 32);
+    drop.step = (unsigned)step;
+    for (int i = 0; i <= kMlpMaxLinear; ++i) {
+        drop.thr[i] = 0;
+        drop.scale[i] = 1.0;
+    }
+    if (h_dropout)
+        for (int i = 0; i < n_linear; ++i) {   // site 0: inputs, site i: after the activation of Linear i - 1
+            const double q = h_dropout[i];
+            MSM_REQUIRE(ctx, q >= 0.0 && q < 1.0, "msm_mlp_loss_grad: dropout probability %g at site %d (0 <= p < 1)", q,
+                        i);
+            drop.thr[i] = (unsigned)floor(q * 4294967296.0);
+            drop.scale[i] = 1.0 / (1.0 - q);
+            if (drop.thr[i]) drop.on = 1;
+        }
+    const TrainLayout lay = train_layout(p, (int)m, n_params);
+    MSM_REQUIRE(ctx, work_bytes >= (size_t)lay.total * sizeof(double),
+                "msm_mlp_loss_grad: workspace of %zu bytes, %zu are needed", work_bytes,
+                (size_t)lay.total * sizeof(double));
+
+    const size_t lds = (size_t)16 * (p.stride[0] + p.stride[1]) * sizeof(double);   // <= 66 KiB
+    const int n_groups = (int)((2 * m + 15) / 16);
+#define MSM_MLP_TRAIN(T)                                                                                              \
+    do {                                                                                                              \
+        if (lds > 48 * 1024)                                                                                          \
+            MSM_HIP(ctx, hipFuncSetAttribute((const void*)mlp_train_forward_kernel<T>,                                \
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                  \
+        int per_cu = 0;                                                                                               \
+        MSM_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mlp_train_forward_kernel<T>, 64, lds));    \
+        const int grid = (int)std::min<int64_t>(n_groups, (int64_t)ctx->n_cu * std::max(per_cu, 1));                  \
+        hipLaunchKernelGGL(mlp_train_forward_kernel<T>, dim3(grid), dim3(64), lds, ctx->stream, (const T*)d_x, n, ld, \
+                           d_mean, d_scale, d_params, p, d_idx_t, d_idx_tau, (int)m, drop, lay, d_work);              \
+    } while (0)
+    if (dtype == MSM_F32) MSM_MLP_TRAIN(float);
+    else MSM_MLP_TRAIN(double);
+#undef MSM_MLP_TRAIN
+    MSM_CHECK_LAUNCH(ctx);
+    double* y = d_work + lay.y;
+    double* dy = d_work + lay.dy;
+    const VampOpts o = {eps, std::max(eps_abs, 0.0), std::min(std::max(alpha, 0.0), 1.0), std::max(cond_reg, 0.0)};
+    if (msm_status st = vamp2_launch(ctx, y, y + (size_t)m * n_out, (int)m, n_out, n_out, o, d_work + lay.loss, d_stats,
+                                     d_grad ? dy : nullptr, d_grad ? dy + (size_t)m * n_out : nullptr, n_out))
+        return st;
+    if (d_out)
+        MSM_HIP(ctx, hipMemcpy2DAsync(d_out, (size_t)ldo * sizeof(double), y, (size_t)n_out * sizeof(double),
+                                      (size_t)n_out * sizeof(double), (size_t)(2 * m), hipMemcpyDeviceToDevice,
+                                      ctx->stream));
+    if (!d_grad) return MSM_OK;
+    {
+        if (lds > 48 * 1024)
+            MSM_HIP(ctx, hipFuncSetAttribute((const void*)mlp_train_backward_kernel,
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        int per_cu = 0;
+        MSM_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mlp_train_backward_kernel, 64, lds));
+        const int grid = (int)std::min<int64_t>(n_groups, (int64_t)ctx->n_cu * std::max(per_cu, 1));
+        hipLaunchKernelGGL(mlp_train_backward_kernel, dim3(grid), dim3(64), lds, ctx->stream, d_params, p, (int)m, drop,
+                           lay, d_work);
+    }
+    int jobs = 0;
+    if (ln_in) jobs += 2 * ((F + 63) / 64);
+    for (int l = 0; l < n_linear; ++l) {
+        const int K = p.width[l], N = p.width[l + 1];
+        jobs += ((K + 15) / 16) * ((N + 15) / 16) + ((N + 63) / 64) * (p.ln_off[l] >= 0 ? 3 : 1);
+    }
+    const int chunks = (int)((2 * m + kChunk - 1) / kChunk);
+    hipLaunchKernelGGL(mlp_train_param_partial_kernel, dim3(jobs, chunks), dim3(64), 0, ctx->stream, p, (int)m, lay,
+                       (int)n_params, d_work, d_work + lay.partial);
+    hipLaunchKernelGGL(mlp_train_param_reduce_kernel, dim3((unsigned)((n_params + 255) / 256)), dim3(256), 0, ctx->stream,
+                       d_work + lay.partial, chunks, (int)n_params, d_grad);
+    MSM_CHECK_LAUNCH(ctx);
+    return MSM_OK;
+}
+
+msm_status msm_adamw_step(msm_ctx* ctx, float* d_params, const double* d_grad, double* d_m, double* d_v, int64_t n,
+                          int64_t step, double lr, double beta1, double beta2, double eps, double weight_decay,
+                          double clip, double* d_out) {
+    if (!ctx) return MSM_ERR_INVALID;
+    MSM_REQUIRE(ctx, n >= 1, "msm_adamw_step: %lld parameters", (long long)n);
+    MSM_REQUIRE(ctx, step >= 1, "msm_adamw_step: step %lld (steps count from 1)", (long long)step);
+    MSM_REQUIRE(ctx, d_params && d_grad && d_m && d_v && d_out, "msm_adamw_step: NULL pointer");
+    MSM_REQUIRE(ctx, beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "msm_adamw_step: betas %g, %g", beta1,
+                beta2);
+    AdamOpts o;
+    o.lr = lr;
+    o.beta1 = beta1;
+    o.beta2 = beta2;
+    o.eps = eps;
+    o.wd = weight_decay;
+    o.bc1 = 1.0 - std::pow(beta1, (double)step);
+    o.bc2_sqrt = std::sqrt(1.0 - std::pow(beta2, (double)step));
+    hipLaunchKernelGGL(adamw_norm_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_grad, n, clip, d_out);
+    hipLaunchKernelGGL(adamw_update_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_params,
+                       d_grad, d_m, d_v, n, o, d_out);
+    MSM_CHECK_LAUNCH(ctx);
+    return MSM_OK;
+}
+
+}  // extern "C"

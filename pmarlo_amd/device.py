@@ -614,6 +614,17 @@ class Engine:
                  out.shape[1], absmax.ptr if absmax is not None else None), self.handle)
         return out
 
+    def _mlp_on_device(self, spec):
+        """(parameters, mean, scale) of a network spec on this device: uploaded on the first call with the spec and
+        kept with it."""
+        dev = getattr(spec, "_dev", None)
+        if dev is None or dev[0] is not self:
+            params = self.to_device(np.ascontiguousarray(spec.params, np.float32).reshape(-1))
+            mean = self.to_device(spec.mean, np.float64) if spec.mean is not None else None
+            scale = self.to_device(spec.scale, np.float64) if spec.scale is not None else None
+            dev = spec._dev = (self, params, mean, scale)
+        return dev[1:]
+
     def mlp_forward(self, x: DeviceArray, spec, out: DeviceArray | None = None, ld: int | None = None) -> DeviceArray:
         """Outputs [n, n_out] f64 of the network `spec` describes (features.deeptica.MLPSpec: widths, activation
         code, flags, packed fp32 parameters, scaler) for the frames x [n, F], f32 or f64 (msm_mlp_forward).
@@ -622,13 +633,7 @@ class Engine:
         ``ld``: row stride in elements when x is a wider buffer's left block."""
         n, F = x.shape
         widths = np.ascontiguousarray(spec.widths, np.int32)
-        dev = getattr(spec, "_dev", None)
-        if dev is None or dev[0] is not self:
-            params = self.to_device(np.ascontiguousarray(spec.params, np.float32).reshape(-1))
-            mean = self.to_device(spec.mean, np.float64) if spec.mean is not None else None
-            scale = self.to_device(spec.scale, np.float64) if spec.scale is not None else None
-            dev = spec._dev = (self, params, mean, scale)
-        _, params, mean, scale = dev
+        params, mean, scale = self._mlp_on_device(spec)
         out = out if out is not None else self.empty((n, int(widths[-1])), np.float64)
         check(lib.msm_mlp_forward(self.handle, x.ptr, _dtype_code(x.dtype), n, F, int(F if ld is None else ld),
                                   mean.ptr if mean is not None else None, scale.ptr if scale is not None else None,
@@ -636,6 +641,133 @@ class Engine:
                                   int(bool(spec.ln_hidden)), int(bool(spec.head_activation)), params.ptr, params.size,
                                   out.ptr, out.shape[1]), self.handle)
         return out
+
+    # -- DeepTICA training ------------------------------------------------------
+    @staticmethod
+    def _vamp2_stats(stats: np.ndarray, d: int) -> dict:
+        """The stats block of msm_vamp2_loss as loss, score, penalty and the reference's ten latest_metrics."""
+        if stats[9] != 0.0:
+            raise RuntimeError("Cholesky decomposition failed after retries")
+        head, w = 16, _lib.MLP_MAX_OUT
+        vec = lambda i: stats[head + i * w: head + i * w + d].tolist()       # noqa: E731
+        return {"loss": float(stats[0]), "score": float(stats[1]), "penalty": float(stats[2]),
+                "metrics": {"cond_C00": float(stats[3]), "cond_Ctt": float(stats[4]), "var_z0": vec(0),
+                            "var_zt": vec(1), "mean_z0": vec(2), "mean_zt": vec(3), "eig_C00_min": float(stats[5]),
+                            "eig_C00_max": float(stats[6]), "eig_Ctt_min": float(stats[7]),
+                            "eig_Ctt_max": float(stats[8])}}
+
+    def vamp2_loss(self, z0: DeviceArray, zt: DeviceArray, *, eps: float = 1e-3, eps_abs: float = 1e-6,
+                   alpha: float = 0.15, cond_reg: float = 1e-4, want_grad: bool = True, ld: int | None = None) -> dict:
+        """VAMP-2 loss of the outputs z0, zt [m, n_out] f64 with uniform weights (msm_vamp2_loss): a dict of loss,
+        score, penalty, `metrics` (the reference's ten latest_metrics) and, with want_grad, `grad0` / `grad_t`
+        [m, n_out] f64 on the device, the derivative of the loss with respect to z0 / zt.  ``ld``: row stride of
+        both inputs when they are blocks of wider buffers.  A Cholesky failure after the jitter ladder raises
+        RuntimeError as the reference does."""
+        m, d = z0.shape
+        if zt.shape != z0.shape:
+            raise ValueError("z0 and zt must share the same shape")
+        if z0.dtype != np.float64 or zt.dtype != np.float64:
+            raise TypeError("outputs must be float64")
+        if m == 0:
+            raise ValueError("VAMP2Loss received empty batch")
+        if d > _lib.MLP_MAX_OUT:
+            raise NotImplementedError(f"{d} outputs (at most {_lib.MLP_MAX_OUT} are supported)")
+        work = self.empty((max(int(lib.msm_vamp2_workspace(m, d)), 8) // 8,), np.float64)
+        stats = self.empty((_lib.VAMP2_STATS,), np.float64)
+        g0 = self.empty((m, d), np.float64) if want_grad else None
+        gt = self.empty((m, d), np.float64) if want_grad else None
+        check(lib.msm_vamp2_loss(self.handle, z0.ptr, zt.ptr, m, d, int(d if ld is None else ld), float(eps),
+                                 float(eps_abs), float(alpha), float(cond_reg), work.ptr, stats.ptr,
+                                 g0.ptr if want_grad else None, gt.ptr if want_grad else None, d), self.handle)
+        res = self._vamp2_stats(stats.to_host(), d)
+        if want_grad:
+            res["grad0"], res["grad_t"] = g0, gt
+        return res
+
+    def _pair_indices(self, idx, n: int) -> DeviceArray:
+        if isinstance(idx, DeviceArray):
+            if idx.dtype != np.int64:
+                raise TypeError("pair indices on the device must be int64")
+            return idx
+        idx = np.ascontiguousarray(idx, np.int64).reshape(-1)
+        if idx.size and (idx.min() < 0 or idx.max() >= n):
+            raise IndexError(f"pair index outside [0, {n})")
+        return self.to_device(idx)
+
+    def mlp_loss_grad(self, x: DeviceArray, spec, idx_t, idx_tau, *, dropout=None, seed: int = 0, step: int = 0,
+                      eps: float = 1e-3, eps_abs: float = 1e-6, alpha: float = 0.15, cond_reg: float = 1e-4,
+                      want_grad: bool = True, want_outputs: bool = False, ld: int | None = None,
+                      work: DeviceArray | None = None) -> dict:
+        """Loss and parameter gradient of the network `spec` on the lagged pairs (idx_t[i], idx_tau[i]) of the
+        resident frames x [n, F] (msm_mlp_loss_grad).  idx_t, idx_tau: equally long integer arrays (host arrays are
+        range-checked and uploaded; int64 device arrays are used as they are).  dropout: None for evaluation
+        mode, else the probabilities [input, after hidden layer 0, ...] (one per Linear layer); masks are a pure
+        function of (seed, step, site, slot, column), see include/msmhip.h.  Returns the dict of vamp2_loss without
+        its output gradients, plus `grad` [n_params] f64 (want_grad) and `outputs` [2m, n_out] f64 (want_outputs:
+        the t frames' outputs, then the tau frames'), both on the device, and `work`, the workspace the call used
+        (msm_mlp_train_workspace bytes): hand it back through ``work`` and the next call of the same or a smaller
+        shape allocates nothing."""
+        n, F = x.shape
+        widths = np.ascontiguousarray(spec.widths, np.int32)
+        spec.check_envelope()
+        n_linear = len(widths) - 1
+        it, itau = self._pair_indices(idx_t, n), self._pair_indices(idx_tau, n)
+        m = it.size
+        if itau.size != m:
+            raise ValueError(f"{m} t frames and {itau.size} tau frames")
+        if m < 2:
+            raise ValueError(f"{m} frame pairs (at least 2 are needed)")
+        drop = None
+        if dropout is not None:
+            drop = np.ascontiguousarray(dropout, np.float64).reshape(-1)
+            if drop.size != n_linear:
+                raise ValueError(f"{drop.size} dropout probabilities for {n_linear} dropout sites")
+            if np.any(drop >= 1.0) or np.any(drop < 0.0) or not np.all(np.isfinite(drop)):
+                raise ValueError(f"dropout probabilities {drop.tolist()} (0 <= p < 1)")
+        params, mean, scale = self._mlp_on_device(spec)
+        flags = (int(bool(spec.ln_in)), int(bool(spec.ln_hidden)), int(bool(spec.head_activation)))
+        need = int(lib.msm_mlp_train_workspace(m, n_linear, widths.ctypes.data, *flags))
+        if need == 0:
+            raise NotImplementedError(f"{m} frame pairs (at most {1 << 24} are supported)")
+        if work is None or work.nbytes < need:
+            work = self.empty((need // 8,), np.float64)
+        d = int(widths[-1])
+        stats = self.empty((_lib.VAMP2_STATS,), np.float64)
+        grad = self.empty((params.size,), np.float64) if want_grad else None
+        out = self.empty((2 * m, d), np.float64) if want_outputs else None
+        check(lib.msm_mlp_loss_grad(self.handle, x.ptr, _dtype_code(x.dtype), n, F, int(F if ld is None else ld),
+                                    mean.ptr if mean is not None else None, scale.ptr if scale is not None else None,
+                                    n_linear, widths.ctypes.data, int(spec.activation), *flags, params.ptr, params.size,
+                                    it.ptr, itau.ptr, m, drop.ctypes.data if drop is not None else None,
+                                    int(seed) & 0xFFFFFFFFFFFFFFFF, int(step), float(eps), float(eps_abs),
+                                    float(alpha), float(cond_reg), work.ptr, work.nbytes, stats.ptr,
+                                    grad.ptr if want_grad else None, out.ptr if want_outputs else None, d),
+              self.handle)
+        res = self._vamp2_stats(stats.to_host(), d)
+        res["work"] = work
+        if want_grad:
+            res["grad"] = grad
+        if want_outputs:
+            res["outputs"] = out
+        return res
+
+    def adamw_step(self, params: DeviceArray, grad: DeviceArray, m: DeviceArray, v: DeviceArray, step: int, *,
+                   lr: float, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
+                   clip: float | None = None) -> dict:
+        """Gradient clip and one AdamW step in place (msm_adamw_step): params [n] f32, grad, m, v [n] f64, step
+        counting from 1; clip None or <= 0: no clipping.  Returns grad_norm_preclip, grad_norm and `skipped`: with a
+        non-finite gradient norm nothing is updated and skipped is True."""
+        n = params.size
+        if params.dtype != np.float32 or any(a.dtype != np.float64 for a in (grad, m, v)):
+            raise TypeError("params must be float32; grad, m and v float64")
+        if any(a.size != n for a in (grad, m, v)):
+            raise ValueError("params, grad, m and v must have the same length")
+        out = self.empty((4,), np.float64)
+        check(lib.msm_adamw_step(self.handle, params.ptr, grad.ptr, m.ptr, v.ptr, n, int(step), float(lr),
+                                 float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
+                                 float(clip) if clip is not None else 0.0, out.ptr), self.handle)
+        o = out.to_host()
+        return {"grad_norm_preclip": float(o[0]), "grad_norm": float(o[1]), "skipped": bool(o[2] != 0.0)}
 
     def eigh(self, a: DeviceArray, want_vectors: bool = True):
         n = a.shape[0]

@@ -1,8 +1,9 @@
-"""DeepTICA on the device (mirror of pmarlo.features.deeptica): inference with a trained network -- load the
-reference's bundle, forward pass and output whitening without the frames leaving the device (model.py) -- and the
-numpy-level eigenvalue estimator of the trainer (core/).  Training stays PyTorch in the reference and is out of
-scope."""
+"""DeepTICA on the device (mirror of pmarlo.features.deeptica and pmarlo.ml.deeptica.trainer): inference with a
+trained network -- load / save the reference's bundle, forward pass and output whitening without the frames leaving
+the device (model.py) --, training -- the curriculum trainer over the device's VAMP-2 loss, backward pass and AdamW
+(trainer.py) -- and the numpy-level eigenvalue estimator of the trainer (core/)."""
 
 from .model import DeepTICAModel, MLPSpec
+from .trainer import CurriculumConfig, DeepTICACurriculumTrainer
 
-__all__ = ["DeepTICAModel", "MLPSpec"]
+__all__ = ["CurriculumConfig", "DeepTICACurriculumTrainer", "DeepTICAModel", "MLPSpec"]

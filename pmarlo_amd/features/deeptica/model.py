@@ -9,8 +9,12 @@ the training history carries output_mean / output_transform, the output whitenin
 analysis.project_cv.apply_output_transform.  Scaler, network and whitening passes run on the device
 (msm_mlp_forward, then the projection and moment kernels); the frames never come back to the host in between.
 
-Training is out of scope.  torch is needed to read the reference's `.pt` files and for nothing else: it is imported
-inside `load` only, and `from_arrays` builds the same object from numpy arrays."""
+Training lives next door (trainer.py: DeepTICACurriculumTrainer); this module gives it `initialize`, a freshly
+initialised network, and `save`, which writes the bundle `load` reads.  Stated divergence of `initialize`: weights and
+biases are drawn uniform in +-1/sqrt(fan_in) from numpy's generator, the distribution of torch's Linear for the
+biases and (in the bound, not the stream) for the weights; the stream is not torch's, so a seed gives other numbers
+than the reference's build_network.  torch is needed to read and write the reference's `.pt` files and for nothing
+else: it is imported inside `load` and `save` only, and `from_arrays` builds the same object from numpy arrays."""
 
 from __future__ import annotations
 
@@ -24,7 +28,7 @@ import numpy as np
 from ..._lib import MLP_MAX_LINEAR, MLP_MAX_OUT, MLP_MAX_WIDTH
 from ...analysis import project_cv
 
-__all__ = ["DeepTICAModel", "MLPSpec", "activation_code", "resolve_hidden_layers"]
+__all__ = ["DeepTICAModel", "MLPSpec", "activation_code", "dropout_sites", "resolve_hidden_layers", "state_dict_layout"]
 
 ACT_TANH, ACT_GELU, ACT_RELU, ACT_ELU, ACT_SELU, ACT_LEAKY_RELU = range(6)
 _ACTIVATIONS = {"gelu": ACT_GELU, "gaussian": ACT_GELU, "relu": ACT_RELU, "relu+": ACT_RELU, "elu": ACT_ELU,
@@ -42,6 +46,54 @@ def resolve_hidden_layers(config: Mapping[str, Any]) -> tuple[int, ...]:
         return ()
     hidden = tuple(int(h) for h in (config.get("hidden", ()) or ()))
     return hidden if hidden else (32, 16)
+
+
+def _hidden_dropout(spec, transitions: int) -> list[float]:
+    """normalize_hidden_dropout (model.py:53-69): one probability per hidden layer, the last one repeated."""
+    if transitions <= 0:
+        return []
+    if spec is None:
+        return [0.0] * transitions
+    if isinstance(spec, (int, float, str)) and not isinstance(spec, bool):
+        return [float(spec)] * transitions
+    values = [float(v) for v in spec] or [0.0]
+    return (values + [values[-1]] * transitions)[:transitions]
+
+
+def dropout_sites(config: Mapping[str, Any], n_linear: int) -> list[float]:
+    """Dropout probabilities in training mode, one per Linear layer: the inputs (resolve_input_dropout,
+    model.py:262-266: `dropout_input`, else `dropout`, else DeepTICAConfig's default 0; clamped at 0), then the
+    hidden layers.  A probability of 1 or more raises ValueError (the reference would zero every activation)."""
+    p_in = config.get("dropout_input")
+    if p_in is None:
+        p_in = config.get("dropout", 0.0)
+    sites = [max(0.0, float(0.0 if p_in is None else p_in))]
+    sites += [max(0.0, p) for p in _hidden_dropout(config.get("hidden_dropout"), n_linear - 1)]
+    for i, p in enumerate(sites):
+        if not p < 1.0:
+            raise ValueError(f"dropout probability {p} at site {i} (0 <= p < 1)")
+    return sites
+
+
+def state_dict_layout(config: Mapping[str, Any], F: int) -> list[tuple[str, tuple[int, ...]]]:
+    """[(key, shape), ...] of the reference network's state_dict in the packed order of the parameters.  The
+    Sequential gives an index to every module, so LayerNorms, activations and dropouts with p > 0 make the Linear
+    indices skip (override_core_mlp, model.py:72-107)."""
+    widths = (int(F), *resolve_hidden_layers(config), int(config.get("n_out", config.get("output_dim", 2))))
+    drop = _hidden_dropout(config.get("hidden_dropout"), len(widths) - 2)
+    keys: list[tuple[str, tuple[int, ...]]] = []
+    if bool(config.get("layer_norm_in", False)):
+        keys += [("ln.weight", (widths[0],)), ("ln.bias", (widths[0],))]
+    idx = 0
+    for i in range(len(widths) - 1):
+        keys += [(f"inner.nn.{idx}.weight", (widths[i + 1], widths[i])), (f"inner.nn.{idx}.bias", (widths[i + 1],))]
+        idx += 1
+        if i < len(widths) - 2:
+            if bool(config.get("layer_norm_hidden", False)):
+                keys += [(f"inner.nn.{idx}.weight", (widths[i + 1],)), (f"inner.nn.{idx}.bias", (widths[i + 1],))]
+                idx += 1
+            idx += 1 + (1 if drop[i] > 0 else 0)        # the activation, the dropout
+    return keys
 
 
 class MLPSpec:
@@ -215,6 +267,68 @@ class DeepTICAModel:
                 history = None
         return cls.from_arrays(config, params, as_np(scaler["mean"]), as_np(scaler["std"]),
                                history if isinstance(history, dict) else None)
+
+    @classmethod
+    def initialize(cls, config: Mapping[str, Any], scaler_mean, scaler_std, seed: int = 0) -> "DeepTICAModel":
+        """A network ready for training: Linear weights and biases uniform in +-1/sqrt(fan_in) from
+        numpy.random.default_rng(seed), LayerNorms at (1, 0).  The stream is not torch's (module docstring)."""
+        F = int(np.asarray(scaler_mean).reshape(-1).shape[0])
+        rng = np.random.default_rng(seed)
+        params: dict[str, np.ndarray] = {}
+        bound = 1.0
+        for key, shape in state_dict_layout(config, F):
+            if len(shape) == 2:
+                bound = 1.0 / np.sqrt(shape[1])
+                params[key] = rng.uniform(-bound, bound, size=shape).astype(np.float32)
+            elif key.endswith("weight"):
+                params[key] = np.ones(shape, np.float32)                        # LayerNorm gamma
+            elif key.startswith("ln.") or params[key.replace("bias", "weight")].ndim == 1:
+                params[key] = np.zeros(shape, np.float32)                       # LayerNorm beta
+            else:
+                params[key] = rng.uniform(-bound, bound, size=shape).astype(np.float32)
+        return cls.from_arrays(config, params, scaler_mean, scaler_std)
+
+    def state_dict(self) -> dict[str, np.ndarray]:
+        """The parameters under the reference's key names, unpacked from the spec (fp32 copies)."""
+        out, off = {}, 0
+        for key, shape in state_dict_layout(self.config, self.spec.widths[0]):
+            size = int(np.prod(shape))
+            out[key] = self.spec.params[off:off + size].reshape(shape).copy()
+            off += size
+        assert off == self.spec.params.size
+        return out
+
+    def save(self, path) -> None:
+        """Write the bundle `load` reads (the reference's DeepTICAModel.save, _full.py:311-352): `<path>.json`,
+        `<path>.pt`, `<path>.scaler.pt` and, with a non-empty history, `<path>.history.json`."""
+        import torch  # only to write the two .pt files
+
+        path = Path(path)
+        path.parent.mkdir(parents=True, exist_ok=True)
+        path.with_suffix(".json").write_text(
+            json.dumps(self.config, sort_keys=True, separators=(",", ":"), allow_nan=False), encoding="utf-8")
+        torch.save({"state_dict": {k: torch.from_numpy(v) for k, v in self.state_dict().items()}},
+                   path.with_suffix(".pt"))
+        mean = self.spec.mean if self.spec.mean is not None else np.zeros(self.spec.widths[0])
+        scale = self.spec.scale if self.spec.scale is not None else np.ones(self.spec.widths[0])
+        torch.save({"mean": np.asarray(mean), "std": np.asarray(scale)}, path.with_suffix(".scaler.pt"))
+        if self.training_history:
+            path.with_suffix(".history.json").write_text(
+                json.dumps(self.training_history, sort_keys=True, indent=2), encoding="utf-8")
+
+    def __eq__(self, other):
+        """Same config, parameters, scaler and history; config and history are compared as the JSON `save` writes
+        (a tuple equals the list it is stored as, an integer key the string it becomes)."""
+        if not isinstance(other, DeepTICAModel):
+            return NotImplemented
+
+        def norm(obj):
+            return json.loads(json.dumps(obj, sort_keys=True))
+
+        return (norm(self.config) == norm(other.config) and self.spec == other.spec
+                and norm(self.training_history) == norm(other.training_history))
+
+    __hash__ = None
 
     # -- evaluation ---------------------------------------------------------
     def transform_device(self, xd):
