@@ -115,6 +115,45 @@ msm_status msm_featurize_dihedrals(msm_ctx* ctx, const float* d_xyz, int64_t n, 
                                    const int32_t* d_quads, int Q, int mode, float* d_out, int64_t ld,
                                    int col_off);
 
+/* Periodic boundaries.
+ *   msm_box_from_cell: d_cell float64 [n, 6] = a, b, c (nm), alpha, beta, gamma (degrees) -> d_box float32 [n, 9],
+ *       rows a, b, c with a along x and b in the xy-plane (mdtraj's unitcell_vectors).  fp64 arithmetic, components
+ *       within 1e-6 of zero set to zero as mdtraj does, one rounding to fp32.
+ *   msm_featurize_spec: one launch for a mixed feature list, the arithmetic of the four entry points above with the
+ *       reference extractor's minimum-image step (S/features/deeptica/ts_feature_extractor.py:414-501) in front.
+ *       d_box: NULL (n_box = 0), or float32 [n_box, 9] with n_box = 1 (one box for every frame) or n_box = n.
+ *       d_rec int32 [F, 8], 16-byte aligned, one record per feature; sort it by kind so waves stay converged:
+ *           [0] kind      MSM_FEAT_DISTANCE (atoms 0, 1), _ANGLE (0, 1, 2; vertex 1), _DIHEDRAL (0..3), _CONTACT (0, 1)
+ *           [1..4] atoms  indices into [0, A); unused slots 0
+ *           [5] flags     MSM_FEAT_MIC: bond vectors are replaced by their minimum image (ignored without a box);
+ *                         MSM_FEAT_COSSIN (dihedral): emit cos into column [6] and sin into column [7]
+ *           [6] column    relative to col_off, in [0, width)
+ *           [7] column of the sine for MSM_FEAT_COSSIN, else ignored
+ *       d_param float32 [F]: the weight every emitted value is multiplied by (1 is exact), or rcut for a contact.
+ *       width: columns [col_off, col_off + width) of d_out [n, ld] are the table's; col_off + width <= ld is checked
+ *           here, and a record whose column lies outside [0, width) writes nothing.
+ *       mic: MSM_MIC_ROUND   f = v B^-1, v' = (f - round(f)) B, the reference extractor's rule;
+ *            MSM_MIC_SEARCH  additionally the 27 neighbouring images of v', shortest wins, lowest image index
+ *                            9 (i + 1) + 3 (j + 1) + (k + 1) on a tie: mdtraj's rule for triclinic cells.  (A v'
+ *                            shorter than 0.49 of the cell's smallest perpendicular width is the only shortest
+ *                            image and is kept without trying the others.)
+ *       B^-1 is the adjugate over the determinant in fp32, once per frame and block.  Without a box, or for an
+ *       unflagged record, the result is bit for bit that of the per-kind entry points.  A frame whose box is not
+ *       finite or has determinant 0 gets NaN in its flagged columns; so does a record with an unknown kind or an
+ *       atom index outside [0, A), in every frame. */
+#define MSM_FEAT_DISTANCE 0
+#define MSM_FEAT_ANGLE 1
+#define MSM_FEAT_DIHEDRAL 2
+#define MSM_FEAT_CONTACT 3
+#define MSM_FEAT_MIC 1
+#define MSM_FEAT_COSSIN 2
+#define MSM_MIC_ROUND 0
+#define MSM_MIC_SEARCH 1
+msm_status msm_box_from_cell(msm_ctx* ctx, const double* d_cell, int64_t n, float* d_box);
+msm_status msm_featurize_spec(msm_ctx* ctx, const float* d_xyz, int64_t n, int A, const float* d_box,
+                              int64_t n_box, const int32_t* d_rec, const float* d_param, int F, int width,
+                              int mic, float* d_out, int64_t ld, int col_off);
+
 /* Structure features whose reference implementation is an mdtraj algorithm (S/features/builtins.py:171-250: the
  * built-ins "sasa", "hbonds_count", "ssfrac", all three in the default feature set of S/api/features.py:378).
  *   sasa: Shrake-Rupley accessible area per atom, float32 [n, A] (nm^2), as mdtraj.shrake_rupley computes it

@@ -16,6 +16,10 @@ LIB_PATH = Path(__file__).resolve().parent / "csrc" / "libmsmhip.so"
 
 MSM_OK, MSM_ERR_INVALID, MSM_ERR_HIP, MSM_ERR_NOMEM, MSM_ERR_UNSUPPORTED, MSM_ERR_NOCONV = range(6)
 MSM_F32, MSM_F64 = 0, 1
+# msm_featurize_spec (MSM_FEAT_*, MSM_MIC_* in include/msmhip.h): record kinds, record flags, minimum-image rules
+FEAT_DISTANCE, FEAT_ANGLE, FEAT_DIHEDRAL, FEAT_CONTACT = range(4)
+FEAT_MIC, FEAT_COSSIN = 1, 2
+MIC_ROUND, MIC_SEARCH = 0, 1
 # launch thresholds of msm_superpose (MSM_SUPERPOSE_* in include/msmhip.h)
 SUPERPOSE_TILE_FRAMES, SUPERPOSE_TILE_FLOATS, SUPERPOSE_LDS_ATOMS, SUPERPOSE_NARROW_SEL = 64, 12288, 4096, 64
 # representative frames (MSM_REP_* in include/msmhip.h): widest feature row, frames per grouping chunk, the
@@ -75,6 +79,8 @@ _PROTOTYPES: dict[str, tuple] = {
     "msm_featurize_rg": (_i32, [_vp, _vp, _i64, _i32, _vp, _i64, _i32]),
     "msm_featurize_angles": (_i32, [_vp, _vp, _i64, _i32, _vp, _i32, _vp, _i64, _i32]),
     "msm_featurize_dihedrals": (_i32, [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _vp, _i64, _i32]),
+    "msm_box_from_cell": (_i32, [_vp, _vp, _i64, _vp]),
+    "msm_featurize_spec": (_i32, [_vp, _vp, _i64, _i32, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _i32]),
     "msm_featurize_sasa": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _i32, _vp]),
     "msm_hbond_presence": (_i32, [_vp, _vp, _i64, _i32, _vp, _i32, C.c_float, C.c_float, _vp]),
     "msm_dssp": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _vp]),

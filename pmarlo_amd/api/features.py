@@ -89,6 +89,9 @@ def feature_cache_file(traj, feature_specs: Sequence[str], cache_path: Optional[
         pos_hash = hashlib.sha1((sample * 1000.0).round().astype(np.int32).tobytes()).hexdigest()
     meta = {"n_frames": int(traj.n_frames), "n_atoms": int(traj.n_atoms), "specs": list(feature_specs),
             "top_hash": top_hash, "pos_hash": pos_hash}
+    cell = getattr(traj, "unitcell", None)
+    if cell is not None:   # periodic features depend on the cell; the key of a cell-less trajectory stays as it was
+        meta["cell_hash"] = hashlib.sha1(np.ascontiguousarray(cell, dtype=np.float64).tobytes()).hexdigest()
     return folder / f"features_{hashlib.sha1(_compact(meta, sort_keys=True)).hexdigest()}.npz"
 
 

@@ -17,7 +17,7 @@ import numpy as np
 from . import _lib
 from ._lib import check, lib
 
-__all__ = ["Engine", "DeviceArray", "get_engine", "segments_to_bounds"]
+__all__ = ["Engine", "DeviceArray", "FeatureTable", "get_engine", "segments_to_bounds"]
 
 
 def _dtype_code(dtype: np.dtype) -> int:
@@ -141,6 +141,99 @@ class _Event:
                 lib.msm_event_destroy(self.handle)
         except Exception:
             pass
+
+
+class FeatureTable:
+    """The device-resident feature list of `msm_featurize_spec` (include/msmhip.h has the record layout): `rec` int32
+    [F, 8], `param` float32 [F], and what the host needs to know without reading them back."""
+
+    __slots__ = ("rec", "param", "width", "max_atom", "any_mic")
+
+    def __init__(self, rec: DeviceArray, param: DeviceArray, width: int, max_atom: int, any_mic: bool):
+        self.rec, self.param, self.width, self.max_atom, self.any_mic = rec, param, int(width), int(max_atom), any_mic
+
+    @property
+    def n_features(self) -> int:
+        return self.rec.shape[0]
+
+
+def _records(kind: int, atoms, flags, params, cols, cols2=None) -> tuple[np.ndarray, np.ndarray]:
+    atoms = np.asarray(atoms, np.int64)
+    m = atoms.shape[0]
+    rec = np.zeros((m, 8), np.int64)
+    rec[:, 0] = kind
+    rec[:, 1:1 + atoms.shape[1]] = atoms
+    rec[:, 5] = flags
+    rec[:, 6] = cols
+    if cols2 is not None:
+        rec[:, 7] = cols2
+    return rec, np.broadcast_to(np.asarray(params, np.float32), (m,))
+
+
+def _finish_table(blocks) -> tuple[np.ndarray, np.ndarray, int]:
+    """Concatenate per-kind record blocks (already in kind order, so waves rarely diverge), check atoms and columns."""
+    rec = np.concatenate([b[0] for b in blocks]) if blocks else np.zeros((0, 8), np.int64)
+    param = np.concatenate([b[1] for b in blocks]).astype(np.float32) if blocks else np.zeros((0,), np.float32)
+    if rec.shape[0] == 0:
+        raise ValueError("the feature table is empty")
+    if rec[:, 1:5].min() < 0 or rec[:, 1:5].max() >= 2 ** 31:
+        raise ValueError("atom indices must be non-negative int32")
+    trig = (rec[:, 0] == _lib.FEAT_DIHEDRAL) & ((rec[:, 5] & _lib.FEAT_COSSIN) != 0)
+    cols = np.concatenate([rec[:, 6], rec[trig, 7]])
+    if cols.min() < 0 or cols.max() >= 2 ** 31 - 1:
+        raise ValueError("output positions must be non-negative int32")
+    if np.unique(cols).size != cols.size:
+        raise ValueError("two features share an output position")
+    return np.ascontiguousarray(rec, np.int32), np.ascontiguousarray(param), int(cols.max()) + 1
+
+
+def _table_from_spec(spec) -> tuple[np.ndarray, np.ndarray, int]:
+    if not hasattr(spec, "distance_pairs"):
+        from .features.deeptica.ts_feature_extractor import canonicalize_feature_spec
+
+        spec = canonicalize_feature_spec(spec)
+    w = np.asarray(spec.feature_weights, np.float32)
+    blocks = []
+    for kind, atoms, pos, pbc in ((_lib.FEAT_DISTANCE, spec.distance_pairs, spec.distance_positions, spec.distance_pbc),
+                                  (_lib.FEAT_ANGLE, spec.angle_triplets, spec.angle_positions, spec.angle_pbc),
+                                  (_lib.FEAT_DIHEDRAL, spec.dihedral_quads, spec.dihedral_positions, spec.dihedral_pbc)):
+        pos = np.asarray(pos, np.int64)
+        if pos.size:
+            if pos.min() < 0 or pos.max() >= w.size:
+                raise ValueError(f"feature position outside [0, {w.size})")
+            blocks.append(_records(kind, atoms, np.where(np.asarray(pbc, bool), _lib.FEAT_MIC, 0), w[pos], pos))
+    return _finish_table(blocks)
+
+
+def _table_from_indices(pairs, triplets, quads, dihedral_mode: int, contacts, rcut: float, periodic: bool):
+    if dihedral_mode not in (0, 1, 2):
+        raise ValueError("dihedral_mode must be 0, 1 or 2")
+    flag = _lib.FEAT_MIC if periodic else 0
+
+    def _idx(arr, width):
+        return np.zeros((0, width), np.int64) if arr is None else np.asarray(arr, np.int64).reshape(-1, width)
+
+    p, t, q, c = _idx(pairs, 2), _idx(triplets, 3), _idx(quads, 4), _idx(contacts, 2)
+    P, Tn, Q = p.shape[0], t.shape[0], q.shape[0]
+    blocks = []
+    if P:
+        blocks.append(_records(_lib.FEAT_DISTANCE, p, flag, 1.0, np.arange(P)))
+    if Tn:
+        blocks.append(_records(_lib.FEAT_ANGLE, t, flag, 1.0, P + np.arange(Tn)))
+    if Q:
+        k, base = np.arange(Q), P + Tn
+        if dihedral_mode == 0:
+            blocks.append(_records(_lib.FEAT_DIHEDRAL, q, flag, 1.0, base + k))
+        elif dihedral_mode == 1:
+            blocks.append(_records(_lib.FEAT_DIHEDRAL, q, flag | _lib.FEAT_COSSIN, 1.0, base + 2 * k, base + 2 * k + 1))
+        else:
+            blocks.append(_records(_lib.FEAT_DIHEDRAL, q, flag | _lib.FEAT_COSSIN, 1.0, base + k, base + Q + k))
+    if c.shape[0]:
+        if not rcut > 0.0:
+            raise ValueError("rcut must be positive")
+        base = P + Tn + (Q if dihedral_mode == 0 else 2 * Q)
+        blocks.append(_records(_lib.FEAT_CONTACT, c, flag, rcut, base + np.arange(c.shape[0])))
+    return _finish_table(blocks)
 
 
 class Engine:
@@ -353,6 +446,95 @@ class Engine:
         n, A, _ = xyz.shape
         check(lib.msm_featurize_distances(self.handle, xyz.ptr, n, A, pairs.ptr, pairs.shape[0], out.ptr, out.shape[1],
                                           int(col0)), self.handle)
+        return out
+
+    # -- periodic boundaries ---------------------------------------------------
+    def box_from_cell(self, cell) -> DeviceArray:
+        """Cell parameters float64 [n, 6] (a, b, c in nm, alpha, beta, gamma in degrees; host array or DeviceArray)
+        -> box vectors float32 [n, 9] on the device, rows a, b, c in mdtraj's convention."""
+        if not isinstance(cell, DeviceArray):
+            c = np.ascontiguousarray(cell, np.float64)
+            if c.ndim == 1:
+                c = c[None]
+            if c.ndim != 2 or c.shape[1] != 6:
+                raise ValueError(f"cell must have shape (n, 6), got {c.shape}")
+            cell = self.to_device(c)
+        elif cell.dtype != np.float64 or len(cell.shape) != 2 or cell.shape[1] != 6:
+            raise ValueError("a device cell must be float64 with shape (n, 6)")
+        n = cell.shape[0]
+        box = self.empty((n, 9), np.float32)
+        check(lib.msm_box_from_cell(self.handle, cell.ptr, n, box.ptr), self.handle)
+        return box
+
+    def feature_table(self, spec=None, *, pairs=None, triplets=None, quads=None, dihedral_mode: int = 0,
+                      contacts=None, rcut: float = 0.0, periodic: bool = True) -> FeatureTable:
+        """Upload the feature table of `msm_featurize_spec`.  Either `spec` (a feature specification in any form
+        `canonicalize_feature_spec` accepts, or its result: entries land at their position, scaled by their weight,
+        flagged by their ``pbc``), or index tables in the column layout of `featurize` (distances, angles, dihedrals
+        in `dihedral_mode`) followed by one 0/1 column per `contacts` pair at `rcut`, all flagged when `periodic`."""
+        if spec is not None:
+            rec, param, width = _table_from_spec(spec)
+        else:
+            rec, param, width = _table_from_indices(pairs, triplets, quads, int(dihedral_mode), contacts, float(rcut),
+                                                    bool(periodic))
+        return FeatureTable(self.to_device(rec), self.to_device(param), width, int(rec[:, 1:5].max(initial=-1)),
+                            bool((rec[:, 5] & _lib.FEAT_MIC).any()))
+
+    def _box_arg(self, box, n: int):
+        """(device box or None, n_box) from None, a host (3, 3) / (n, 3, 3) / (n_box, 9) array (checked: finite,
+        determinant > 0) or a device float32 [n_box, 9] / [n_box, 3, 3] array (taken as it is)."""
+        if box is None:
+            return None, 0
+        if isinstance(box, DeviceArray):
+            if box.dtype != np.float32 or box.size % 9 or len(box.shape) > 3:
+                raise ValueError("a device box must be float32 with shape (n_box, 9) or (n_box, 3, 3)")
+            n_box, dev = box.size // 9, box
+        else:
+            b = np.asarray(box, np.float64)
+            if b.size == 0 or b.size % 9 or b.shape[-1] not in (3, 9) or (b.shape[-1] == 3 and b.shape[-2:] != (3, 3)):
+                raise ValueError(f"box must have shape (3, 3), (n, 3, 3) or (n, 9), got {b.shape}")
+            b = b.reshape(-1, 3, 3)
+            if not np.isfinite(b).all():
+                raise ValueError("box has non-finite entries")
+            if not (np.linalg.det(b) > 0.0).all():
+                raise ValueError("box vectors must have a positive determinant (singular or left-handed box)")
+            n_box, dev = b.shape[0], None
+        if n_box != 1 and n_box != n:
+            raise ValueError(f"need one box or one per frame: got {n_box} boxes for {n} frames")
+        return (dev if dev is not None else self.to_device(b.reshape(-1, 9), np.float32)), n_box
+
+    def featurize_spec(self, xyz: DeviceArray, spec_or_table, box=None, mic: str = "round", out: DeviceArray | None = None,
+                       col0: int = 0) -> DeviceArray:
+        """A mixed feature list in one launch, with the minimum-image convention where an entry asks for it.
+        xyz float32 [n, A, 3] -> columns col0.. of `out` (float32 [n, ld]; default a new [n, width] array).
+        `spec_or_table`: a `FeatureTable` (see `feature_table`) or a specification, which is uploaded for this call.
+        `box`: None (nothing wraps), one box or one per frame; `mic`: "round", the reference extractor's rule, or
+        "search", mdtraj's (the shortest of the 27 neighbouring images).  With a device-resident table and box (or
+        none) nothing is uploaded and nothing waits: the form a timed step uses."""
+        if xyz.dtype != np.float32 or len(xyz.shape) != 3 or xyz.shape[2] != 3:
+            raise ValueError("xyz must be float32 with shape (n_frames, n_atoms, 3)")
+        modes = {"round": _lib.MIC_ROUND, "search": _lib.MIC_SEARCH}
+        if mic not in modes:
+            raise ValueError(f"mic must be 'round' or 'search', got {mic!r}")
+        n, A, _ = xyz.shape
+        uploaded = not isinstance(spec_or_table, FeatureTable)
+        table = self.feature_table(spec_or_table) if uploaded else spec_or_table
+        if table.max_atom >= A:
+            raise ValueError(f"atom index {table.max_atom} out of range [0, {A})")
+        dbox, n_box = self._box_arg(box, n)
+        uploaded = uploaded or (dbox is not None and dbox is not box)
+        if not table.any_mic:
+            dbox, n_box = None, 0
+        out = out if out is not None else self.empty((n, int(col0) + table.width), np.float32)
+        if out.dtype != np.float32 or len(out.shape) != 2 or out.shape[0] != n:
+            raise ValueError(f"out must be float32 with shape ({n}, ld)")
+        if col0 < 0 or col0 + table.width > out.shape[1]:
+            raise ValueError(f"output columns [{col0}, {col0 + table.width}) exceed the {out.shape[1]} columns of out")
+        check(lib.msm_featurize_spec(self.handle, xyz.ptr, n, A, dbox.ptr if dbox is not None else None, n_box,
+                                     table.rec.ptr, table.param.ptr, table.n_features, table.width, modes[mic],
+                                     out.ptr, out.shape[1], int(col0)), self.handle)
+        if uploaded:
+            self.sync()  # the uploaded table / box are freed on return
         return out
 
     def _superpose_args(self, xyz: DeviceArray, sel, ref):

@@ -12,15 +12,17 @@ import numpy as np
 
 from ..device import get_engine
 from .base import register_feature
+from .featurize import device_geometry
 
 __all__ = ["PhiPsiFeature", "Chi1Feature", "DistanceFeature", "AngleFeature", "DihedralFeature",
            "RadiusOfGyrationFeature", "DistancePairFeature", "ContactsPairFeature", "SASAFeature",
            "HBondsCountFeature", "SecondaryStructureFractionFeature", "RMSDToReferenceFeature"]
 
 
-def _device_features(traj, **kw) -> np.ndarray:
+def _device_features(traj, periodic: bool = True, **kw) -> np.ndarray:
+    """``periodic`` as in mdtraj: minimum-image bond vectors when the trajectory carries a unit cell."""
     eng = get_engine()
-    out = eng.featurize(eng.to_device(np.ascontiguousarray(traj.xyz, np.float32)), **kw)
+    out = device_geometry(eng, eng.to_device(np.ascontiguousarray(traj.xyz, np.float32)), traj, periodic, **kw)
     return out.to_host()
 
 
@@ -31,14 +33,14 @@ class PhiPsiFeature:
         self._periodic: np.ndarray | None = None
         self.labels: list[str] | None = None
 
-    def compute(self, traj, **kwargs) -> np.ndarray:
+    def compute(self, traj, periodic: bool = True, **kwargs) -> np.ndarray:
         phi_idx = traj.topology.phi_indices()
         psi_idx = traj.topology.psi_indices()
         if len(phi_idx) == 0 and len(psi_idx) == 0:
             self.labels = []
             return np.zeros((traj.n_frames, 0), dtype=float)
         quads = np.vstack([phi_idx, psi_idx])
-        X = _device_features(traj, quads=quads)  # wrapped to (-pi, pi] by the kernel
+        X = _device_features(traj, periodic, quads=quads)  # wrapped to (-pi, pi] by the kernel
         self.labels = ([f"phi:res{int(traj.topology.res_index[q[1]])}" for q in phi_idx]
                        + [f"psi:res{int(traj.topology.res_index[q[2]])}" for q in psi_idx])
         self._periodic = np.ones((X.shape[1],), dtype=bool)
@@ -58,12 +60,12 @@ class Chi1Feature:
         self._periodic: np.ndarray | None = None
         self.labels: list[str] | None = None
 
-    def compute(self, traj, **kwargs) -> np.ndarray:
+    def compute(self, traj, periodic: bool = True, **kwargs) -> np.ndarray:
         quads = traj.topology.chi1_indices()
         if len(quads) == 0:
             self.labels = []
             return np.zeros((traj.n_frames, 0), dtype=float)
-        X = _device_features(traj, quads=quads)
+        X = _device_features(traj, periodic, quads=quads)
         self._periodic = np.ones((X.shape[1],), dtype=bool)
         self.labels = [f"chi1:res{int(traj.topology.res_index[q[1]])}" for q in quads]
         return X
@@ -81,13 +83,13 @@ class _IndexedFeature:
         self._periodic: np.ndarray | None = None
         self.labels: list[str] | None = None
 
-    def compute(self, traj, indices=None, **kwargs) -> np.ndarray:
+    def compute(self, traj, indices=None, periodic: bool = True, **kwargs) -> np.ndarray:
         if indices is None or len(indices) != self.width:
             raise ValueError(f"{self.name} requires {self.width} atom indices")
         idx = [int(i) for i in indices]
         if min(idx) < 0 or max(idx) >= traj.n_atoms:
             raise ValueError(f"{self.name} indices out of range")
-        X = _device_features(traj, **{self.kw: [idx]}).astype(float)
+        X = _device_features(traj, periodic, **{self.kw: [idx]}).astype(float)
         X = np.nan_to_num(X, nan=0.0)
         self._periodic = np.array([self.periodic], dtype=bool)
         self.labels = [f"{self.name}:" + "-".join(str(i) for i in idx)]
@@ -178,9 +180,9 @@ class _PairKwFeature:
 class DistancePairFeature(_PairKwFeature):
     name = "distance_pair"
 
-    def compute(self, traj, **kwargs) -> np.ndarray:
+    def compute(self, traj, periodic: bool = True, **kwargs) -> np.ndarray:
         i, j = self._pair(traj, kwargs)
-        d = _device_features(traj, pairs=[[i, j]]).astype(float)
+        d = _device_features(traj, periodic, pairs=[[i, j]]).astype(float)
         self.labels = [f"dist:atoms:{i}-{j}"]
         return np.nan_to_num(d, nan=0.0, posinf=0.0, neginf=0.0)
 
@@ -188,14 +190,12 @@ class DistancePairFeature(_PairKwFeature):
 class ContactsPairFeature(_PairKwFeature):
     name = "contacts_pair"
 
-    def compute(self, traj, **kwargs) -> np.ndarray:
+    def compute(self, traj, periodic: bool = True, **kwargs) -> np.ndarray:
         rcut = float(kwargs.get("rcut", 0.5))
         if rcut <= 0:
             raise ValueError("rcut must be positive")
         i, j = self._pair(traj, kwargs)
-        eng = get_engine()
-        out = eng.featurize_contacts(eng.to_device(np.ascontiguousarray(traj.xyz, np.float32)), [[i, j]], rcut)
-        return out.to_host().astype(float)
+        return _device_features(traj, periodic, contacts=[[i, j]], rcut=rcut).astype(float)
 
 
 def _zeros_after_failure(feature: str, exc: Exception, shape: tuple[int, int]) -> np.ndarray:

@@ -166,8 +166,8 @@ def load_dcd(filename: str | Path, top=None, stride: int = 1, atom_indices: Sequ
     """Whole file (strided / atom-sliced) as one Trajectory; `top` = Topology, Trajectory (e.g. from
     load_pdb) or None."""
     f = DCDFile(filename)
-    xyz, _ = f.read(0, None, stride, atom_indices)
-    return Trajectory(xyz, _as_topology(top, f.n_atoms, atom_indices))
+    xyz, cell = f.read(0, None, stride, atom_indices)
+    return Trajectory(xyz, _as_topology(top, f.n_atoms, atom_indices), cell)
 
 
 def iterload(filename: str | Path, *, top=None, stride: int = 1, atom_indices: Sequence[int] | None = None,
@@ -180,9 +180,9 @@ def iterload(filename: str | Path, *, top=None, stride: int = 1, atom_indices: S
     chunk = max(1, int(chunk))
     span = chunk * stride
     for start in range(0, f.n_frames, span):
-        xyz, _ = f.read(start, min(f.n_frames, start + span), stride, atom_indices)
+        xyz, cell = f.read(start, min(f.n_frames, start + span), stride, atom_indices)
         if xyz.shape[0]:
-            yield Trajectory(xyz, topo)
+            yield Trajectory(xyz, topo, cell)
 
 
 def write_dcd(filename: str | Path, xyz_nm: np.ndarray, cell: np.ndarray | None = None, *, big_endian: bool = False,

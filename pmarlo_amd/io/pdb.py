@@ -14,7 +14,23 @@ from pathlib import Path
 
 import numpy as np
 
-__all__ = ["Topology", "Trajectory", "load_pdb"]
+__all__ = ["Topology", "Trajectory", "load_pdb", "cell_to_vectors"]
+
+
+def cell_to_vectors(cell: np.ndarray) -> np.ndarray:
+    """(n, 6) [a, b, c, alpha, beta, gamma (degrees)] -> (n, 3, 3) box vectors, rows a, b, c with a along x and b in
+    the xy-plane, as mdtraj's ``unitcell_vectors``: components within 1e-6 of zero are set to zero, so an
+    orthorhombic cell comes out exactly diagonal.  float64."""
+    c = np.asarray(cell, dtype=np.float64).reshape(-1, 6)
+    ca, cb, cg = (np.cos(np.radians(c[:, k])) for k in (3, 4, 5))
+    sg = np.sin(np.radians(c[:, 5]))
+    box = np.zeros((c.shape[0], 3, 3))
+    box[:, 0, 0] = c[:, 0]
+    box[:, 1, 0], box[:, 1, 1] = c[:, 1] * cg, c[:, 1] * sg
+    cx, cy = c[:, 2] * cb, c[:, 2] * (ca - cb * cg) / sg
+    box[:, 2, 0], box[:, 2, 1], box[:, 2, 2] = cx, cy, np.sqrt(c[:, 2] * c[:, 2] - cx * cx - cy * cy)
+    box[np.abs(box) < 1.0e-6] = 0.0
+    return box
 
 
 def _guess_element(atom_name: str) -> str:
@@ -122,11 +138,37 @@ class Topology:
 class Trajectory:
     xyz: np.ndarray                # float32 (n_frames, n_atoms, 3), nanometres
     topology: Topology
+    unitcell: np.ndarray | None = None     # float64 (n_frames, 6): a, b, c (nm), alpha, beta, gamma (degrees)
 
     def __post_init__(self):
         self.xyz = np.ascontiguousarray(self.xyz, dtype=np.float32)
         if self.xyz.ndim != 3 or self.xyz.shape[2] != 3 or self.xyz.shape[1] != self.topology.n_atoms:
             raise ValueError(f"xyz shape {self.xyz.shape} does not match topology ({self.topology.n_atoms} atoms)")
+        if self.unitcell is not None:
+            self.unitcell = np.ascontiguousarray(self.unitcell, dtype=np.float64)
+            if self.unitcell.shape != (self.xyz.shape[0], 6):
+                raise ValueError(f"unitcell shape {self.unitcell.shape} is not ({self.xyz.shape[0]}, 6)")
+
+    @staticmethod
+    def _view(a: np.ndarray) -> np.ndarray:
+        a = a.view()
+        a.flags.writeable = False
+        return a
+
+    @property
+    def unitcell_lengths(self) -> np.ndarray | None:
+        """(n_frames, 3) a, b, c in nm, read-only; None without a cell (as the two below)."""
+        return None if self.unitcell is None else self._view(self.unitcell[:, :3])
+
+    @property
+    def unitcell_angles(self) -> np.ndarray | None:
+        """(n_frames, 3) alpha, beta, gamma in degrees."""
+        return None if self.unitcell is None else self._view(self.unitcell[:, 3:])
+
+    @property
+    def unitcell_vectors(self) -> np.ndarray | None:
+        """(n_frames, 3, 3) box vectors: rows a, b, c, a along x, b in the xy-plane."""
+        return None if self.unitcell is None else self._view(cell_to_vectors(self.unitcell))
 
     @property
     def n_frames(self) -> int:
@@ -141,15 +183,21 @@ class Trajectory:
 
     def __getitem__(self, key) -> "Trajectory":
         xyz = self.xyz[key]
+        cell = None if self.unitcell is None else self.unitcell[key]
         if xyz.ndim == 2:
             xyz = xyz[None]
-        return Trajectory(xyz, self.topology)
+            cell = None if cell is None else cell[None]
+        return Trajectory(xyz, self.topology, cell)
 
     def save_pdb(self, path: str | Path) -> None:
         """Fixed-column ATOM records from the topology, one MODEL per frame, nm -> Angstrom (8.3f: 1e-3 A)."""
         top = self.topology
         chains = top.chain_ids or [" "] * self.n_atoms
         with open(path, "w") as fh:
+            if self.unitcell is not None and self.n_frames:   # the format holds one cell: the first frame's
+                a, b, c, alp, bet, gam = self.unitcell[0]
+                fh.write(f"CRYST1{a * 10.0:9.3f}{b * 10.0:9.3f}{c * 10.0:9.3f}{alp:7.2f}{bet:7.2f}{gam:7.2f} P 1"
+                         "           1\n")
             for m, frame in enumerate(np.asarray(self.xyz, dtype=np.float64) * 10.0):
                 fh.write(f"MODEL     {m + 1:4d}\n")
                 for i, (x, y, z) in enumerate(frame):
@@ -185,7 +233,9 @@ class Trajectory:
 
 
 def load_pdb(path: str | Path) -> Trajectory:
-    """Read ATOM/HETATM records of every MODEL (coordinates in Angstrom -> nm)."""
+    """Read ATOM/HETATM records of every MODEL (coordinates in Angstrom -> nm) and the CRYST1 cell, which is
+    repeated for every model."""
+    cell = None
     models: list[list[list[float]]] = []
     cur: list[list[float]] = []
     names: list[str] = []
@@ -216,6 +266,9 @@ def load_pdb(path: str | Path) -> Trajectory:
                         resseq.append(0)
                     el = line[76:78].strip() if len(line) >= 78 else ""
                     elems.append(el.capitalize() if el else _guess_element(line[12:16]))
+            elif rec == "CRYST1" and cell is None:
+                cell = [float(line[6:15]) / 10.0, float(line[15:24]) / 10.0, float(line[24:33]) / 10.0,
+                        float(line[33:40]), float(line[40:47]), float(line[47:54])]
             elif rec == "ENDMDL":
                 if cur:
                     models.append(cur)
@@ -236,5 +289,6 @@ def load_pdb(path: str | Path) -> Trajectory:
             last = key
         res_index[i] = idx
     xyz = np.asarray(models, dtype=np.float64) / 10.0
+    unitcell = None if cell is None else np.tile(np.asarray(cell, dtype=np.float64), (xyz.shape[0], 1))
     return Trajectory(xyz.astype(np.float32), Topology(names, resn, res_index, chains, np.asarray(resseq), elems,
-                                                      np.asarray(serials)))
+                                                      np.asarray(serials)), unitcell)

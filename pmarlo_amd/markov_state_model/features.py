@@ -17,6 +17,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from ..device import get_engine
+from ..features.featurize import device_geometry
 from .reduction import tica_fit_transform_trajectories
 
 __all__ = ["MSMFeatures", "compute_msm_features", "ca_distance_pairs", "ca_contact_pairs"]
@@ -69,7 +70,7 @@ def _phi_psi_block(eng, xd, traj) -> np.ndarray:
 
 
 def _features_for_traj(eng, traj, feature_type: str, n_features: Optional[int], lag: int = 10,
-                       cache_dir: Optional[str] = None) -> np.ndarray:
+                       cache_dir: Optional[str] = None, periodic: bool = True) -> np.ndarray:
     ft = feature_type.lower()
     if ft.startswith("universal"):
         from .. import api as _api
@@ -88,17 +89,18 @@ def _features_for_traj(eng, traj, feature_type: str, n_features: Optional[int], 
         return _phi_psi_block(eng, xd, traj)
     if ft == "distances":
         return eng.featurize(xd, pairs=ca_distance_pairs(traj.topology.select("name CA"), n_features)).to_host()
-    if ft == "contacts":   # the C-alpha DISTANCE of every listed residue pair (nm), not a 0/1 flag
+    if ft == "contacts":   # the C-alpha DISTANCE of every listed residue pair (nm), not a 0/1 flag; like
+        # mdtraj.compute_contacts, minimum-image when `periodic` and the trajectory has a unit cell
         pairs = ca_contact_pairs(traj.topology)
         if len(pairs) == 0:
             return np.zeros((traj.n_frames, 0), dtype=np.float32)
-        return eng.featurize(xd, pairs=pairs).to_host()
+        return device_geometry(eng, xd, traj, periodic, pairs=pairs).to_host()
     raise ValueError(f"Unknown feature type: {feature_type}")
 
 
 def compute_msm_features(trajectories: Sequence, feature_type: str = "phi_psi", n_features: Optional[int] = None,
                          feature_stride: int = 1, tica_lag: int = 0, tica_components: Optional[int] = None,
-                         lag_time: int = 10, cache_dir: Optional[str] = None) -> MSMFeatures:
+                         lag_time: int = 10, cache_dir: Optional[str] = None, periodic: bool = True) -> MSMFeatures:
     """Stride every trajectory, featurize it, stack; then (when ``tica_components`` is given, ``tica_lag``
     > 0 or the type name contains "tica") project with TICA: dimensions clamped to [2, 5] and the last
     ``tica_lag`` frames of every trajectory dropped, as the reference does.
@@ -109,14 +111,16 @@ def compute_msm_features(trajectories: Sequence, feature_type: str = "phi_psi", 
     ``cache_dir`` (None: ``./feature_cache``, the reference's ``output_dir / "feature_cache"``).  The name
     ``universal_tica`` contains "tica", so -- in the reference's order too -- its single column then enters the
     generic TICA step above whenever ``tica_components`` or ``n_features`` gives a dimension hint: a one-feature
-    TICA whose [2, 5] clamp is cut to rank 1, i.e. the column centred and rescaled, minus ``tica_lag`` frames."""
+    TICA whose [2, 5] clamp is cut to rank 1, i.e. the column centred and rescaled, minus ``tica_lag`` frames.
+
+    ``periodic`` reaches the ``contacts`` type only: minimum-image distances when a trajectory has a unit cell."""
     stride = int(max(1, feature_stride))
     lag = int(max(0, tica_lag))
     raw = sum(int(t.n_frames) for t in trajectories)
     eng = get_engine()
     strided = [t[::stride] for t in trajectories]
     universal_lag = int(max(1, lag or lag_time))
-    blocks = [_features_for_traj(eng, t, feature_type, n_features, universal_lag, cache_dir) for t in strided]
+    blocks = [_features_for_traj(eng, t, feature_type, n_features, universal_lag, cache_dir, periodic) for t in strided]
     lengths = [int(b.shape[0]) for b in blocks]
     X = np.vstack(blocks) if blocks else np.empty((0, 0))
     if tica_components is not None or lag > 0 or "tica" in feature_type.lower():
