@@ -226,6 +226,16 @@ msm_status msm_count_transitions(msm_ctx* ctx, const int32_t* d_labels, int64_t 
                                  int n_seg, int lag, int stride, int k,
                                  int64_t* d_counts, int64_t* d_pairs);
 
+/* msm_count_transitions followed by msm_transition_matrix in mode 0 (d_T = counts / row sum with zero rows left zero,
+ * d_rowsum [k], d_diag_mass = trace(T) / k), same values and bits.  Where the dense two-pass counting runs (unweighted,
+ * pairs >= k^2, a bucket of rows fits the LDS) the workgroup that owns a bucket of rows normalises them before it lets
+ * them go, and the one that finishes last adds up the diagonal: ONE launch less per step.  Every other case (sparse
+ * pairs, large k, a capture that cannot grow the scratch) runs the two calls. */
+msm_status msm_count_transitions_normalised(msm_ctx* ctx, const int32_t* d_labels, int64_t n,
+                                            const int64_t* h_seg_start, const int64_t* h_seg_stop, int n_seg, int lag,
+                                            int stride, int k, int64_t* d_counts, int64_t* d_pairs, double* d_T,
+                                            double* d_rowsum, double* d_diag_mass);
+
 /* Weighted variant: counts[src][dst] += w[t] (weight of the STARTING frame,
  * S/analysis/discretize.py:633-641).  d_counts is float64 [k*k]. The sum is
  * accumulated with fp64 atomics, so it equals the reference up to summation
@@ -353,6 +363,16 @@ msm_status msm_moments_from_lagged(msm_ctx* ctx, const void* d_x, msm_dtype dtyp
                                    const int64_t* h_seg_start, const int64_t* h_seg_stop, int n_seg, int lag,
                                    const double* d_shift, const double* d_moments, double* d_sums);
 
+/* msm_moments_from_lagged and msm_standardise_params(d_sums, d_shift, F, n_rows, with_std, ...) in ONE launch of one
+ * workgroup: d_sums as the former leaves them, d_mean / d_scale / d_inv_scale [F] as the latter, same bits.  For a
+ * single shard (with several, the sums are all-reduced between the two).  d_zero_slot (8 bytes on the device, may be
+ * NULL) is set to zero by the same launch: pointing it at the max |Y| word of a k-means fit state lets
+ * msm_project_preset go without its clear. */
+msm_status msm_moments_tail(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n, int F, int64_t ld,
+                            const int64_t* h_seg_start, const int64_t* h_seg_stop, int n_seg, int lag,
+                            const double* d_shift, const double* d_moments, double* d_sums, double n_rows, int with_std,
+                            double* d_mean, double* d_scale, double* d_inv_scale, double* d_zero_slot);
+
 /* TICA solve on the device (deeptime 0.4.5 TICA._decomposition semantics):
  *   mean = (sx+sy)/(2T); C00 = M00/(2T) - mean mean'; C0t = (M0t+M0t')/(2T) - mean mean'
  *   (all divided by d_scale[i]*d_scale[j] when d_scale != NULL, i.e. covariances of
@@ -403,6 +423,14 @@ msm_status msm_project(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n
 msm_status msm_project_finite(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n, int F, int64_t ld,
                               const double* d_mu, const double* d_inv_sigma, const double* d_mean2,
                               const double* d_w, int d, int64_t ldw, double* d_y, int64_t ldy, double* d_absmax);
+
+/* msm_project (assume_finite == 0) or msm_project_finite (!= 0) for a d_absmax word that an earlier call on the
+ * same stream has already set to zero (msm_moments_tail's d_zero_slot): no clear of its own in front of the kernel.
+ * A word that is not zero gives max(word, max |Y|). */
+msm_status msm_project_preset(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n, int F, int64_t ld,
+                              const double* d_mu, const double* d_inv_sigma, const double* d_mean2,
+                              const double* d_w, int d, int64_t ldw, double* d_y, int64_t ldy, double* d_absmax,
+                              int assume_finite);
 
 /* Symmetric eigendecomposition by parallel cyclic Jacobi, ascending
  * eigenvalues d_w [n], eigenvectors in the columns of d_v [n, n] (may be NULL).
@@ -619,6 +647,13 @@ msm_status msm_kmeans_fit_begin(msm_ctx* ctx, const void* d_x, msm_dtype dtype, 
                                 int64_t ld, const double* d_mean, const double* d_std, int k,
                                 uint64_t seed, int init_centers, double n_total, double tol2,
                                 double* d_centers, double* d_state, int absmax_ready);
+/* msm_kmeans_fit_begin that also zeroes the member sums of the fit that begins (d_sums int64 [k*d], d_counts int64
+ * [k]): by the launch that draws the centres (init_centers != 0), so the caller's clear of them falls away. */
+msm_status msm_kmeans_fit_begin_clear(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n, int d,
+                                      int64_t ld, const double* d_mean, const double* d_std, int k,
+                                      uint64_t seed, int init_centers, double n_total, double tol2,
+                                      double* d_centers, double* d_state, int absmax_ready, int64_t* d_sums,
+                                      int64_t* d_counts);
 msm_status msm_kmeans_accumulate(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n, int d,
                                  int64_t ld, const double* d_centers, int k, const double* d_mean,
                                  const double* d_std, const double* d_state, int64_t* d_sums,
@@ -678,6 +713,19 @@ msm_status msm_kmeans_lloyd_pass(msm_ctx* ctx, const void* d_x, msm_dtype dtype,
                                  double* d_centers, int k, const double* d_mean, const double* d_std,
                                  const void* d_image, double* d_state, int32_t* d_prev_labels, int64_t* d_sums,
                                  int64_t* d_counts);
+/* The two incremental entry points with first_pass: != 0 on the first pass of a fit, when no frame is booked under a
+ * centre yet.  d_prev_labels then need not hold -1: its contents are ignored (the filter kernel does not read them; for
+ * shapes that run the all-fp64 kernel the call fills the buffer itself) and every frame is added to its centre, as
+ * after a fill with -1.  first_pass == 0: the entry points above. */
+msm_status msm_kmeans_accumulate_delta_from(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n, int d,
+                                            int64_t ld, const double* d_centers, int k, const double* d_mean,
+                                            const double* d_std, const void* d_image, const double* d_state,
+                                            int32_t* d_prev_labels, int64_t* d_sums, int64_t* d_counts,
+                                            int first_pass);
+msm_status msm_kmeans_lloyd_pass_from(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n, int d, int64_t ld,
+                                      double* d_centers, int k, const double* d_mean, const double* d_std,
+                                      const void* d_image, double* d_state, int32_t* d_prev_labels, int64_t* d_sums,
+                                      int64_t* d_counts, int first_pass);
 msm_status msm_kmeans_filter_scanned(msm_ctx* ctx, uint64_t* h_out, int reset);
 /* Hardware rule the filter's certificate rests on (kmeans_filter.h, step 1): n_tiles independent
  * v_mfma_f32_16x16x32_bf16 instructions, D = A B + C with A [16][32], B [32][16] bf16 (row major, raw 16-bit

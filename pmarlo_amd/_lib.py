@@ -86,6 +86,7 @@ _PROTOTYPES: dict[str, tuple] = {
     "msm_dssp": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _vp]),
     "msm_superpose": (_i32, [_vp, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp]),
     "msm_count_transitions": (_i32, [_vp, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "msm_count_transitions_normalised": (_i32, [_vp, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "msm_count_transitions_weighted": (
         _i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "msm_count_transitions_lagscan": (_i32, [_vp, _vp, _i64, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp]),
@@ -102,6 +103,9 @@ _PROTOTYPES: dict[str, tuple] = {
     "msm_lagged_moments_onesided": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _vp, _i32, _i32, _vp, _i32, _vp]),
     "msm_onesided_tica_eigenvalues": (_i32, [_vp, _vp, _i32, _f64, _vp]),
     "msm_moments_from_lagged": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "msm_moments_tail": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _f64, _i32, _vp, _vp,
+                                _vp, _vp]),
+    "msm_project_preset": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _i64, _vp, _i32]),
     "msm_project": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _i64, _vp]),
     "msm_project_finite": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _vp, _vp, _vp, _i32, _i64, _vp, _i64, _vp]),
     "msm_eigh": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp]),
@@ -120,6 +124,8 @@ _PROTOTYPES: dict[str, tuple] = {
     "msm_kmeans_fit": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _vp, _i32, C.c_uint64, _i32, _i32, _f64, _vp, _vp]),
     "msm_kmeans_fit_begin": (
         _i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _vp, _i32, C.c_uint64, _i32, _f64, _f64, _vp, _vp, _i32]),
+    "msm_kmeans_fit_begin_clear": (
+        _i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _vp, _i32, C.c_uint64, _i32, _f64, _f64, _vp, _vp, _i32, _vp, _vp]),
     "msm_kmeans_accumulate": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "msm_kmeans_update": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32]),
     "msm_comm_unique_id": (_i32, [_vp, _sz]),
@@ -141,6 +147,10 @@ _PROTOTYPES: dict[str, tuple] = {
     "msm_kmeans_lloyd_pass": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "msm_kmeans_accumulate_delta": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
                                            _vp]),
+    "msm_kmeans_lloyd_pass_from": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                          _i32]),
+    "msm_kmeans_accumulate_delta_from": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                _vp, _i32]),
     "msm_kmeans_filter_scanned": (_i32, [_vp, C.POINTER(C.c_uint64), _i32]),
     "msm_kmeans_init_plusplus": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _vp, _i32, C.c_uint64, _f64, _vp, _vp, _vp]),
     "msm_mfma_bf16_probe": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32]),

@@ -13,6 +13,7 @@
 // further down instead: no global atomics at all.
 #include "common.h"
 #include "wave.h"
+#include "step_folds.h"
 
 #include <cstdlib>
 
@@ -229,13 +230,28 @@ __global__ __launch_bounds__(kThreads) void count_bucket_scatter_kernel(const in
     if (tid == 0) valid_out[blockIdx.x] = n_valid;
 }
 
+// What the row normalisation (row_normalise_kernel, msm.hip) leaves behind, for the launch that has the rows in its LDS.
+constexpr int kNormRowsMax = 64;            // rows of a bucket whose sums the fused normalisation keeps (R is 8 at most)
+struct RowNorm {
+    double* rowsum;         // [k]
+    double* T;              // [k][k]
+    double* tdiag;          // [k] device scratch: the diagonal of T on its way to the closing workgroup
+    unsigned int* ticket;   // arrival ticket, zero between launches
+    double* diag_out;       // trace(T) / k
+};
+
 // Pass 2.  grid = buckets rounded up to a multiple of 8; workgroup b owns the rows [b R, b R + R) of the matrix.
+// NORM: the workgroup also normalises its rows -- rowsum, T = C / rowsum (zero rows stay zero) and the diagonal entry,
+// the values and bits of row_normalise_kernel (a row sum of integers below 2^31 is exact in any order) -- and the one
+// that arrives last adds up trace(T) / k in that kernel's order: the step's counts and T in one launch.
+template <bool NORM>
 __global__ __launch_bounds__(kThreads) void count_bucket_bin_kernel(const unsigned short* __restrict__ elems,
                                                                    const unsigned int* __restrict__ offs, int chunks,
                                                                    int chunk, int k, int R, int n_buckets, int copies,
                                                                    unsigned long long* __restrict__ counts,
                                                                    const unsigned int* __restrict__ valid,
-                                                                   unsigned long long* __restrict__ pairs_out) {
+                                                                   unsigned long long* __restrict__ pairs_out,
+                                                                   RowNorm nm) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int nb = R * k;                                                  // bins of one copy
     unsigned int* bins = reinterpret_cast<unsigned int*>(smem_raw);        // [copies][nb]
@@ -298,6 +314,7 @@ __global__ __launch_bounds__(kThreads) void count_bucket_bin_kernel(const unsign
         unsigned long long v = 0;
         for (int c = 0; c < copies; ++c) v += bins[(size_t)c * nb + i];
         dst[i] = v;
+        if constexpr (NORM) bins[i] = (unsigned int)v;      // (copy 0 becomes the matrix rows; < 2^31 pairs in all)
     }
     if (b == 0 && pairs_out) {         // number of counted pairs: the chunks' valid counts, no atomics, no memset
         unsigned long long v = 0;
@@ -311,6 +328,45 @@ __global__ __launch_bounds__(kThreads) void count_bucket_bin_kernel(const unsign
             for (int w = 0; w < kThreads / 64; ++w) t += wave_part[w];
             *pairs_out = t;
         }
+    }
+    if constexpr (NORM) {
+        __shared__ double rs_sh[kNormRowsMax];
+        __shared__ double red[16];
+        __shared__ int is_last;
+        __syncthreads();
+        const int lane = tid & 63;
+        for (int r = tid >> 6; r < nrows; r += kThreads / 64) {        // a wave per row
+            unsigned long long sum = 0;
+            for (int j = lane; j < k; j += 64) sum += bins[(size_t)r * k + j];
+            sum = wave_sum_down(sum);
+            if (lane == 0) {
+                const double rs = (double)(long long)sum;
+                rs_sh[r] = rs;
+                nm.rowsum[r0 + r] = rs;
+            }
+        }
+        __syncthreads();
+        double* Trow = nm.T + (size_t)r0 * k;
+        for (int i = tid; i < nrows * k; i += kThreads) {
+            const double rs = rs_sh[i / k];
+            Trow[i] = rs > 0.0 ? (double)(long long)bins[i] / rs : 0.0;
+        }
+        // the diagonal entries travel as device-scope stores; every wave waits for the acknowledgement of its own before
+        // the workgroup takes its ticket, and the last arrival reads them with device-scope loads (row_normalise_kernel)
+        if (tid < nrows) {
+            const double rs = rs_sh[tid];
+            const double tii = rs > 0.0 ? (double)(long long)bins[(size_t)tid * k + r0 + tid] / rs : 0.0;
+            __hip_atomic_store(&nm.tdiag[r0 + tid], tii, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (tid == 0) {
+            const unsigned t = __hip_atomic_fetch_add(nm.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            is_last = t == (unsigned)n_buckets - 1u;      // (the workgroups past the last bucket left above)
+            if (is_last) __hip_atomic_store(nm.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        __syncthreads();
+        if (is_last) diag_mass_close<kThreads>(nm.tdiag, k, red, nm.diag_out);
     }
 }
 
@@ -406,9 +462,13 @@ CountPlan plan_counts(const msm_ctx* ctx, int k, int64_t total_pairs, size_t bin
 
 template <bool WEIGHTED>
 msm_status launch_counts(msm_ctx* ctx, const int32_t* d_labels, const double* d_weights,
-                         const SegTab& st, int k, void* d_counts, int64_t* d_pairs) {
+                         const SegTab& st, int k, void* d_counts, int64_t* d_pairs, const RowNorm* norm = nullptr,
+                         bool* normalised = nullptr) {
+    // norm: the bucket path also leaves the row-normalised matrix (*normalised tells whether it did; every other path
+    // leaves that to the caller)
     using out_t = typename BinT<WEIGHTED>::out_t;
     using lds_t = typename BinT<WEIGHTED>::lds_t;
+    if (normalised) *normalised = false;
     if constexpr (!WEIGHTED) {
         // dense regime, a bucket of rows fits the LDS: two passes without global atomics (see count_bucket_*)
         const int R = msm_ceil_div(k, kBucketsMax), buckets = msm_ceil_div(k, R);
@@ -438,13 +498,16 @@ msm_status launch_counts(msm_ctx* ctx, const int32_t* d_labels, const double* d_
                 int copies = 1;
                 while (copies < kThreads / 64 && (size_t)2 * copies * bin_bytes <= (size_t)kBinCopiesBytes) copies *= 2;
                 const size_t lds2 = (size_t)copies * bin_bytes + (size_t)(2 * kThreads + 1) * sizeof(unsigned int);
+                const bool fuse = norm && R <= kNormRowsMax;
+                auto kern = fuse ? count_bucket_bin_kernel<true> : count_bucket_bin_kernel<false>;
                 if (lds2 > 48 * 1024)
-                    MSM_HIP(ctx, hipFuncSetAttribute((const void*)count_bucket_bin_kernel,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-                hipLaunchKernelGGL(count_bucket_bin_kernel, dim3(8 * ((buckets + 7) / 8)), dim3(kThreads), lds2, ctx->stream,
+                    MSM_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
+                hipLaunchKernelGGL(kern, dim3(8 * ((buckets + 7) / 8)), dim3(kThreads), lds2, ctx->stream,
                                    (const unsigned short*)elems, (const unsigned int*)offs, chunks, chunk, k, R, buckets, copies,
-                                   (unsigned long long*)d_counts, (const unsigned int*)valid, (unsigned long long*)d_pairs);
+                                   (unsigned long long*)d_counts, (const unsigned int*)valid, (unsigned long long*)d_pairs,
+                                   fuse ? *norm : RowNorm{});
                 MSM_CHECK_LAUNCH(ctx);
+                if (normalised) *normalised = fuse;
                 return MSM_OK;
             }
         }
@@ -514,6 +577,36 @@ msm_status msm_count_transitions(msm_ctx* ctx, const int32_t* d_labels, int64_t 
     msm_status rs = msm_build_segtab(ctx, n, h_seg_start, h_seg_stop, n_seg, lag, stride, &st, 0);
     if (rs != MSM_OK) return rs;
     return launch_counts<false>(ctx, d_labels, nullptr, st, k, d_counts, d_pairs);
+}
+
+// msm_count_transitions followed by msm_transition_matrix mode 0 (T = C / row sum, trace(T) / k), same values and bits:
+// in the counting launch itself where the bucket path runs, else as those two calls.
+msm_status msm_count_transitions_normalised(msm_ctx* ctx, const int32_t* d_labels, int64_t n,
+                                            const int64_t* h_seg_start, const int64_t* h_seg_stop, int n_seg, int lag,
+                                            int stride, int k, int64_t* d_counts, int64_t* d_pairs, double* d_T,
+                                            double* d_rowsum, double* d_diag_mass) {
+    if (!ctx) return MSM_ERR_INVALID;
+    MSM_REQUIRE(ctx, n >= 0 && k >= 1, "msm_count_transitions_normalised: need n >= 0 and k >= 1 (n=%lld k=%d)",
+                (long long)n, k);
+    MSM_REQUIRE(ctx, k <= 46340, "msm_count_transitions_normalised: k=%d too large", k);
+    MSM_REQUIRE(ctx, d_counts && d_T && d_rowsum && d_diag_mass && (d_labels || n == 0),
+                "msm_count_transitions_normalised: NULL pointer");
+    SegTab st;
+    msm_status rs = msm_build_segtab(ctx, n, h_seg_start, h_seg_stop, n_seg, lag, stride, &st, 0);
+    if (rs != MSM_OK) return rs;
+    // the diagonal's scratch and the ticket as msm_transition_matrix has them (a capture cannot grow the scratch)
+    const size_t diag_bytes = (size_t)k * sizeof(double);
+    bool normalised = false;
+    if (ctx->km_stats && !(ctx->capturing && diag_bytes > ctx->scratch_bytes)) {
+        rs = msm_reserve_scratch(ctx, diag_bytes);
+        if (rs != MSM_OK) return rs;
+        const RowNorm nm{d_rowsum, d_T, (double*)ctx->scratch, (unsigned int*)ctx->km_stats + 3, d_diag_mass};
+        rs = launch_counts<false>(ctx, d_labels, nullptr, st, k, d_counts, d_pairs, &nm, &normalised);
+    } else {
+        rs = launch_counts<false>(ctx, d_labels, nullptr, st, k, d_counts, d_pairs);
+    }
+    if (rs != MSM_OK || normalised) return rs;
+    return msm_transition_matrix(ctx, d_counts, 0, k, 0, 0.0, 0.0, d_T, nullptr, nullptr, nullptr, d_rowsum, d_diag_mass);
 }
 
 msm_status msm_count_transitions_weighted(msm_ctx* ctx, const int32_t* d_labels,

@@ -23,6 +23,7 @@
 // Roofline: 3*F^2 flop per frame (2F^2 for M0t + F^2 for the symmetric half of
 // M00) against F*s bytes -> MFMA-bound for F >~ 27.
 #include "common.h"
+#include "step_folds.h"
 
 #include <cstring>
 
@@ -836,11 +837,20 @@ struct EdgeSegs {
 // frames of a segment, which this kernel adds (segments no longer than the lag lie in both edges
 // entirely): 2 S1 = sx + sy + first + last, 2 S2 = diag(M00) + first2 + last2.
 // One workgroup; thread f owns feature f (F <= 1024 per pass), at most 2 lag frames per segment.
-template <typename T>
+// PARAMS: the kernel also finishes what standardise_params_kernel (moments.hip) would do with those sums in a launch
+// of its own -- mean, scale, 1/scale of every column, over n_rows frames -- and, handed `zero_bits`, clears that
+// word (the max |Y| slot the projection raises with atomics): one launch where the single-shard step had three.
+template <typename T, bool PARAMS>
 __global__ __launch_bounds__(256) void moments_from_lagged_kernel(const T* __restrict__ x, int F, int64_t ld,
                                                                   EdgeSegs sg, const double* __restrict__ shift,
                                                                   const double* __restrict__ mom,
-                                                                  double* __restrict__ sums) {
+                                                                  double* __restrict__ sums, double n_rows, int with_std,
+                                                                  double* __restrict__ mean, double* __restrict__ scale,
+                                                                  double* __restrict__ inv_scale,
+                                                                  unsigned long long* __restrict__ zero_bits) {
+    if constexpr (PARAMS) {
+        if (zero_bits && threadIdx.x == 0) *zero_bits = 0ull;
+    }
     double frames = 0.0;
     for (int q = 0; q < sg.n; ++q) frames += (double)(sg.stop[q] - sg.start[q]);
     for (int f = threadIdx.x; f < F; f += blockDim.x) {
@@ -859,10 +869,53 @@ __global__ __launch_bounds__(256) void moments_from_lagged_kernel(const T* __res
             }
         }
         const double sx = mom[(size_t)2 * F * F + f], sy = mom[(size_t)2 * F * F + F + f];
+        const double s1 = 0.5 * (sx + sy + e1), s2 = 0.5 * (mom[(size_t)f * F + f] + e2);
         sums[f] = frames;
-        sums[F + f] = 0.5 * (sx + sy + e1);
-        sums[2 * F + f] = 0.5 * (mom[(size_t)f * F + f] + e2);
+        sums[F + f] = s1;
+        sums[2 * F + f] = s2;
+        if constexpr (PARAMS)
+            standardise_params_body(frames, s1, s2, sh, n_rows, with_std, &mean[f], &scale[f], &inv_scale[f]);
     }
+}
+
+// PARAMS: see moments_from_lagged_kernel
+template <bool PARAMS>
+msm_status moments_from_lagged_impl(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n, int F, int64_t ld,
+                                           const int64_t* h_seg_start, const int64_t* h_seg_stop, int n_seg, int lag,
+                                           const double* d_shift, const double* d_moments, double* d_sums, double n_rows,
+                                           int with_std, double* d_mean, double* d_scale, double* d_inv_scale,
+                                           double* d_zero_slot) {
+    if (!ctx) return MSM_ERR_INVALID;
+    MSM_REQUIRE(ctx, n >= 0 && F >= 1 && ld >= F && lag >= 1, "msm_moments_from_lagged: bad shape / lag");
+    MSM_REQUIRE(ctx, dtype == MSM_F32 || dtype == MSM_F64, "msm_moments_from_lagged: bad dtype");
+    MSM_REQUIRE(ctx, d_shift && d_moments && d_sums && (d_x || n == 0), "msm_moments_from_lagged: NULL pointer");
+    MSM_REQUIRE(ctx, n_seg >= 0 && n_seg <= MSM_SEG_INLINE && (n_seg == 0 || (h_seg_start && h_seg_stop)),
+                "msm_moments_from_lagged: at most %d segments per call", MSM_SEG_INLINE);
+    if (PARAMS) {
+        MSM_REQUIRE(ctx, n_rows >= 1.0, "msm_moments_tail: need n_rows >= 1");
+        MSM_REQUIRE(ctx, d_mean && d_scale && d_inv_scale, "msm_moments_tail: NULL pointer");
+    }
+    EdgeSegs sg;
+    sg.n = 0;
+    sg.lag = lag;
+    if (n_seg == 0) {
+        if (n > 0) { sg.start[0] = 0; sg.stop[0] = n; sg.n = 1; }
+    } else {
+        for (int q = 0; q < n_seg; ++q) {
+            const int64_t a = std::max<int64_t>(0, h_seg_start[q]), b = std::min<int64_t>(n, h_seg_stop[q]);
+            if (b > a) { sg.start[sg.n] = a; sg.stop[sg.n] = b; ++sg.n; }
+        }
+    }
+    if (dtype == MSM_F32)
+        hipLaunchKernelGGL((moments_from_lagged_kernel<float, PARAMS>), dim3(1), dim3(256), 0, ctx->stream,
+                           (const float*)d_x, F, ld, sg, d_shift, d_moments, d_sums, n_rows, with_std, d_mean, d_scale,
+                           d_inv_scale, (unsigned long long*)d_zero_slot);
+    else
+        hipLaunchKernelGGL((moments_from_lagged_kernel<double, PARAMS>), dim3(1), dim3(256), 0, ctx->stream,
+                           (const double*)d_x, F, ld, sg, d_shift, d_moments, d_sums, n_rows, with_std, d_mean, d_scale,
+                           d_inv_scale, (unsigned long long*)d_zero_slot);
+    MSM_CHECK_LAUNCH(ctx);
+    return MSM_OK;
 }
 
 }  // namespace
@@ -913,31 +966,16 @@ msm_status msm_lagged_moments_onesided(msm_ctx* ctx, const void* d_x, msm_dtype 
 msm_status msm_moments_from_lagged(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n, int F, int64_t ld,
                                    const int64_t* h_seg_start, const int64_t* h_seg_stop, int n_seg, int lag,
                                    const double* d_shift, const double* d_moments, double* d_sums) {
-    if (!ctx) return MSM_ERR_INVALID;
-    MSM_REQUIRE(ctx, n >= 0 && F >= 1 && ld >= F && lag >= 1, "msm_moments_from_lagged: bad shape / lag");
-    MSM_REQUIRE(ctx, dtype == MSM_F32 || dtype == MSM_F64, "msm_moments_from_lagged: bad dtype");
-    MSM_REQUIRE(ctx, d_shift && d_moments && d_sums && (d_x || n == 0), "msm_moments_from_lagged: NULL pointer");
-    MSM_REQUIRE(ctx, n_seg >= 0 && n_seg <= MSM_SEG_INLINE && (n_seg == 0 || (h_seg_start && h_seg_stop)),
-                "msm_moments_from_lagged: at most %d segments per call", MSM_SEG_INLINE);
-    EdgeSegs sg;
-    sg.n = 0;
-    sg.lag = lag;
-    if (n_seg == 0) {
-        if (n > 0) { sg.start[0] = 0; sg.stop[0] = n; sg.n = 1; }
-    } else {
-        for (int q = 0; q < n_seg; ++q) {
-            const int64_t a = std::max<int64_t>(0, h_seg_start[q]), b = std::min<int64_t>(n, h_seg_stop[q]);
-            if (b > a) { sg.start[sg.n] = a; sg.stop[sg.n] = b; ++sg.n; }
-        }
-    }
-    if (dtype == MSM_F32)
-        hipLaunchKernelGGL(moments_from_lagged_kernel<float>, dim3(1), dim3(256), 0, ctx->stream, (const float*)d_x, F, ld,
-                           sg, d_shift, d_moments, d_sums);
-    else
-        hipLaunchKernelGGL(moments_from_lagged_kernel<double>, dim3(1), dim3(256), 0, ctx->stream, (const double*)d_x, F,
-                           ld, sg, d_shift, d_moments, d_sums);
-    MSM_CHECK_LAUNCH(ctx);
-    return MSM_OK;
+    return moments_from_lagged_impl<false>(ctx, d_x, dtype, n, F, ld, h_seg_start, h_seg_stop, n_seg, lag, d_shift,
+                                           d_moments, d_sums, 0.0, 0, nullptr, nullptr, nullptr, nullptr);
+}
+
+msm_status msm_moments_tail(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n, int F, int64_t ld,
+                            const int64_t* h_seg_start, const int64_t* h_seg_stop, int n_seg, int lag,
+                            const double* d_shift, const double* d_moments, double* d_sums, double n_rows, int with_std,
+                            double* d_mean, double* d_scale, double* d_inv_scale, double* d_zero_slot) {
+    return moments_from_lagged_impl<true>(ctx, d_x, dtype, n, F, ld, h_seg_start, h_seg_stop, n_seg, lag, d_shift,
+                                          d_moments, d_sums, n_rows, with_std, d_mean, d_scale, d_inv_scale, d_zero_slot);
 }
 
 }  // extern "C"

@@ -129,15 +129,20 @@ __global__ void fit_scale_kernel(const unsigned long long* __restrict__ absmax_b
 }
 
 // centres[j] = whitened frame floor((j + u_j) * n / k), u_j = hash(seed, j) in [0, 1)
+// zero_sums [k d] / zero_counts [k]: the member sums of the fit that begins, cleared here (the grid has a thread for
+// every word) instead of by a fill of their own
 template <typename T>
 __global__ void init_centers_kernel(const T* __restrict__ x, int64_t n, int d, int64_t ld,
                                     const double* __restrict__ mean, const double* __restrict__ stdv, int k,
                                     unsigned long long seed, double* __restrict__ centers,
                                     const unsigned long long* __restrict__ absmax_bits, double n_total, double tol2,
-                                    FitState* __restrict__ st) {
+                                    FitState* __restrict__ st, unsigned long long* __restrict__ zero_sums,
+                                    unsigned long long* __restrict__ zero_counts) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i == 0 && st) fit_scale_body(absmax_bits, n_total, tol2, st);     // (fit_scale_kernel's job, one launch less)
     if (i >= k * d) return;
+    if (zero_sums) zero_sums[i] = 0ull;
+    if (zero_counts && i < k) zero_counts[i] = 0ull;
     const int j = i / d, f = i - j * d;
     unsigned long long h = seed + 0x9E3779B97F4A7C15ull * (unsigned long long)(j + 1);  // splitmix64
     h = (h ^ (h >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -978,7 +983,8 @@ msm_status filter_stats_buffer(msm_ctx* ctx, unsigned long long** out) {
 template <typename T, int DP, bool ACCUM>
 msm_status launch_filter_dp(msm_ctx* ctx, const T* x, int64_t n, int d, int64_t ld, const double* centers, int k,
                             const double* mean, const double* stdv, const uint4* image, int32_t* labels, double* mindist,
-                            const FitState* st, unsigned long long* sums, unsigned long long* counts, double* upd_centers) {
+                            const FitState* st, unsigned long long* sums, unsigned long long* counts, double* upd_centers,
+                            bool first_pass) {
     constexpr int NF = 4;
     const size_t lds = filter_lds_bytes(k, d, ACCUM);
     // (the centre tables are built by every workgroup of the kernel for itself: no staging launch)
@@ -994,7 +1000,7 @@ msm_status launch_filter_dp(msm_ctx* ctx, const T* x, int64_t n, int d, int64_t 
         MSM_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * kWaves), lds, ctx->stream, x, n, d, ld, k, mean, stdv, image, centers,
                        labels, mindist, st, sums, counts, stats, stats ? upd_centers : nullptr,
-                       stats ? (unsigned int*)(stats + 1) : nullptr);
+                       stats ? (unsigned int*)(stats + 1) : nullptr, (int)first_pass);
     MSM_CHECK_LAUNCH(ctx);
     return MSM_OK;
 }
@@ -1002,12 +1008,13 @@ msm_status launch_filter_dp(msm_ctx* ctx, const T* x, int64_t n, int d, int64_t 
 template <typename T, bool ACCUM>
 msm_status launch_filter(msm_ctx* ctx, const T* x, int64_t n, int d, int64_t ld, const double* centers, int k,
                          const double* mean, const double* stdv, const uint4* image, int32_t* labels, double* mindist,
-                         const FitState* st, unsigned long long* sums, unsigned long long* counts, double* upd_centers) {
+                         const FitState* st, unsigned long long* sums, unsigned long long* counts, double* upd_centers,
+                         bool first_pass) {
     if (filter_dp(d) == 4)
         return launch_filter_dp<T, 4, ACCUM>(ctx, x, n, d, ld, centers, k, mean, stdv, image, labels, mindist, st, sums,
-                                             counts, upd_centers);
+                                             counts, upd_centers, first_pass);
     return launch_filter_dp<T, 10, ACCUM>(ctx, x, n, d, ld, centers, k, mean, stdv, image, labels, mindist, st, sums, counts,
-                                          upd_centers);
+                                          upd_centers, first_pass);
 }
 
 bool filter_fits(int k, int d, bool accum) { return filter_enabled() && d <= kFilterMaxD && filter_lds_bytes(k, d, accum) != 0; }
@@ -1017,7 +1024,9 @@ template <typename T, bool ACCUM>
 msm_status dispatch_mfma(msm_ctx* ctx, const T* x, int64_t n, int d, int64_t ld, const double* centers, int k,
                          const double* mean, const double* stdv, int32_t* labels, double* mindist, const FitState* st,
                          unsigned long long* sums, unsigned long long* counts, const void* image = nullptr,
-                         double* upd_centers = nullptr, bool* folded = nullptr) {
+                         double* upd_centers = nullptr, bool* folded = nullptr, bool first_pass = false) {
+    // first_pass (accumulate passes in delta mode): every frame's previous label counts as -1, whatever `labels` holds;
+    // the filter kernel then never reads the buffer, the all-fp64 kernel gets it filled here
     // upd_centers: close the Lloyd iteration inside the accumulate launch (its last workgroup); *folded tells the caller
     // whether that happened (filter path, small table, not under a capture without the ticket word) or the separate update
     // launch is still due
@@ -1036,8 +1045,9 @@ msm_status dispatch_mfma(msm_ctx* ctx, const T* x, int64_t n, int d, int64_t ld,
         if (upd_centers && !(ACCUM && (int64_t)k * d <= kUpdateWide && (ctx->km_stats || !ctx->capturing))) upd_centers = nullptr;
         if (folded) *folded = upd_centers != nullptr;
         return launch_filter<T, ACCUM>(ctx, x, n, d, ld, centers, k, mean, stdv, (const uint4*)image, labels, mindist, st,
-                                       sums, counts, upd_centers);
+                                       sums, counts, upd_centers, ACCUM && first_pass);
     }
+    if (ACCUM && first_pass && labels) MSM_HIP(ctx, hipMemsetAsync(labels, 0xFF, (size_t)n * sizeof(int32_t), ctx->stream));
 #define MSM_MFMA_CASE(KSV) \
     if (d <= 4 * KSV)      \
         return launch_mfma<T, KSV, ACCUM>(ctx, x, n, d, ld, centers, k, mean, stdv, labels, mindist, st, sums, counts)
@@ -1163,10 +1173,14 @@ msm_status msm_mfma_f16_probe(msm_ctx* ctx, const uint16_t* h_a, const uint16_t*
     return mfma_probe(ctx, true, h_a, h_b, h_c, h_d, n_tiles);
 }
 
-msm_status msm_kmeans_fit_begin(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n, int d, int64_t ld,
-                                const double* d_mean, const double* d_std, int k, uint64_t seed, int init_centers,
-                                double n_total, double tol2, double* d_centers, double* d_state, int absmax_ready) {
+// d_zero_sums [k d] / d_zero_counts [k] (both or neither): member sums to clear for the fit that begins
+static msm_status kmeans_fit_begin_impl(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n, int d, int64_t ld,
+                                        const double* d_mean, const double* d_std, int k, uint64_t seed, int init_centers,
+                                        double n_total, double tol2, double* d_centers, double* d_state, int absmax_ready,
+                                        int64_t* d_zero_sums, int64_t* d_zero_counts) {
     if (!ctx) return MSM_ERR_INVALID;
+    MSM_REQUIRE(ctx, (d_zero_sums == nullptr) == (d_zero_counts == nullptr),
+                "msm_kmeans_fit_begin_clear: member sums and counts must come together");
     MSM_REQUIRE(ctx, n >= 1 && d >= 1 && d <= 256 && k >= 1 && ld >= d, "msm_kmeans_fit_begin: bad shape");
     MSM_REQUIRE(ctx, !absmax_ready || !d_mean, "msm_kmeans_fit_begin: a precomputed max |x| excludes whitening");
     MSM_REQUIRE(ctx, !init_centers || n >= k, "msm_kmeans_fit_begin: fewer frames (%lld) than centres (%d)",
@@ -1191,27 +1205,46 @@ msm_status msm_kmeans_fit_begin(msm_ctx* ctx, const void* d_x, msm_dtype dtype, 
     if (!init_centers) {
         hipLaunchKernelGGL(fit_scale_kernel, dim3(1), dim3(64), 0, ctx->stream, bits, n_total, tol2, (FitState*)d_state);
         MSM_CHECK_LAUNCH(ctx);
+        if (d_zero_sums) {     // no launch here with a thread per word: plain clears
+            MSM_HIP(ctx, hipMemsetAsync(d_zero_sums, 0, (size_t)k * d * sizeof(int64_t), ctx->stream));
+            MSM_HIP(ctx, hipMemsetAsync(d_zero_counts, 0, (size_t)k * sizeof(int64_t), ctx->stream));
+        }
     }
     if (init_centers) {
         const int g2 = msm_ceil_div((int64_t)k * d, 256);
         if (dtype == MSM_F32)
             hipLaunchKernelGGL(init_centers_kernel<float>, dim3(g2), dim3(256), 0, ctx->stream, (const float*)d_x, n, d,
                                ld, d_mean, d_std, k, (unsigned long long)seed, d_centers, bits, n_total, tol2,
-                               (FitState*)d_state);
+                               (FitState*)d_state, (unsigned long long*)d_zero_sums, (unsigned long long*)d_zero_counts);
         else
             hipLaunchKernelGGL(init_centers_kernel<double>, dim3(g2), dim3(256), 0, ctx->stream, (const double*)d_x, n,
                                d, ld, d_mean, d_std, k, (unsigned long long)seed, d_centers, bits, n_total, tol2,
-                               (FitState*)d_state);
+                               (FitState*)d_state, (unsigned long long*)d_zero_sums, (unsigned long long*)d_zero_counts);
         MSM_CHECK_LAUNCH(ctx);
     }
     return MSM_OK;
+}
+
+msm_status msm_kmeans_fit_begin(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n, int d, int64_t ld,
+                                const double* d_mean, const double* d_std, int k, uint64_t seed, int init_centers,
+                                double n_total, double tol2, double* d_centers, double* d_state, int absmax_ready) {
+    return kmeans_fit_begin_impl(ctx, d_x, dtype, n, d, ld, d_mean, d_std, k, seed, init_centers, n_total, tol2, d_centers,
+                                 d_state, absmax_ready, nullptr, nullptr);
+}
+
+msm_status msm_kmeans_fit_begin_clear(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n, int d, int64_t ld,
+                                      const double* d_mean, const double* d_std, int k, uint64_t seed, int init_centers,
+                                      double n_total, double tol2, double* d_centers, double* d_state, int absmax_ready,
+                                      int64_t* d_sums, int64_t* d_counts) {
+    return kmeans_fit_begin_impl(ctx, d_x, dtype, n, d, ld, d_mean, d_std, k, seed, init_centers, n_total, tol2, d_centers,
+                                 d_state, absmax_ready, d_sums, d_counts);
 }
 
 static msm_status kmeans_accumulate_impl(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n, int d, int64_t ld,
                                          const double* d_centers, int k, const double* d_mean, const double* d_std,
                                          const void* d_image, const double* d_state, int64_t* d_sums, int64_t* d_counts,
                                          int32_t* d_prev_labels = nullptr, double* d_update_centers = nullptr,
-                                         bool* folded = nullptr) {
+                                         bool* folded = nullptr, bool first_pass = false) {
     if (folded) *folded = false;
     if (!ctx) return MSM_ERR_INVALID;
     MSM_REQUIRE(ctx, n >= 0 && d >= 1 && k >= 1 && ld >= d, "msm_kmeans_accumulate: bad shape");
@@ -1222,33 +1255,50 @@ static msm_status kmeans_accumulate_impl(msm_ctx* ctx, const void* d_x, msm_dtyp
     if (dtype == MSM_F32)
         return dispatch_mfma<float, true>(ctx, (const float*)d_x, n, d, ld, d_centers, k, d_mean, d_std, d_prev_labels,
                                           nullptr, (const FitState*)d_state, (unsigned long long*)d_sums,
-                                          (unsigned long long*)d_counts, d_image, d_update_centers, folded);
+                                          (unsigned long long*)d_counts, d_image, d_update_centers, folded, first_pass);
     return dispatch_mfma<double, true>(ctx, (const double*)d_x, n, d, ld, d_centers, k, d_mean, d_std, d_prev_labels,
                                        nullptr, (const FitState*)d_state, (unsigned long long*)d_sums,
-                                       (unsigned long long*)d_counts, d_image, d_update_centers, folded);
+                                       (unsigned long long*)d_counts, d_image, d_update_centers, folded, first_pass);
 }
 
 // One Lloyd iteration: member sums of the frames under `d_centers` (following the frames that change centre when
 // d_prev_labels is given), then centres <- sums / counts, shift and convergence flag -- in ONE launch where the filter
 // kernel runs (its last workgroup closes the iteration), else msm_kmeans_accumulate* + msm_kmeans_update.
+// first_pass: the first pass of a fit in delta mode -- d_prev_labels need not be filled with -1, it is only written.
+msm_status msm_kmeans_lloyd_pass_from(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n, int d, int64_t ld,
+                                      double* d_centers, int k, const double* d_mean, const double* d_std,
+                                      const void* d_image, double* d_state, int32_t* d_prev_labels, int64_t* d_sums,
+                                      int64_t* d_counts, int first_pass) {
+    bool folded = false;
+    msm_status rs = kmeans_accumulate_impl(ctx, d_x, dtype, n, d, ld, d_centers, k, d_mean, d_std, d_image, d_state, d_sums,
+                                           d_counts, d_prev_labels, d_centers, &folded, first_pass != 0);
+    if (rs != MSM_OK || folded) return rs;
+    return msm_kmeans_update(ctx, d_sums, d_counts, k, d, d_centers, d_state, 0);
+}
+
 msm_status msm_kmeans_lloyd_pass(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n, int d, int64_t ld,
                                  double* d_centers, int k, const double* d_mean, const double* d_std, const void* d_image,
                                  double* d_state, int32_t* d_prev_labels, int64_t* d_sums, int64_t* d_counts) {
-    bool folded = false;
-    msm_status rs = kmeans_accumulate_impl(ctx, d_x, dtype, n, d, ld, d_centers, k, d_mean, d_std, d_image, d_state, d_sums,
-                                           d_counts, d_prev_labels, d_centers, &folded);
-    if (rs != MSM_OK || folded) return rs;
-    return msm_kmeans_update(ctx, d_sums, d_counts, k, d, d_centers, d_state, 0);
+    return msm_kmeans_lloyd_pass_from(ctx, d_x, dtype, n, d, ld, d_centers, k, d_mean, d_std, d_image, d_state,
+                                      d_prev_labels, d_sums, d_counts, 0);
+}
+
+msm_status msm_kmeans_accumulate_delta_from(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n, int d, int64_t ld,
+                                            const double* d_centers, int k, const double* d_mean, const double* d_std,
+                                            const void* d_image, const double* d_state, int32_t* d_prev_labels,
+                                            int64_t* d_sums, int64_t* d_counts, int first_pass) {
+    if (!ctx) return MSM_ERR_INVALID;
+    MSM_REQUIRE(ctx, d_prev_labels || n == 0, "msm_kmeans_accumulate_delta: NULL label buffer");
+    return kmeans_accumulate_impl(ctx, d_x, dtype, n, d, ld, d_centers, k, d_mean, d_std, d_image, d_state, d_sums,
+                                  d_counts, d_prev_labels, nullptr, nullptr, first_pass != 0);
 }
 
 msm_status msm_kmeans_accumulate_delta(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n, int d, int64_t ld,
                                        const double* d_centers, int k, const double* d_mean, const double* d_std,
                                        const void* d_image, const double* d_state, int32_t* d_prev_labels,
                                        int64_t* d_sums, int64_t* d_counts) {
-    if (!ctx) return MSM_ERR_INVALID;
-    MSM_REQUIRE(ctx, d_prev_labels || n == 0, "msm_kmeans_accumulate_delta: NULL label buffer");
-    return kmeans_accumulate_impl(ctx, d_x, dtype, n, d, ld, d_centers, k, d_mean, d_std, d_image, d_state, d_sums,
-                                  d_counts, d_prev_labels);
+    return msm_kmeans_accumulate_delta_from(ctx, d_x, dtype, n, d, ld, d_centers, k, d_mean, d_std, d_image, d_state,
+                                            d_prev_labels, d_sums, d_counts, 0);
 }
 
 msm_status msm_kmeans_accumulate(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n, int d, int64_t ld,

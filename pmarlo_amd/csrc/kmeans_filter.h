@@ -486,7 +486,10 @@ __global__ __launch_bounds__(64 * filter_waves(DP, ACCUM, sizeof(T) == 8 && !WHI
     int32_t* __restrict__ labels,
     double* __restrict__ mindist, const FitState* __restrict__ st, unsigned long long* __restrict__ sums,
     unsigned long long* __restrict__ counts, unsigned long long* __restrict__ n_scanned, double* upd_centers,
-    unsigned int* __restrict__ ticket) {
+    unsigned int* __restrict__ ticket, int first_pass) {
+    // first_pass (delta mode): no frame is booked under a centre yet -- every previous label counts as -1 and `labels`
+    // is only written, so the fit needs neither a fill of the label buffer nor the pass over it (a kernel argument:
+    // uniform, it stays in a scalar register)
     using S = FilterShape<DP>;
     constexpr int kFilterWaves = filter_waves(DP, ACCUM, sizeof(T) == 8 && !WHITEN);
     constexpr int kMT = 64 * kFilterWaves, RF = S::RF, RQ = kFilterRowQ;
@@ -656,7 +659,7 @@ __global__ __launch_bounds__(64 * filter_waves(DP, ACCUM, sizeof(T) == 8 && !WHI
         if (sbi >= k) { sbi = 0; sbest = -__builtin_inf(); }   // every score NaN: label 0, as the fp64 kernel
         int old_s = -1;
         if constexpr (ACCUM) {
-            if (labels) old_s = labels[t];
+            if (labels && !first_pass) old_s = labels[t];
         }
         commit_scan(t, sbi, sbest, zz, old_s);
 #ifdef MSM_KMF_DIAG_COUNT   // diagnostic builds count one kind of event: 1 = plain scans, 2 = bands resolved in fp64
@@ -722,7 +725,7 @@ __global__ __launch_bounds__(64 * filter_waves(DP, ACCUM, sizeof(T) == 8 && !WHI
         // delta mode: the previous label goes out BEFORE the coordinates -- loads return in order
         int old = -1;
         if constexpr (ACCUM) {
-            if (labels) old = labels[fr];
+            if (labels && !first_pass) old = labels[fr];
         }
         double z[DP];
         load_frame(fr, z);

@@ -8,6 +8,7 @@
 // scratch, then one fixed-order pass), so results are run-to-run reproducible.
 #include "common.h"
 #include "wave.h"
+#include "step_folds.h"
 
 namespace {
 
@@ -121,28 +122,14 @@ __global__ void moments_finalize_kernel(const double* __restrict__ sums, const d
     if (count) count[f] = cnt;
 }
 
-// mean / divisor of reduction._preprocess from raw sums, entirely on the device:
-//   mean  = shift + S1/cnt
-//   sigma = sqrt((S2 - S1^2/cnt) / n_rows)      (NaNs were imputed with the mean: they add 0
-//           to the centred square sum but count in the divisor), sigma < 10 eps -> 1
+// mean / divisor of reduction._preprocess from raw sums, entirely on the device (standardise_params_body, step_folds.h)
 __global__ void standardise_params_kernel(const double* __restrict__ sums, const double* __restrict__ shift, int F,
                                           double n_rows, int with_std, double* __restrict__ mean,
                                           double* __restrict__ scale, double* __restrict__ inv_scale) {
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= F) return;
-    const double cnt = sums[f], s1 = sums[F + f], s2 = sums[2 * F + f];
-    double m = 0.0, sd = 1.0;
-    if (cnt > 0.0) {
-        m = shift[f] + s1 / cnt;
-        if (with_std) {
-            const double var = (s2 - s1 * s1 / cnt) / n_rows;
-            sd = var > 0.0 ? sqrt(var) : 0.0;
-            if (sd < 10.0 * 2.220446049250313e-16) sd = 1.0;
-        }
-    }
-    mean[f] = m;
-    scale[f] = sd;
-    inv_scale[f] = 1.0 / sd;
+    standardise_params_body(sums[f], sums[F + f], sums[2 * F + f], shift[f], n_rows, with_std, &mean[f], &scale[f],
+                            &inv_scale[f]);
 }
 
 // ---------------------------------------------------------------------------
@@ -568,11 +555,13 @@ msm_status msm_column_moments(msm_ctx* ctx, const void* d_x, msm_dtype dtype, in
 
 static msm_status project_impl(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n, int F, int64_t ld,
                                const double* d_mu, const double* d_inv_sigma, const double* d_mean2, const double* d_w, int d,
-                               int64_t ldw, double* d_y, int64_t ldy, double* d_absmax, bool finite) {
+                               int64_t ldw, double* d_y, int64_t ldy, double* d_absmax, bool finite,
+                               bool absmax_zeroed = false) {
     if (!ctx) return MSM_ERR_INVALID;
     MSM_REQUIRE(ctx, n >= 0 && F >= 1 && d >= 1 && d <= 64, "msm_project: need n >= 0, F >= 1, 1 <= d <= 64");
     unsigned long long* bits = reinterpret_cast<unsigned long long*>(d_absmax);
-    if (bits) MSM_HIP(ctx, hipMemsetAsync(bits, 0, sizeof(unsigned long long), ctx->stream));
+    // absmax_zeroed: an earlier launch on this stream left the slot at zero (msm_moments_tail): no clear of its own
+    if (bits && !absmax_zeroed) MSM_HIP(ctx, hipMemsetAsync(bits, 0, sizeof(unsigned long long), ctx->stream));
     MSM_REQUIRE(ctx, ld >= F && ldw >= d && ldy >= d, "msm_project: bad leading dimension");
     MSM_REQUIRE(ctx, dtype == MSM_F32 || dtype == MSM_F64, "msm_project: bad dtype");
     if (n == 0) return MSM_OK;
@@ -628,6 +617,13 @@ msm_status msm_project_finite(msm_ctx* ctx, const void* d_x, msm_dtype dtype, in
                               const double* d_mu, const double* d_inv_sigma, const double* d_mean2, const double* d_w,
                               int d, int64_t ldw, double* d_y, int64_t ldy, double* d_absmax) {
     return project_impl(ctx, d_x, dtype, n, F, ld, d_mu, d_inv_sigma, d_mean2, d_w, d, ldw, d_y, ldy, d_absmax, true);
+}
+
+msm_status msm_project_preset(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n, int F, int64_t ld,
+                              const double* d_mu, const double* d_inv_sigma, const double* d_mean2, const double* d_w,
+                              int d, int64_t ldw, double* d_y, int64_t ldy, double* d_absmax, int assume_finite) {
+    return project_impl(ctx, d_x, dtype, n, F, ld, d_mu, d_inv_sigma, d_mean2, d_w, d, ldw, d_y, ldy, d_absmax,
+                        assume_finite != 0, true);
 }
 
 }  // extern "C"

@@ -13,6 +13,7 @@
 #include "common.h"
 #include "wave.h"
 #include "small_eig.h"
+#include "step_folds.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -159,19 +160,7 @@ __global__ __launch_bounds__(kThreads) void row_normalise_kernel(const CT* __res
     }
     __syncthreads();
     if (!is_last) return;
-    for (int v0 = 0; v0 < 1024; v0 += kThreads) {          // diag_mass_kernel's 1024 threads, kThreads at a time
-        const int v = v0 + threadIdx.x;
-        double t = 0.0;
-        for (int q = v; q < k; q += 1024) t += __hip_atomic_load(&tdiag[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        t = wave_sum_down(t);
-        if ((v & 63) == 0) red[v >> 6] = t;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double s = 0.0;
-        for (int w = 0; w < 16; ++w) s += red[w];
-        *diag_out = k > 0 ? s / (double)k : __builtin_nan("");
-    }
+    diag_mass_close<kThreads>(tdiag, k, red, diag_out);    // diag_mass_kernel's 1024 threads, kThreads at a time
 }
 
 // T_full = I with the active block; pi_full = 0 outside the active set (_estimation.py:174-181)

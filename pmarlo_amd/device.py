@@ -601,6 +601,22 @@ class Engine:
               self.handle)
         return out, pairs
 
+    def count_transitions_normalised(self, labels: DeviceArray, k: int, lag: int, T: DeviceArray, rowsum: DeviceArray,
+                                     diag_mass: DeviceArray, *, starts=None, stops=None, stride: int = 1,
+                                     out: DeviceArray | None = None, pairs: DeviceArray | None = None):
+        """count_transitions + row_normalise_into with the same bits, in the counting launch itself where the dense
+        two-pass counting runs (msm_count_transitions_normalised) -> (counts, pairs)."""
+        n = labels.size
+        if starts is None:
+            starts, stops = segments_to_bounds(None, n)
+        starts, stops = self._seg_ptrs(starts, stops)
+        out = out if out is not None else self.empty((k, k), np.int64)
+        pairs = pairs if pairs is not None else self.empty((1,), np.int64)
+        check(lib.msm_count_transitions_normalised(self.handle, labels.ptr, n, starts.ctypes.data, stops.ctypes.data,
+                                                   len(starts), int(lag), int(stride), int(k), out.ptr, pairs.ptr, T.ptr,
+                                                   rowsum.ptr, diag_mass.ptr), self.handle)
+        return out, pairs
+
     def count_transitions_weighted(self, labels: DeviceArray, weights: DeviceArray, k: int, lag: int, *,
                                    starts=None, stops=None, stride: int = 1,
                                    out: DeviceArray | None = None, pairs: DeviceArray | None = None):
@@ -764,6 +780,24 @@ class Engine:
                                           moments.ptr, out.ptr), self.handle)
         return out
 
+    def moments_tail(self, x: DeviceArray, lag: int, shift: DeviceArray, moments: DeviceArray, n_rows: float,
+                     with_std: bool = True, *, starts=None, stops=None, sums: DeviceArray | None = None, out=None,
+                     zero_slot: DeviceArray | None = None, ld: int | None = None):
+        """moments_from_lagged + standardise_params in one launch, same bits -> (sums, (mean, scale, inv_scale)).
+        zero_slot: one 8-byte device word the launch also clears (the max |Y| slot of a fit state, for
+        project(absmax_preset=True))."""
+        n, F = x.shape
+        if starts is None:
+            starts, stops = segments_to_bounds(None, n)
+        starts, stops = self._seg_ptrs(starts, stops)
+        sums = sums if sums is not None else self.empty((3 * F,), np.float64)
+        mean, scale, inv = out if out is not None else tuple(self.empty((F,), np.float64) for _ in range(3))
+        check(lib.msm_moments_tail(self.handle, x.ptr, _dtype_code(x.dtype), n, F, int(F if ld is None else ld),
+                                   starts.ctypes.data, stops.ctypes.data, len(starts), int(lag), shift.ptr, moments.ptr,
+                                   sums.ptr, float(n_rows), int(bool(with_std)), mean.ptr, scale.ptr, inv.ptr,
+                                   zero_slot.ptr if zero_slot is not None else None), self.handle)
+        return sums, (mean, scale, inv)
+
     def tica_solve(self, moments: DeviceArray, F: int, *, scale: DeviceArray | None = None,
                    epsilon: float = 1e-6, kinetic_map: bool = True, out=None, n_lead: int = 0):
         """-> (eigvals [F], coeffs [F,F], mean [F], rank int32[1]) on the device (`out`: the same four, preallocated).
@@ -783,17 +817,22 @@ class Engine:
 
     def project(self, x: DeviceArray, mu: DeviceArray, inv_sigma: DeviceArray, W: DeviceArray, d: int, *,
                 mean2: DeviceArray | None = None, out: DeviceArray | None = None,
-                absmax: DeviceArray | None = None, assume_finite: bool = False, ld: int | None = None) -> DeviceArray:
+                absmax: DeviceArray | None = None, assume_finite: bool = False, ld: int | None = None,
+                absmax_preset: bool = False) -> DeviceArray:
         """`absmax` (one f64, e.g. slot 2 of a k-means fit state) receives max |Y| from the same pass.
+        absmax_preset: an earlier call on the stream left `absmax` at zero (moments_tail's zero_slot): no clear here.
         assume_finite: X holds no NaN (column_moments' count tells); the per-element NaN test is left out.
         ``ld``: row stride in elements when x is a wider buffer's left block."""
         n, F = x.shape
         ldw = W.shape[1]
         out = out if out is not None else self.empty((n, d), np.float64)
-        fn = lib.msm_project_finite if assume_finite else lib.msm_project
-        check(fn(self.handle, x.ptr, _dtype_code(x.dtype), n, F, int(F if ld is None else ld), mu.ptr, inv_sigma.ptr,
-                 mean2.ptr if mean2 is not None else None, W.ptr, int(d), ldw, out.ptr,
-                 out.shape[1], absmax.ptr if absmax is not None else None), self.handle)
+        args = (self.handle, x.ptr, _dtype_code(x.dtype), n, F, int(F if ld is None else ld), mu.ptr, inv_sigma.ptr,
+                mean2.ptr if mean2 is not None else None, W.ptr, int(d), ldw, out.ptr, out.shape[1],
+                absmax.ptr if absmax is not None else None)
+        if absmax_preset:
+            check(lib.msm_project_preset(*args, int(bool(assume_finite))), self.handle)
+        else:
+            check((lib.msm_project_finite if assume_finite else lib.msm_project)(*args), self.handle)
         return out
 
     def _mlp_on_device(self, spec):
@@ -1050,32 +1089,44 @@ class Engine:
     def kmeans_fit_begin(self, x: DeviceArray, k: int, *, seed: int, n_total: int, tol2: float,
                          mean: DeviceArray | None = None, std: DeviceArray | None = None,
                          centers: DeviceArray | None = None, init_centers: bool = True,
-                         state: DeviceArray | None = None, absmax_ready: bool = False):
-        """absmax_ready: slot 2 of `state` already holds max |x| (left there by project(absmax=...))."""
+                         state: DeviceArray | None = None, absmax_ready: bool = False,
+                         sums: DeviceArray | None = None, counts: DeviceArray | None = None):
+        """absmax_ready: slot 2 of `state` already holds max |x| (left there by project(absmax=...)).
+        sums [k*d] / counts [k] (int64, both or neither): the member sums of the fit, zeroed by the same launch."""
         n, d = x.shape
         centers = centers if centers is not None else self.empty((k, d), np.float64)
         state = state if state is not None else self.zeros((8,), np.float64)
-        check(lib.msm_kmeans_fit_begin(self.handle, x.ptr, _dtype_code(x.dtype), n, d, d,
-                                       mean.ptr if mean is not None else None,
-                                       std.ptr if std is not None else None, int(k), int(seed) & (2**64 - 1),
-                                       int(bool(init_centers)), float(n_total), float(tol2), centers.ptr, state.ptr,
-                                       int(bool(absmax_ready))), self.handle)
+        args = (self.handle, x.ptr, _dtype_code(x.dtype), n, d, d, mean.ptr if mean is not None else None,
+                std.ptr if std is not None else None, int(k), int(seed) & (2**64 - 1), int(bool(init_centers)),
+                float(n_total), float(tol2), centers.ptr, state.ptr, int(bool(absmax_ready)))
+        if (sums is None) != (counts is None):
+            raise ValueError("kmeans_fit_begin: sums and counts must come together")
+        if sums is not None:
+            if sums.size != k * d or counts.size != k:
+                raise ValueError("kmeans_fit_begin: sums must hold k*d and counts k entries")
+            check(lib.msm_kmeans_fit_begin_clear(*args, sums.ptr, counts.ptr), self.handle)
+        else:
+            check(lib.msm_kmeans_fit_begin(*args), self.handle)
         return centers, state
 
     def kmeans_accumulate(self, x: DeviceArray, centers: DeviceArray, state: DeviceArray, sums: DeviceArray,
                           counts: DeviceArray, *, mean: DeviceArray | None = None, std: DeviceArray | None = None,
-                          image: DeviceArray | None = None, prev_labels: DeviceArray | None = None):
+                          image: DeviceArray | None = None, prev_labels: DeviceArray | None = None,
+                          first_pass: bool = False):
         """Member sums / counts of one Lloyd pass.  With `prev_labels` (int32 [n], -1 before the first pass, updated
         in place) only the frames that changed centre move their contribution: `sums` / `counts` must then persist
-        between the passes (kmeans_update(clear=False))."""
+        between the passes (kmeans_update(clear=False)).  first_pass: the first pass of a fit -- `prev_labels` need
+        not hold -1, its contents are ignored."""
         n, d = x.shape
         k = centers.shape[0]
         if prev_labels is not None:
-            check(lib.msm_kmeans_accumulate_delta(self.handle, x.ptr, _dtype_code(x.dtype), n, d, d, centers.ptr, k,
-                                                  mean.ptr if mean is not None else None,
-                                                  std.ptr if std is not None else None,
-                                                  image.ptr if image is not None else None, state.ptr,
-                                                  prev_labels.ptr, sums.ptr, counts.ptr), self.handle)
+            args = (self.handle, x.ptr, _dtype_code(x.dtype), n, d, d, centers.ptr, k,
+                    mean.ptr if mean is not None else None, std.ptr if std is not None else None,
+                    image.ptr if image is not None else None, state.ptr, prev_labels.ptr, sums.ptr, counts.ptr)
+            if first_pass:
+                check(lib.msm_kmeans_accumulate_delta_from(*args, 1), self.handle)
+            else:
+                check(lib.msm_kmeans_accumulate_delta(*args), self.handle)
             return
         check(lib.msm_kmeans_accumulate_packed(self.handle, x.ptr, _dtype_code(x.dtype), n, d, d, centers.ptr, k,
                                                mean.ptr if mean is not None else None,
@@ -1134,16 +1185,20 @@ class Engine:
 
     def kmeans_lloyd_pass(self, x: DeviceArray, centers: DeviceArray, state: DeviceArray, sums: DeviceArray,
                           counts: DeviceArray, *, mean: DeviceArray | None = None, std: DeviceArray | None = None,
-                          image: DeviceArray | None = None, prev_labels: DeviceArray | None = None):
+                          image: DeviceArray | None = None, prev_labels: DeviceArray | None = None,
+                          first_pass: bool = False):
         """One Lloyd iteration on a single shard: kmeans_accumulate + kmeans_update(clear=False), in one launch where the
-        filter kernel runs (msm_kmeans_lloyd_pass)."""
+        filter kernel runs (msm_kmeans_lloyd_pass).  first_pass: as in kmeans_accumulate."""
         n, d = x.shape
         k = centers.shape[0]
-        check(lib.msm_kmeans_lloyd_pass(self.handle, x.ptr, _dtype_code(x.dtype), n, d, d, centers.ptr, k,
-                                        mean.ptr if mean is not None else None, std.ptr if std is not None else None,
-                                        image.ptr if image is not None else None, state.ptr,
-                                        prev_labels.ptr if prev_labels is not None else None, sums.ptr, counts.ptr),
-              self.handle)
+        args = (self.handle, x.ptr, _dtype_code(x.dtype), n, d, d, centers.ptr, k,
+                mean.ptr if mean is not None else None, std.ptr if std is not None else None,
+                image.ptr if image is not None else None, state.ptr,
+                prev_labels.ptr if prev_labels is not None else None, sums.ptr, counts.ptr)
+        if first_pass:
+            check(lib.msm_kmeans_lloyd_pass_from(*args, 1), self.handle)
+        else:
+            check(lib.msm_kmeans_lloyd_pass(*args), self.handle)
 
     def kmeans_update(self, sums: DeviceArray, counts: DeviceArray, centers: DeviceArray, state: DeviceArray,
                       clear: bool = True):

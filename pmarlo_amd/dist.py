@@ -399,6 +399,12 @@ class ShardedMSM:
         # passes and the final assignment (None when d / k are outside the filter's range)
         nbytes = eng.kmeans_image_bytes(n, d)
         self.km_image = eng.empty((nbytes,), np.uint8) if nbytes else None
+        # Single-shard step: the clears and the one-workgroup launches between the large kernels ride in their
+        # neighbours (moments_tail, project(absmax_preset), kmeans_fit_begin(sums, counts), first_pass,
+        # count_transitions_normalised): same bits, six launches fewer.  MSM_STEP_FOLDS=0 (read here, once) keeps the
+        # separate calls, for A/B timing and tests; so does an engine without those methods (a host stand-in).
+        self.folds = (not multi_shard and os.environ.get("MSM_STEP_FOLDS", "1") != "0"
+                      and all(hasattr(eng, m) for m in ("moments_tail", "count_transitions_normalised")))
         self.accum_events: list = []
         self.stage_events: dict = {}
         self.time_accum = False
@@ -425,6 +431,8 @@ class ShardedMSM:
         eng, cfg, b, comm = self.eng, self.cfg, self.buf, self.comm
         multi = comm is not None and (comm.world > 1 or self.always_exchange)
         F, d, k = cfg.n_features, cfg.cluster_dim, cfg.k
+        folds = self.folds and not multi
+        absmax_slot = b["fit_state"].view((1,), offset_elems=2)
         self._stamp("begin")
         # 0. featurize: pair distances from the resident coordinates
         if self.xyz is not None:
@@ -434,11 +442,16 @@ class ShardedMSM:
             # 1. time-lagged raw moments about the shared shift (fp64 MFMA): the only pass over X before the
             #    projection -- the standardisation sums follow from them and 2 * lag edge frames
             eng.lagged_moments(self.x, cfg.lag, b["shift"], assume_finite=True, out=b["lagged"], symmetric=True)
-            eng.moments_from_lagged(self.x, cfg.lag, b["shift"], b["lagged"], out=b["mom_sums"])
-            if multi:
-                comm.allreduce_sum("moments")
-            eng.standardise_params(b["mom_sums"], b["shift"], F, float(self.n_total), True,
-                                   out=(self.mean, self.scale, self.inv_scale))
+            if folds:
+                # the column sums, the standardisation parameters and the clear of the max |Y| slot in one launch
+                eng.moments_tail(self.x, cfg.lag, b["shift"], b["lagged"], float(self.n_total), True,
+                                 sums=b["mom_sums"], out=(self.mean, self.scale, self.inv_scale), zero_slot=absmax_slot)
+            else:
+                eng.moments_from_lagged(self.x, cfg.lag, b["shift"], b["lagged"], out=b["mom_sums"])
+                if multi:
+                    comm.allreduce_sum("moments")
+                eng.standardise_params(b["mom_sums"], b["shift"], F, float(self.n_total), True,
+                                       out=(self.mean, self.scale, self.inv_scale))
             self._stamp("moments")
             # 2. TICA solve (every rank solves the same F x F problem on identical bits)
             #    and only the tica_dim components the projection reads are solved for
@@ -448,11 +461,14 @@ class ShardedMSM:
             # 3. projection; max |Y| (the fixed-point scale of the Lloyd sums needs it) falls out of the same pass
             # (x - shift) / sigma - m2: m2 is the symmetric mean about the SAME shift the moments used
             eng.project(self.x, b["shift"], self.inv_scale, self.W, d, mean2=self.m2, out=self.Y,
-                        absmax=b["fit_state"].view((1,), offset_elems=2), assume_finite=True)
+                        absmax=absmax_slot, assume_finite=True, **({"absmax_preset": True} if folds else {}))
             self._stamp("project")
         # 4. k-means: fixed number of Lloyd iterations over all frames
+        acc = self.km_local if self.km_local is not None else b["km_acc"]
+        acc_sums, acc_counts = acc.view((k * d,), np.int64), acc.view((k,), np.int64, offset_elems=k * d)
         eng.kmeans_fit_begin(self.Y, k, seed=cfg.seed, n_total=self.n_total, tol2=0.0, centers=b["centers"],
-                             state=b["fit_state"], absmax_ready=cfg.tica_dim > 0)
+                             state=b["fit_state"], absmax_ready=cfg.tica_dim > 0,
+                             **({"sums": acc_sums, "counts": acc_counts} if folds else {}))
         if multi:
             # identical start on every rank in ONE collective: the MIN over [centres | scale] where every rank but 0
             # offers 0x7F7F... = 1.4e306 for the centres (finite coordinates pass through bit for bit) and its own
@@ -463,21 +479,22 @@ class ShardedMSM:
             comm.allreduce_min("start")
             b["fit_scale"].copy_from(b["start_scale"])
             comm.reciprocal("fit_inv_scale", "fit_scale")
-        acc = self.km_local if self.km_local is not None else b["km_acc"]
-        acc.zero_()
-        acc_sums, acc_counts = acc.view((k * d,), np.int64), acc.view((k,), np.int64, offset_elems=k * d)
-        self.labels.fill_bytes_(0xFF)          # the centre each frame is booked under: none yet
+        if not folds:
+            acc.zero_()
+            self.labels.fill_bytes_(0xFF)          # the centre each frame is booked under: none yet
         if self.km_image is not None:
             # the frames' scale from max |Y| in slot 2 of the fit state (left there by the projection or fit_begin)
             eng.kmeans_pack(self.Y, image=self.km_image, absmax=b["fit_state"].view((1,), offset_elems=2))
-        for _ in range(cfg.kmeans_iters):
+        for it in range(cfg.kmeans_iters):
+            # folds: the first pass takes every frame as booked under no centre, whatever the label buffer holds
+            first = {"first_pass": True} if folds and it == 0 else {}
             if self.time_accum:
                 e0, e1 = eng.event(), eng.event()
                 e0.record()
             if not multi:
                 # one shard: the accumulate launch closes the iteration itself (its last workgroup)
                 eng.kmeans_lloyd_pass(self.Y, b["centers"], b["fit_state"], acc_sums, acc_counts,
-                                      image=self.km_image, prev_labels=self.labels)
+                                      image=self.km_image, prev_labels=self.labels, **first)
             else:
                 eng.kmeans_accumulate(self.Y, b["centers"], b["fit_state"], acc_sums, acc_counts,
                                       image=self.km_image, prev_labels=self.labels)
@@ -499,6 +516,11 @@ class ShardedMSM:
             # the matrix of the model lag (the first lag of the scan that equals cfg.lag, else the first one)
             li = list(cfg.lags).index(cfg.lag) if cfg.lag in cfg.lags else 0
             eng.row_normalise_into(b["counts"].view((k, k), offset_elems=li * k * k), self.T, self.rowsum, self.diag)
+        elif folds:
+            # counts and the row-normalised matrix from one launch (the workgroup that owns a row normalises it)
+            eng.count_transitions_normalised(self.labels, k, cfg.lag, self.T, self.rowsum, self.diag,
+                                             out=b["counts"].view((k, k)),
+                                             pairs=b["counts"].view((1,), offset_elems=k * k))
         else:
             eng.count_transitions(self.labels, k, cfg.lag, out=b["counts"].view((k, k)),
                                   pairs=b["counts"].view((1,), offset_elems=k * k))
