@@ -154,6 +154,39 @@ msm_status msm_featurize_spec(msm_ctx* ctx, const float* d_xyz, int64_t n, int A
                               int64_t n_box, const int32_t* d_rec, const float* d_param, int F, int width,
                               int mic, float* d_out, int64_t ld, int col_off);
 
+/* The adjoint of msm_featurize_spec: d_gxyz[t, a, :] = sign * sum_f d_gfeat[t, col_off + col(f)] * d feature_f / d x_a,
+ * float64 [n, A, 3], for the record table, box rules and mic modes above.  Used with sign = -1 on dE/dfeature it
+ * gives the force on every atom.
+ *   Bond vectors are the forward's: the same fp32 difference and the same minimum-image step, then widened to fp64;
+ *   everything after that is fp64.  The image shift is piecewise constant, so a wrapped vector differentiates like a
+ *   plain difference; there is no gradient with respect to the box.
+ *   Jacobians are closed forms: distance v / |v|; angle -1 / sin(theta) d cos(theta), written on v1, v2 and v1 x v2
+ *   (d theta / d v1 = v1 x (v1 x v2) / (|v1|^2 |v1 x v2|)); dihedral the four-atom formula on c0 = b0 x b1,
+ *   c1 = b1 x b2 and |b1| (d phi / d x0 = -|b1| c0 / |c0|^2, d phi / d x3 = |b1| c1 / |c1|^2; the +2 pi wrap does not
+ *   enter); MSM_FEAT_COSSIN: (g_cos * -sin(phi) + g_sin * cos(phi)) times the dihedral's Jacobian, with cos and sin
+ *   taken from the forward's (x, y), no inverse trigonometry.  d_param[f] multiplies every Jacobian.  A contact is
+ *   a step function and contributes nothing.
+ *   Degenerate geometry: where the forward's floor, clamp or mask is active -- a squared norm at or below 1e-12,
+ *   |cos(theta)| >= 1 (or v1 x v2 = 0), |x| + |y| < 1e-12 of a dihedral, all evaluated in this function's fp64
+ *   arithmetic -- the feature contributes exactly zero.  DIVERGENCE from torch's autograd, which returns 0, inf or
+ *   NaN there depending on the branch (sqrt at the floor, acos at the clamp, atan2 at the origin).
+ *   A record with an unknown kind, a column outside [0, width), an atom outside [0, A), or a flagged record under a
+ *   singular box contributes nothing (the forward wrote NaN there, and its consumer hands a NaN gradient back).
+ *   A frame whose gradient block [col_off, col_off + width) holds a non-finite value gets NaN on ALL its atoms and
+ *   disturbs no other frame.  NaN coordinates propagate into the atoms they reach.
+ *   d_inc_ptr int32 [A + 1], d_inc int32 [d_inc_ptr[A]]: the atom -> (record, slot) incidence in CSR form, built
+ *   once per table: atom a's entries are d_inc[d_inc_ptr[a] .. d_inc_ptr[a + 1]), each record * 4 + slot (slot: which
+ *   of the record's atoms a is), in ascending order; at most 4 F entries in all.  One thread owns one (frame, atom),
+ *   walks the atom's entries in that order and sums in fp64: no floating-point atomics, equal inputs give equal
+ *   bits, and a frame's result depends neither on n nor on where the frame sits.  An entry naming a record outside
+ *   [0, F), or a slot that is not atom a's, contributes nothing.  An atom without entries is written as 0.0: the
+ *   whole block [n, A, 3] is written.
+ * One plain launch on the context's stream, capturable. */
+msm_status msm_featurize_spec_vjp(msm_ctx* ctx, const float* d_xyz, int64_t n, int A, const float* d_box,
+                                  int64_t n_box, const int32_t* d_rec, const float* d_param, int F, int width,
+                                  int mic, const double* d_gfeat, int64_t ldg, int col_off,
+                                  const int32_t* d_inc_ptr, const int32_t* d_inc, double sign, double* d_gxyz);
+
 /* Structure features whose reference implementation is an mdtraj algorithm (S/features/builtins.py:171-250: the
  * built-ins "sasa", "hbonds_count", "ssfrac", all three in the default feature set of S/api/features.py:378).
  *   sasa: Shrake-Rupley accessible area per atom, float32 [n, A] (nm^2), as mdtraj.shrake_rupley computes it
@@ -572,6 +605,53 @@ msm_status msm_mlp_loss_grad(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int
 msm_status msm_adamw_step(msm_ctx* ctx, float* d_params, const double* d_grad, double* d_m, double* d_v, int64_t n,
                           int64_t step, double lr, double beta1, double beta2, double eps, double weight_decay,
                           double clip, double* d_out);
+
+/* ---- Using a trained network: the gradient with respect to the inputs, and the bias potential -------------------
+ *
+ * msm_mlp_vjp: forward pass in evaluation mode and the vector-Jacobian product with respect to the input rows, for
+ * the network, packed parameters and scaler of msm_mlp_forward, in ONE launch (forward and backward of a group of 16
+ * frames back to back, the tape read while it is still in L2).
+ *   d_out [n, ldo] f64 or NULL: the outputs, bit-identical to msm_mlp_forward's.
+ *   d_energy [n] f64 or NULL: strength * sum_c y_c^2.
+ *   d_gout [n, ldgo] f64: the upstream gradient dE/dy; NULL: E is the energy above and 2 strength y goes upstream.
+ *   d_gx [n, ldgx] f64, ldgx >= F: dE/dx.  The adjoints are those of msm_mlp_loss_grad with dropout off, carried on
+ *       past the first Linear (dA_0 = du_0 W_0), through the input LayerNorm if there is one, to dx = dZ / scale;
+ *       the fp32 rounding of Z is the identity for the derivative (as .to(float32) is in torch).  All fp64.
+ *   d_work: msm_mlp_vjp_workspace(...) bytes (0: outside the envelope), given in work_bytes: per frame the scaled
+ *       inputs (with an input LayerNorm), each hidden LayerNorm's input and each activation's argument.
+ * A frame with a non-finite Z is NaN in its own rows of d_out, d_energy and d_gx only; every result of a frame
+ * depends on that frame alone, bit for bit.  Envelope and messages are msm_mlp_forward's.  Capturable.
+ *
+ * msm_bias_energy_forces: the harmonic bias of a DeepTICA collective variable (CVBiasPotential with
+ * HarmonicExpansionBias, S/features/deeptica/cv_bias_potential.py): positions and box -> features
+ * (msm_featurize_spec) -> scaler and network -> E = strength * sum cv^2, and the force -dE/dx on every atom.
+ *   Three plain launches on the context's stream -- msm_featurize_spec, msm_mlp_vjp with d_gout = NULL,
+ *   msm_featurize_spec_vjp with sign = -1 -- no host synchronisation, capturable; n = 1 is one MD step.  The
+ *   features are msm_featurize_spec's bits, except that a record reading a non-finite coordinate gives NaN (that
+ *   function's floors and clamps turn such a coordinate into a finite value).
+ *   The table has n_rec records and its width is the network's F = h_widths[0]; every column in [0, F) must be
+ *   written by a record (a column no record writes would be read uninitialised).  d_inc_ptr / d_inc: the table's
+ *   incidence (msm_featurize_spec_vjp).  d_energy [n], d_cv [n, ldo] or NULL (the raw network outputs), d_force
+ *   [n, A, 3], all f64.  d_work: msm_bias_workspace(...) bytes: features f32 [n, F], their gradient f64 [n, F] and
+ *   msm_mlp_vjp's tape.  Whatever one of the three steps would refuse is refused before the first launches.
+ *   A frame with a NaN coordinate, an invalid record or (with flagged records) a singular box has NaN energy, CVs
+ *   and forces; no other frame is disturbed. */
+size_t msm_mlp_vjp_workspace(int64_t n, int n_linear, const int32_t* h_widths, int ln_in, int ln_hidden,
+                             int head_activation);
+msm_status msm_mlp_vjp(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n, int F, int64_t ld,
+                       const double* d_mean, const double* d_scale, int n_linear, const int32_t* h_widths,
+                       int activation, int ln_in, int ln_hidden, int head_activation, const float* d_params,
+                       size_t n_params, const double* d_gout, int64_t ldgo, double strength, double* d_energy,
+                       double* d_out, int64_t ldo, double* d_gx, int64_t ldgx, double* d_work, size_t work_bytes);
+size_t msm_bias_workspace(int64_t n, int F, int n_linear, const int32_t* h_widths, int ln_in, int ln_hidden,
+                          int head_activation);
+msm_status msm_bias_energy_forces(msm_ctx* ctx, const float* d_xyz, int64_t n, int A, const float* d_box,
+                                  int64_t n_box, const int32_t* d_rec, const float* d_param, int n_rec,
+                                  const int32_t* d_inc_ptr, const int32_t* d_inc, int mic, const double* d_mean,
+                                  const double* d_scale, int n_linear, const int32_t* h_widths, int activation,
+                                  int ln_in, int ln_hidden, int head_activation, const float* d_params,
+                                  size_t n_params, double strength, double* d_work, size_t work_bytes,
+                                  double* d_energy, double* d_cv, int64_t ldo, double* d_force);
 
 /* ------------------------------------------------------------------ */
 /* k-means                                                          */

@@ -81,6 +81,8 @@ _PROTOTYPES: dict[str, tuple] = {
     "msm_featurize_dihedrals": (_i32, [_vp, _vp, _i64, _i32, _vp, _i32, _i32, _vp, _i64, _i32]),
     "msm_box_from_cell": (_i32, [_vp, _vp, _i64, _vp]),
     "msm_featurize_spec": (_i32, [_vp, _vp, _i64, _i32, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _i32]),
+    "msm_featurize_spec_vjp": (_i32, [_vp, _vp, _i64, _i32, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _i32, _vp, _vp,
+                                      _f64, _vp]),
     "msm_featurize_sasa": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _i32, _vp]),
     "msm_hbond_presence": (_i32, [_vp, _vp, _i64, _i32, _vp, _i32, C.c_float, C.c_float, _vp]),
     "msm_dssp": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _vp]),
@@ -120,6 +122,12 @@ _PROTOTYPES: dict[str, tuple] = {
                                  _vp, _vp, _i64, _vp, C.c_uint64, C.c_uint64, _f64, _f64, _f64, _f64, _vp, _sz, _vp,
                                  _vp, _vp, _i64]),
     "msm_adamw_step": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _f64, _f64, _f64, _f64, _f64, _f64, _vp]),
+    "msm_mlp_vjp_workspace": (_sz, [_i64, _i32, _vp, _i32, _i32, _i32]),
+    "msm_mlp_vjp": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _sz, _vp, _i64,
+                           _f64, _vp, _vp, _i64, _vp, _i64, _vp, _sz]),
+    "msm_bias_workspace": (_sz, [_i64, _i32, _i32, _vp, _i32, _i32, _i32]),
+    "msm_bias_energy_forces": (_i32, [_vp, _vp, _i64, _i32, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp,
+                                      _i32, _i32, _i32, _i32, _vp, _sz, _f64, _vp, _sz, _vp, _vp, _i64, _vp]),
     "msm_kmeans_assign": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _i32, _vp, _vp, _vp, _vp]),
     "msm_kmeans_fit": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _vp, _i32, C.c_uint64, _i32, _i32, _f64, _vp, _vp]),
     "msm_kmeans_fit_begin": (

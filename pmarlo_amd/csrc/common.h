@@ -119,3 +119,9 @@ __device__ __forceinline__ int64_t seg_pair_to_frame(const SegTab& st, int64_t p
 }
 
 static inline int msm_ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+
+// featurize.hip: msm_featurize_spec's checks and launch; with nan_in a record that reads a non-finite coordinate
+// writes NaN (the forward of msm_bias_energy_forces, mlp_vjp.hip)
+msm_status featurize_spec_launch(msm_ctx* ctx, const float* d_xyz, int64_t n, int A, const float* d_box, int64_t n_box,
+                                 const int32_t* d_rec, const float* d_param, int F, int width, int mic, float* d_out,
+                                 int64_t ld, int col_off, bool nan_in);

@@ -9,6 +9,8 @@
 // dihedral = atan2((c0 x c1).b1/|b1|, c0.c1) with c0 = b0 x b1, c1 = b1 x b2 normalised.
 // The per-kind kernels know no periodic box; spec_kernel takes a mixed feature list and
 // replaces flagged bond vectors by their minimum image (pbc.h) before the same arithmetic.
+#include <cfloat>
+
 #include "common.h"
 #include "pbc.h"
 #include "wave.h"
@@ -147,7 +149,11 @@ __global__ __launch_bounds__(kThreads) void rg_kernel(const float* __restrict__ 
 constexpr int kTileElems = 1024;
 constexpr int kTileFrames = 256;
 
-template <bool kSearch>
+// kNanIn (the bias potential's forward): a record that reads a non-finite coordinate writes NaN, which the floors and
+// clamps of the geometry would otherwise turn into a finite value; false: the code of msm_featurize_spec as it was.
+__device__ __forceinline__ bool finite3(V3 v) { return fabsf(v.x) <= FLT_MAX && fabsf(v.y) <= FLT_MAX && fabsf(v.z) <= FLT_MAX; }
+
+template <bool kSearch, bool kNanIn>
 __global__ __launch_bounds__(kThreads, 6) void spec_kernel(const float* __restrict__ xyz, int64_t n, int A,
                                                        const float* __restrict__ box, int64_t n_box,
                                                        const int4* __restrict__ rec, const float* __restrict__ param,
@@ -194,12 +200,15 @@ __global__ __launch_bounds__(kThreads, 6) void spec_kernel(const float* __restri
             const float* w = s_box + (per_frame ? tl * kBoxWords : 0);
             if (wrap && w[18] < 0.0f) valid = false;
             float* row = out + t * ld + col_off;
+            const float* fr = xyz + t * A * 3;
+            if (kNanIn && valid)
+                valid = finite3(ld3(fr + 3 * i0)) && finite3(ld3(fr + 3 * i1)) && (n_atoms < 3 || finite3(ld3(fr + 3 * i2))) &&
+                        (n_atoms < 4 || finite3(ld3(fr + 3 * i3)));
             if (!valid) {
                 row[col] = __builtin_nanf("");
                 if (trig) row[col2] = __builtin_nanf("");
                 continue;
             }
-            const float* fr = xyz + t * A * 3;
             if (kind == MSM_FEAT_DISTANCE || kind == MSM_FEAT_CONTACT) {
                 V3 v = sub(ld3(fr + 3 * i1), ld3(fr + 3 * i0));
                 if (wrap) v = minimum_image<kSearch>(v, w);
@@ -223,6 +232,169 @@ __global__ __launch_bounds__(kThreads, 6) void spec_kernel(const float* __restri
                 if (trig) { row[col] = cosf(ang) * par; row[col2] = sinf(ang) * par; }
                 else row[col] = ang * par;
             }
+        }
+    }
+}
+
+// ---- the adjoint of spec_kernel (msmhip.h: msm_featurize_spec_vjp) ----------------------------------------------
+// Bond vectors are the forward's (fp32 difference, the same minimum_image call), widened to fp64; the image shift is
+// piecewise constant, so they differentiate like plain differences.  Everything below is fp64, written in the
+// operation order of the restatement the tests hold it to.
+struct D3 { double x, y, z; };
+__device__ __forceinline__ D3 wide(V3 v) { return {(double)v.x, (double)v.y, (double)v.z}; }
+__device__ __forceinline__ double dot(D3 a, D3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+__device__ __forceinline__ D3 cross(D3 a, D3 b) {
+    return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
+}
+__device__ __forceinline__ D3 over(D3 a, double s) { return {a.x / s, a.y / s, a.z / s}; }
+__device__ __forceinline__ D3 times(double s, D3 a) { return {s * a.x, s * a.y, s * a.z}; }
+__device__ __forceinline__ D3 plus(D3 a, D3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
+__device__ __forceinline__ D3 minus(D3 a, D3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
+__device__ __forceinline__ D3 neg(D3 a) { return {-a.x, -a.y, -a.z}; }
+
+// What record (r0, r1) adds to atom a, which sits in its slot `slot`: upstream gradient times weight times the
+// closed-form Jacobian of the slot.  Exactly zero for a contact, an unknown kind, a column outside the block, an atom
+// outside [0, A), a slot that is not atom a's, a singular box under a flagged record, and wherever the forward's
+// floor, clamp or mask is active (the conditions are written so that a NaN coordinate is not "degenerate": it
+// propagates).  fr: the frame's coordinates; w: the frame's box words or nullptr; grow: the frame's gradient block.
+template <bool kSearch>
+__device__ __forceinline__ D3 vjp_entry(const float* __restrict__ fr, int A, const float* w, int4 r0, int4 r1,
+                                        float par, int slot, int a, int width, const double* __restrict__ grow) {
+    const D3 zero = {0.0, 0.0, 0.0};
+    const int kind = r0.x, i0 = r0.y, i1 = r0.z, i2 = r0.w, i3 = r1.x, flags = r1.y, col = r1.z, col2 = r1.w;
+    if ((unsigned)kind > (unsigned)MSM_FEAT_DIHEDRAL) return zero;
+    const int n_atoms = kind == MSM_FEAT_DIHEDRAL ? 4 : (kind == MSM_FEAT_ANGLE ? 3 : 2);
+    const bool trig = kind == MSM_FEAT_DIHEDRAL && (flags & MSM_FEAT_COSSIN);
+    if (slot >= n_atoms || col < 0 || col >= width || (trig && (col2 < 0 || col2 >= width))) return zero;
+    bool valid = (unsigned)i0 < (unsigned)A && (unsigned)i1 < (unsigned)A;
+    valid = valid && (n_atoms < 3 || (unsigned)i2 < (unsigned)A) && (n_atoms < 4 || (unsigned)i3 < (unsigned)A);
+    const int mine = slot == 0 ? i0 : (slot == 1 ? i1 : (slot == 2 ? i2 : i3));
+    const bool wrap = w != nullptr && (flags & MSM_FEAT_MIC);
+    if (!valid || mine != a || (wrap && w[18] < 0.0f)) return zero;
+    const double eps = (double)kEps;
+    if (kind == MSM_FEAT_DISTANCE) {
+        V3 v = sub(ld3(fr + 3 * i1), ld3(fr + 3 * i0));
+        if (wrap) v = minimum_image<kSearch>(v, w);
+        const D3 d = wide(v);
+        const double q = dot(d, d);
+        if (q <= eps) return zero;
+        const D3 j = over(d, sqrt(q));
+        return times(grow[col] * (double)par, slot == 1 ? j : neg(j));
+    }
+    if (kind == MSM_FEAT_ANGLE) {
+        const V3 pj = ld3(fr + 3 * i1);
+        V3 f1 = sub(ld3(fr + 3 * i0), pj), f2 = sub(ld3(fr + 3 * i2), pj);
+        if (wrap) { f1 = minimum_image<kSearch>(f1, w); f2 = minimum_image<kSearch>(f2, w); }
+        const D3 v1 = wide(f1), v2 = wide(f2);
+        const double q1 = dot(v1, v1), q2 = dot(v2, v2);
+        const D3 nrm = cross(v1, v2);
+        const double ww = dot(nrm, nrm);
+        const double c = dot(v1, v2) / (sqrt(fmax(q1, eps)) * sqrt(fmax(q2, eps)));
+        if (q1 <= eps || q2 <= eps || fabs(c) >= 1.0 || ww <= 0.0) return zero;
+        const double nw = sqrt(ww);
+        // d theta / d v1 = v1 x (v1 x v2) / (|v1|^2 |v1 x v2|), d theta / d v2 = -v2 x (v1 x v2) / (|v2|^2 |v1 x v2|):
+        // -1 / sin(theta) d cos(theta) with the sine taken from the cross product, sound up to the collinear limit
+        const D3 g1 = over(cross(v1, nrm), q1 * nw), g2 = neg(over(cross(v2, nrm), q2 * nw));
+        const D3 j = slot == 0 ? g1 : (slot == 2 ? g2 : neg(plus(g1, g2)));
+        return times(grow[col] * (double)par, j);
+    }
+    const V3 p0 = ld3(fr + 3 * i0), p1 = ld3(fr + 3 * i1), p2 = ld3(fr + 3 * i2), p3 = ld3(fr + 3 * i3);
+    V3 e0 = sub(p1, p0), e1 = sub(p2, p1), e2 = sub(p3, p2);
+    if (wrap) {
+        e0 = minimum_image<kSearch>(e0, w);
+        e1 = minimum_image<kSearch>(e1, w);
+        e2 = minimum_image<kSearch>(e2, w);
+    }
+    const D3 b0 = wide(e0), b1 = wide(e1), b2 = wide(e2);
+    const D3 c0 = cross(b0, b1), c1 = cross(b1, b2);
+    const double q0 = dot(c0, c0), q1 = dot(c1, c1), qb = dot(b1, b1);
+    if (q0 <= eps || q1 <= eps || qb <= eps) return zero;
+    const double nb = sqrt(qb);
+    const D3 u0 = over(c0, sqrt(q0)), u1 = over(c1, sqrt(q1));
+    const double x = dot(u0, u1), y = dot(cross(u0, u1), over(b1, nb));
+    if (fabs(x) + fabs(y) < eps) return zero;
+    // the four-atom formula for phi = atan2(y, x) above: d phi / d x0 = -|b1| c0 / |c0|^2, d phi / d x3 = |b1| c1 / |c1|^2,
+    // the inner atoms from them and the projections of b0, b2 on b1 (the four add up to zero)
+    const D3 f1 = times(-(nb / q0), c0), f4 = times(nb / q1, c1);
+    const double s01 = dot(b0, b1) / qb, s21 = dot(b2, b1) / qb;
+    D3 j;
+    if (slot == 0) j = f1;
+    else if (slot == 3) j = f4;
+    else if (slot == 1) j = plus(minus(neg(f1), times(s01, f1)), times(s21, f4));
+    else j = minus(plus(neg(f4), times(s01, f1)), times(s21, f4));
+    double coef = grow[col];
+    if (trig) {   // cos(phi) = x / r, sin(phi) = y / r: no inverse trigonometry in the adjoint
+        const double r = sqrt(x * x + y * y);
+        coef = coef * -(y / r) + grow[col2] * (x / r);
+    }
+    return times(coef * (double)par, j);
+}
+
+// A block works on tiles of kVjpFrames consecutive frames; a thread owns one (frame, atom) of the tile and walks the
+// atom's incidence entries in their (ascending) order, so the sum has one order whatever n is.  Threads are ordered
+// frame-fastest inside an atom: with a full tile a wave is one atom's 64 frames, every lane walks the same entries and
+// the wave never diverges; coordinates and gradients of a tile are a few KB that stay in L1.  Boxes as in spec_kernel.
+// 3 A and nf * A fit an int: A <= 2^23 is checked by the entry point.
+constexpr int kVjpFrames = 64;
+
+template <bool kSearch>
+__global__ __launch_bounds__(kThreads) void spec_vjp_kernel(const float* __restrict__ xyz, int64_t n, int A,
+                                                           const float* __restrict__ box, int64_t n_box,
+                                                           const int4* __restrict__ rec, const float* __restrict__ param,
+                                                           int F, int width, const double* __restrict__ gfeat,
+                                                           int64_t ldg, int col_off, const int* __restrict__ inc_ptr,
+                                                           const int* __restrict__ inc, double sign,
+                                                           double* __restrict__ gxyz) {
+    __shared__ float s_box[kVjpFrames * kBoxWords];
+    __shared__ int s_bad[kVjpFrames];   // the frame's gradient block holds a non-finite value
+    const bool per_frame = box != nullptr && n_box != 1;
+    if (box != nullptr && !per_frame && threadIdx.x == 0) box_inverse(box, s_box);
+    for (int64_t t0 = (int64_t)blockIdx.x * kVjpFrames; t0 < n; t0 += (int64_t)gridDim.x * kVjpFrames) {
+        const int nf = (int)min((int64_t)kVjpFrames, n - t0);
+        __syncthreads();   // the previous trip's readers are done (first trip: the one box is in place after the next)
+        for (int i = threadIdx.x; i < nf; i += kThreads) {
+            if (per_frame) box_inverse(box + (t0 + i) * 9, s_box + i * kBoxWords);
+            s_bad[i] = 0;
+        }
+        __syncthreads();
+        for (int e = threadIdx.x; e < nf * width; e += kThreads) {
+            const int tl = e / width;
+            const double g = gfeat[(t0 + tl) * ldg + col_off + (e - tl * width)];
+            if (!(fabs(g) <= DBL_MAX)) atomicOr(&s_bad[tl], 1);
+        }
+        __syncthreads();
+        // atoms no record refers to (most atoms of a solvated system) get exact zeros, NaN in a poisoned frame, in one
+        // coalesced sweep over the tile's contiguous block; the strided stores below are for referenced atoms only
+        const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+        double* tile = gxyz + t0 * A * 3;
+        for (int tl = threadIdx.x >> 6; tl < nf; tl += kThreads / 64) {   // a wave per frame: its 3 A doubles are one run
+            const double fill = s_bad[tl] ? qnan : 0.0;
+            double* row = tile + (int64_t)tl * A * 3;
+            for (int c = threadIdx.x & 63; c < 3 * A; c += 64) {
+                const int a = c / 3;
+                if (min(inc_ptr[a + 1], 4 * F) <= max(inc_ptr[a], 0)) row[c] = fill;
+            }
+        }
+        for (int j = threadIdx.x; j < nf * A; j += kThreads) {
+            const int a = j / nf, tl = j - a * nf;
+            const int first = max(inc_ptr[a], 0), last = min(inc_ptr[a + 1], 4 * F);   // at most four slots a record
+            if (first >= last) continue;
+            const int64_t t = t0 + tl;
+            const float* fr = xyz + t * A * 3;
+            const float* w = box != nullptr ? s_box + (per_frame ? tl * kBoxWords : 0) : nullptr;
+            const double* grow = gfeat + t * ldg + col_off;
+            D3 acc = {0.0, 0.0, 0.0};
+            for (int k = first; k < last; ++k) {
+                const int code = inc[k], f = code >> 2;
+                if (code < 0 || f >= F) continue;
+                const D3 term = vjp_entry<kSearch>(fr, A, w, rec[2 * f], rec[2 * f + 1], param[f], code & 3, a, width, grow);
+                acc = plus(acc, term);
+            }
+            double* out = tile + ((int64_t)tl * A + a) * 3;
+            const bool bad = s_bad[tl] != 0;
+            out[0] = bad ? qnan : sign * acc.x;
+            out[1] = bad ? qnan : sign * acc.y;
+            out[2] = bad ? qnan : sign * acc.z;
         }
     }
 }
@@ -260,6 +432,40 @@ msm_status check_common(msm_ctx* ctx, const char* who, const float* xyz, int64_t
 }
 
 }  // namespace
+
+// msm_featurize_spec, and with nan_in the bias potential's forward (common.h)
+msm_status featurize_spec_launch(msm_ctx* ctx, const float* d_xyz, int64_t n, int A, const float* d_box, int64_t n_box,
+                                 const int32_t* d_rec, const float* d_param, int F, int width, int mic, float* d_out,
+                                 int64_t ld, int col_off, bool nan_in) {
+    if (!ctx) return MSM_ERR_INVALID;
+    const char* who = "msm_featurize_spec";
+    MSM_REQUIRE(ctx, n >= 0 && A >= 1 && F >= 0 && width >= 0, "%s: need n >= 0, A >= 1, F >= 0, width >= 0", who);
+    MSM_REQUIRE(ctx, mic == MSM_MIC_ROUND || mic == MSM_MIC_SEARCH, "%s: mic must be MSM_MIC_ROUND or MSM_MIC_SEARCH, got %d",
+                who, mic);
+    MSM_REQUIRE(ctx, d_box ? (n_box == 1 || n_box == n) : n_box == 0,
+                "%s: n_box=%lld must be 1 or n=%lld with a box, 0 without", who, (long long)n_box, (long long)n);
+    MSM_REQUIRE(ctx, col_off >= 0 && ld >= col_off + (int64_t)width, "%s: output columns [%d, %d) exceed ld=%lld", who,
+                col_off, col_off + width, (long long)ld);
+    if (n == 0 || F == 0) return MSM_OK;
+    MSM_REQUIRE(ctx, d_xyz && d_rec && d_param && d_out, "%s: NULL pointer", who);
+    MSM_REQUIRE(ctx, ((uintptr_t)d_rec & 15) == 0, "%s: the record table must be 16-byte aligned", who);
+    const int tile_frames = std::min(kTileFrames, std::max(1, kTileElems / F));
+    const dim3 grid(grid_for(ctx, ((n + tile_frames - 1) / tile_frames) * kThreads)), block(kThreads);   // a block per tile, capped
+    const int4* rec = reinterpret_cast<const int4*>(d_rec);
+#define MSM_SPEC(S, N)                                                                                             \
+    hipLaunchKernelGGL((spec_kernel<S, N>), grid, block, 0, ctx->stream, d_xyz, n, A, d_box, n_box, rec, d_param, F, \
+                       width, tile_frames, d_out, ld, col_off)
+    if (mic == MSM_MIC_SEARCH) {
+        if (nan_in) MSM_SPEC(true, true);
+        else MSM_SPEC(true, false);
+    } else {
+        if (nan_in) MSM_SPEC(false, true);
+        else MSM_SPEC(false, false);
+    }
+#undef MSM_SPEC
+    MSM_CHECK_LAUNCH(ctx);
+    return MSM_OK;
+}
 
 extern "C" {
 
@@ -334,27 +540,35 @@ msm_status msm_box_from_cell(msm_ctx* ctx, const double* d_cell, int64_t n, floa
 msm_status msm_featurize_spec(msm_ctx* ctx, const float* d_xyz, int64_t n, int A, const float* d_box, int64_t n_box,
                               const int32_t* d_rec, const float* d_param, int F, int width, int mic, float* d_out,
                               int64_t ld, int col_off) {
+    return featurize_spec_launch(ctx, d_xyz, n, A, d_box, n_box, d_rec, d_param, F, width, mic, d_out, ld, col_off, false);
+}
+
+msm_status msm_featurize_spec_vjp(msm_ctx* ctx, const float* d_xyz, int64_t n, int A, const float* d_box, int64_t n_box,
+                                  const int32_t* d_rec, const float* d_param, int F, int width, int mic,
+                                  const double* d_gfeat, int64_t ldg, int col_off, const int32_t* d_inc_ptr,
+                                  const int32_t* d_inc, double sign, double* d_gxyz) {
     if (!ctx) return MSM_ERR_INVALID;
-    const char* who = "msm_featurize_spec";
+    const char* who = "msm_featurize_spec_vjp";
     MSM_REQUIRE(ctx, n >= 0 && A >= 1 && F >= 0 && width >= 0, "%s: need n >= 0, A >= 1, F >= 0, width >= 0", who);
     MSM_REQUIRE(ctx, mic == MSM_MIC_ROUND || mic == MSM_MIC_SEARCH, "%s: mic must be MSM_MIC_ROUND or MSM_MIC_SEARCH, got %d",
                 who, mic);
     MSM_REQUIRE(ctx, d_box ? (n_box == 1 || n_box == n) : n_box == 0,
                 "%s: n_box=%lld must be 1 or n=%lld with a box, 0 without", who, (long long)n_box, (long long)n);
-    MSM_REQUIRE(ctx, col_off >= 0 && ld >= col_off + (int64_t)width, "%s: output columns [%d, %d) exceed ld=%lld", who,
-                col_off, col_off + width, (long long)ld);
-    if (n == 0 || F == 0) return MSM_OK;
-    MSM_REQUIRE(ctx, d_xyz && d_rec && d_param && d_out, "%s: NULL pointer", who);
+    MSM_REQUIRE(ctx, col_off >= 0 && ldg >= col_off + (int64_t)width, "%s: gradient columns [%d, %d) exceed ld=%lld", who,
+                col_off, col_off + width, (long long)ldg);
+    MSM_REQUIRE(ctx, F <= (1 << 28) && A <= (1 << 23), "%s: %d records, %d atoms (at most 2^28, 2^23)", who, F, A);
+    if (n == 0) return MSM_OK;
+    MSM_REQUIRE(ctx, d_xyz && d_gxyz && d_inc_ptr && (width == 0 || d_gfeat), "%s: NULL pointer", who);
+    MSM_REQUIRE(ctx, F == 0 || (d_rec && d_param && d_inc), "%s: NULL pointer", who);
     MSM_REQUIRE(ctx, ((uintptr_t)d_rec & 15) == 0, "%s: the record table must be 16-byte aligned", who);
-    const int tile_frames = std::min(kTileFrames, std::max(1, kTileElems / F));
-    const dim3 grid(grid_for(ctx, ((n + tile_frames - 1) / tile_frames) * kThreads)), block(kThreads);   // a block per tile, capped
+    const dim3 grid(grid_for(ctx, ((n + kVjpFrames - 1) / kVjpFrames) * kThreads)), block(kThreads);   // a block per tile, capped
     const int4* rec = reinterpret_cast<const int4*>(d_rec);
     if (mic == MSM_MIC_SEARCH)
-        hipLaunchKernelGGL(spec_kernel<true>, grid, block, 0, ctx->stream, d_xyz, n, A, d_box, n_box, rec, d_param, F,
-                           width, tile_frames, d_out, ld, col_off);
+        hipLaunchKernelGGL(spec_vjp_kernel<true>, grid, block, 0, ctx->stream, d_xyz, n, A, d_box, n_box, rec, d_param, F,
+                           width, d_gfeat, ldg, col_off, d_inc_ptr, d_inc, sign, d_gxyz);
     else
-        hipLaunchKernelGGL(spec_kernel<false>, grid, block, 0, ctx->stream, d_xyz, n, A, d_box, n_box, rec, d_param, F,
-                           width, tile_frames, d_out, ld, col_off);
+        hipLaunchKernelGGL(spec_vjp_kernel<false>, grid, block, 0, ctx->stream, d_xyz, n, A, d_box, n_box, rec, d_param, F,
+                           width, d_gfeat, ldg, col_off, d_inc_ptr, d_inc, sign, d_gxyz);
     MSM_CHECK_LAUNCH(ctx);
     return MSM_OK;
 }

@@ -134,6 +134,64 @@ __device__ __forceinline__ void mlp_linear(const double* cur, double* nxt, const
     }
 }
 
+// ---- what the backward passes share (mlp_train.hip, mlp_vjp.hip) ----
+__device__ __forceinline__ double mlp_activate_grad(double x, int kind) {
+    switch (kind) {
+        case kActGelu:
+            return 0.5 * (1.0 + erf(x * 0.70710678118654752440)) + x * exp(-0.5 * x * x) * 0.39894228040143267794;
+        case kActRelu: return x <= 0.0 ? 0.0 : 1.0;
+        case kActElu: return x > 0.0 ? 1.0 : exp(x);
+        case kActSelu: return kSeluScale * (x > 0.0 ? 1.0 : kSeluAlpha * exp(x));
+        case kActLeakyRelu: return x > 0.0 ? 1.0 : 0.01;
+        default: {
+            const double t = tanh(x);
+            return 1.0 - t * t;
+        }
+    }
+}
+
+// rows 0 .. rows-1 of an LDS image (row stride S, w entries each) to / from global rows of w doubles, coalesced
+__device__ __forceinline__ void save_rows(const double* img, int S, int w, int rows, double* __restrict__ dst, int lane) {
+    for (int r = 0; r < rows; ++r)
+        for (int f = lane; f < w; f += 64) dst[(size_t)r * w + f] = img[r * S + f];
+}
+
+// LayerNorm adjoint of frame j's row: `grow` holds dL/d(LN output) on entry and dL/d(LN input) on exit; `xin` is
+// the row the LayerNorm was applied to (global).  dL/d(output) and dL/d(output) * xhat go to dh / dhx (the beta and
+// gamma gradients are their column sums).  Lane g owns entries g, g + 4, ...; `store`: the slot exists.
+__device__ __forceinline__ void mlp_layer_norm_adjoint(double* grow, int g, int w, const double* __restrict__ xin,
+                                                       const float* __restrict__ gamma, double* __restrict__ dh,
+                                                       double* __restrict__ dhx, bool store) {
+    double s = 0.0;
+    for (int f = g; f < w; f += 4) s += xin[f];
+    const double mean = xrow_reduce(s, op_sum{}) / (double)w;
+    double q = 0.0;
+    for (int f = g; f < w; f += 4) {
+        const double c = xin[f] - mean;
+        q += c * c;
+    }
+    const double rstd = 1.0 / sqrt(xrow_reduce(q, op_sum{}) / (double)w + 1e-5);
+    double s1 = 0.0, s2 = 0.0;
+    for (int f = g; f < w; f += 4) {
+        const double xhat = (xin[f] - mean) * rstd;
+        const double d = grow[f];
+        if (store) {
+            dh[f] = d;
+            dhx[f] = d * xhat;
+        }
+        const double dxhat = d * (double)gamma[f];
+        grow[f] = dxhat;
+        s1 += dxhat;
+        s2 += dxhat * xhat;
+    }
+    s1 = xrow_reduce(s1, op_sum{}) / (double)w;
+    s2 = xrow_reduce(s2, op_sum{}) / (double)w;
+    for (int f = g; f < w; f += 4) {
+        const double xhat = (xin[f] - mean) * rstd;
+        grow[f] = rstd * (grow[f] - s1 - xhat * s2);
+    }
+}
+
 constexpr size_t kMlpAnyParams = ~(size_t)0;   // mlp_make_plan: do not check the parameter count
 
 // The plan of a network from the arguments every entry point takes; `fn` names the entry in the messages.  Checks

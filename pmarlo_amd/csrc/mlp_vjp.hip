@@ -1,0 +1,276 @@
+// Gradient of a DeepTICA network's outputs with respect to its inputs (msm_mlp_vjp), and on top of it the bias
+// potential of a trained network (msm_bias_energy_forces).  The law: include/msmhip.h.
+//
+// One launch does both passes.  As in mlp.hip a workgroup is one wave that owns 16 frames whose rows sit in two LDS
+// images.  The forward pass is mlp_forward_kernel's instruction sequence (the outputs agree bit for bit) and leaves
+// per frame, in the workspace, what the adjoints need: z (the scaled inputs, when an input LayerNorm follows), u[l]
+// (the output of Linear l when a LayerNorm follows) and h[l] (the value the activation is applied to) -- the tape of
+// mlp_train.hip without a[l], which only parameter gradients read.  The backward pass of the same 16 frames follows at
+// once, so the tape comes back from L2: the adjoints of mlp_train_backward_kernel with dropout off, carried on past
+// the first Linear (dA_0 = du_0 . W_0), through the input LayerNorm, to dx = dZ / scale (the fp32 rounding of Z is
+// the identity for the derivative).
+//
+// The wave reads tape rows that other lanes of it wrote to global memory; WAVE_SYNC's wavefront-scope fence orders
+// them.  Nothing depends on the launch geometry: a frame's results are a function of that frame's inputs, bit for bit.
+#include "mlp_common.h"
+
+namespace {
+
+// where the tape lies in the workspace (offsets in doubles; -1: absent): [n, width] each; travels by value
+struct VjpLayout {
+    long long z;
+    long long h[kMlpMaxLinear], u[kMlpMaxLinear];
+    long long total;
+};
+
+VjpLayout vjp_layout(const MlpPlan& p, int64_t n) {
+    VjpLayout t;
+    long long off = 0;
+    auto take = [&](long long w) {
+        const long long at = off;
+        off += (long long)n * w;
+        return at;
+    };
+    t.z = p.ln_in_off >= 0 ? take(p.width[0]) : -1;
+    for (int l = 0; l < kMlpMaxLinear; ++l) t.h[l] = t.u[l] = -1;
+    for (int l = 0; l < p.n_linear; ++l) {
+        const bool last = l == p.n_linear - 1;
+        if (!last && p.ln_off[l] >= 0) t.u[l] = take(p.width[l + 1]);
+        if (!last || p.head_activation) t.h[l] = take(p.width[l + 1]);
+    }
+    t.total = std::max(off, 1LL);
+    return t;
+}
+
+template <typename T>
+__global__ __launch_bounds__(64, 2) void mlp_vjp_kernel(
+    const T* __restrict__ x, int64_t n, int64_t ld, const double* __restrict__ sc_mean,
+    const double* __restrict__ sc_scale, const float* __restrict__ params, MlpPlan p,
+    const double* __restrict__ gup, int64_t ldgo, double strength, double* __restrict__ energy,
+    double* __restrict__ out, int64_t ldo, double* __restrict__ gx, int64_t ldgx, VjpLayout lay, double* ws) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char mlp_smem[];
+    const int lane = threadIdx.x;
+    const int j = lane & 15, g = lane >> 4;
+    double* img[2];
+    img[0] = reinterpret_cast<double*>(mlp_smem);
+    img[1] = img[0] + 16 * p.stride[0];
+    const int F = p.width[0];
+    const int L = p.n_linear;
+    const int n_out = p.width[L];
+    const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+    const int64_t n_groups = (n + 15) / 16;
+    for (int64_t grp = blockIdx.x; grp < n_groups; grp += gridDim.x) {
+        const int64_t t0 = grp * 16;
+        const int rows = (int)min<int64_t>(16, n - t0);
+        const bool mine = j < rows;                               // frame j exists
+        const int64_t t = min<int64_t>(t0 + j, n - 1);            // reads of a frame past n are clamped, its writes dropped
+        WAVE_SYNC();   // the previous group's rows have been read
+        // ---- forward: mlp_forward_kernel, with the tape ----
+        const int S = p.stride[0];
+        for (int r = 0; r < 16; ++r)
+            for (int f = lane; f < F; f += 64) {
+                double z = 0.0;
+                if (r < rows) {
+                    z = (double)x[(t0 + r) * ld + f];
+                    if (sc_mean) z = (z - sc_mean[f]) / sc_scale[f];
+                    z = (double)(float)z;
+                }
+                img[0][r * S + f] = z;
+            }
+        WAVE_SYNC();
+        if (lay.z >= 0) save_rows(img[0], S, F, rows, ws + lay.z + (size_t)t0 * F, lane);
+        double* cur = img[0] + j * S;
+        double* nxt = img[1] + j * p.stride[1];
+        int bad = 0;                  // a non-finite Z anywhere in the frame: everything of the frame is NaN
+        for (int f = g; f < F; f += 4) bad |= !(fabs(cur[f]) <= DBL_MAX);
+        bad = xrow_reduce(bad, op_or{});
+        if (p.ln_in_off >= 0) mlp_layer_norm(cur, g, F, params + p.ln_in_off);
+        for (int l = 0; l < L; ++l) {
+            const int K = p.width[l], N = p.width[l + 1];
+            const int Sn = p.stride[(l + 1) & 1];
+            double* image = img[(l + 1) & 1];
+            WAVE_SYNC();   // the rows of `cur` are complete: every lane reads entries other lanes wrote
+            mlp_linear(cur, nxt, params + p.w_off[l], params + p.b_off[l], K, N, j, g);
+            const bool last = l == L - 1;
+            if (!last && p.ln_off[l] >= 0) {
+                WAVE_SYNC();
+                save_rows(image, Sn, N, rows, ws + lay.u[l] + (size_t)t0 * N, lane);
+                mlp_layer_norm(nxt, g, N, params + p.ln_off[l]);
+            }
+            if (!last || p.head_activation) {
+                WAVE_SYNC();
+                save_rows(image, Sn, N, rows, ws + lay.h[l] + (size_t)t0 * N, lane);
+                for (int f = g; f < N; f += 4) nxt[f] = mlp_activate(nxt[f], p.activation);
+            }
+            double* swap = cur;
+            cur = nxt;
+            nxt = swap;
+        }
+        // ---- outputs, energy, and the upstream gradient in place of the outputs ----
+        double e = 0.0;
+        for (int c = g; c < n_out; c += 4) e += cur[c] * cur[c];
+        e = xrow_reduce(e, op_sum{});
+        if (mine) {
+            if (out)
+                for (int c = g; c < n_out; c += 4) out[t * ldo + c] = bad ? qnan : cur[c];
+            if (energy && g == 0) energy[t] = bad ? qnan : strength * e;
+        }
+        for (int c = g; c < n_out; c += 4)
+            cur[c] = !mine ? 0.0 : (gup ? gup[t * ldgo + c] : 2.0 * strength * cur[c]);
+        // ---- backward: mlp_train_backward_kernel without dropout, on to the inputs ----
+        for (int l = L - 1; l >= 0; --l) {
+            const int K = p.width[l], N = p.width[l + 1];
+            double* gout = img[(l + 1) & 1] + j * p.stride[(l + 1) & 1];   // dE/d(output of layer l), then du_l
+            double* gin = img[l & 1] + j * p.stride[l & 1];                // dE/d(input of layer l)
+            const bool last = l == L - 1;
+            WAVE_SYNC();   // the tape rows are in place, and so are the entries of gout other lanes wrote
+            if (!last || p.head_activation) {
+                const double* h = ws + lay.h[l] + (size_t)t * N;
+                for (int f = g; f < N; f += 4) gout[f] = gout[f] * mlp_activate_grad(h[f], p.activation);
+            }
+            if (!last && p.ln_off[l] >= 0)
+                mlp_layer_norm_adjoint(gout, g, N, ws + lay.u[l] + (size_t)t * N, params + p.ln_off[l], nullptr, nullptr,
+                                       false);
+            WAVE_SYNC();
+            // dE/d(input) = du . W: entry (k, frame j) = sum_n W[n][k] du[frame j][n]
+            const float* __restrict__ W = params + p.w_off[l];
+            for (int k0 = 0; k0 < K; k0 += 16) {
+                const int kc = min(k0 + j, K - 1);
+                const v4f64 acc = mfma_tile_acc(
+                    N, g, k0 + j < K, true, [&](int nn) { return (double)W[(size_t)nn * K + kc]; },
+                    [&](int nn) { return gout[nn]; });
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int k = k0 + g + 4 * r;
+                    if (k < K) gin[k] = acc[r];
+                }
+            }
+        }
+        double* gin = img[0] + j * S;
+        if (p.ln_in_off >= 0) {
+            WAVE_SYNC();
+            mlp_layer_norm_adjoint(gin, g, F, ws + lay.z + (size_t)t * F, params + p.ln_in_off, nullptr, nullptr, false);
+        }
+        if (mine)
+            for (int f = g; f < F; f += 4) {
+                const double d = sc_scale ? gin[f] / sc_scale[f] : gin[f];
+                gx[t * ldgx + f] = bad ? qnan : d;
+            }
+    }
+}
+
+size_t feature_bytes(int64_t n, int F) { return (((size_t)n * F * sizeof(float)) + 15) & ~(size_t)15; }
+
+}  // namespace
+
+extern "C" {
+
+size_t msm_mlp_vjp_workspace(int64_t n, int n_linear, const int32_t* h_widths, int ln_in, int ln_hidden,
+                             int head_activation) {
+    if (!h_widths || n < 0 || n > ((int64_t)1 << 40)) return 0;
+    MlpPlan p;   // a refusal has nowhere to leave its message (no context): it is reported as 0
+    if (mlp_make_plan(nullptr, "msm_mlp_vjp_workspace", h_widths[0], n_linear, h_widths, 0, ln_in, ln_hidden,
+                      head_activation, kMlpAnyParams, &p))
+        return 0;
+    return (size_t)vjp_layout(p, n).total * sizeof(double);
+}
+
+msm_status msm_mlp_vjp(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n, int F, int64_t ld,
+                       const double* d_mean, const double* d_scale, int n_linear, const int32_t* h_widths,
+                       int activation, int ln_in, int ln_hidden, int head_activation, const float* d_params,
+                       size_t n_params, const double* d_gout, int64_t ldgo, double strength, double* d_energy,
+                       double* d_out, int64_t ldo, double* d_gx, int64_t ldgx, double* d_work, size_t work_bytes) {
+    if (!ctx) return MSM_ERR_INVALID;
+    MSM_REQUIRE(ctx, dtype == MSM_F32 || dtype == MSM_F64, "msm_mlp_vjp: bad dtype");
+    MlpPlan p;
+    if (msm_status st = mlp_make_plan(ctx, "msm_mlp_vjp", F, n_linear, h_widths, activation, ln_in, ln_hidden,
+                                      head_activation, n_params, &p))
+        return st;
+    const int n_out = p.width[n_linear];
+    MSM_REQUIRE(ctx, n >= 0 && ld >= F && ldgx >= F, "msm_mlp_vjp: bad shape (n = %lld, ld = %lld, ldgx = %lld)",
+                (long long)n, (long long)ld, (long long)ldgx);
+    MSM_REQUIRE(ctx, (!d_out || ldo >= n_out) && (!d_gout || ldgo >= n_out),
+                "msm_mlp_vjp: row stride %lld / %lld for %d outputs", (long long)ldo, (long long)ldgo, n_out);
+    MSM_REQUIRE(ctx, (d_mean == nullptr) == (d_scale == nullptr), "msm_mlp_vjp: scaler mean and scale go together");
+    if (n == 0) return MSM_OK;
+    MSM_REQUIRE(ctx, d_x && d_params && d_gx && d_work, "msm_mlp_vjp: NULL pointer");
+    const VjpLayout lay = vjp_layout(p, n);
+    MSM_REQUIRE(ctx, work_bytes >= (size_t)lay.total * sizeof(double), "msm_mlp_vjp: workspace of %zu bytes, %zu are needed",
+                work_bytes, (size_t)lay.total * sizeof(double));
+
+    const size_t lds = (size_t)16 * (p.stride[0] + p.stride[1]) * sizeof(double);   // <= 66 KiB
+    const int64_t n_groups = (n + 15) / 16;
+#define MSM_MLP_VJP(T)                                                                                               \
+    do {                                                                                                             \
+        if (lds > 48 * 1024)                                                                                         \
+            MSM_HIP(ctx, hipFuncSetAttribute((const void*)mlp_vjp_kernel<T>,                                         \
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                 \
+        int per_cu = 0;   /* one round of workgroups: as many as are resident at once */                             \
+        MSM_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mlp_vjp_kernel<T>, 64, lds));             \
+        const int grid = (int)std::min<int64_t>(n_groups, (int64_t)ctx->n_cu * std::max(per_cu, 1));                 \
+        hipLaunchKernelGGL(mlp_vjp_kernel<T>, dim3(grid), dim3(64), lds, ctx->stream, (const T*)d_x, n, ld, d_mean,  \
+                           d_scale, d_params, p, d_gout, ldgo, strength, d_energy, d_out, ldo, d_gx, ldgx, lay,      \
+                           d_work);                                                                                  \
+    } while (0)
+    if (dtype == MSM_F32) MSM_MLP_VJP(float);
+    else MSM_MLP_VJP(double);
+#undef MSM_MLP_VJP
+    MSM_CHECK_LAUNCH(ctx);
+    return MSM_OK;
+}
+
+size_t msm_bias_workspace(int64_t n, int F, int n_linear, const int32_t* h_widths, int ln_in, int ln_hidden,
+                          int head_activation) {
+    if (!h_widths || F != h_widths[0] || n < 0) return 0;
+    const size_t tape = msm_mlp_vjp_workspace(n, n_linear, h_widths, ln_in, ln_hidden, head_activation);
+    if (tape == 0) return 0;
+    return feature_bytes(n, F) + (size_t)n * F * sizeof(double) + tape;
+}
+
+msm_status msm_bias_energy_forces(msm_ctx* ctx, const float* d_xyz, int64_t n, int A, const float* d_box, int64_t n_box,
+                                  const int32_t* d_rec, const float* d_param, int n_rec, const int32_t* d_inc_ptr,
+                                  const int32_t* d_inc, int mic, const double* d_mean, const double* d_scale,
+                                  int n_linear, const int32_t* h_widths, int activation, int ln_in, int ln_hidden,
+                                  int head_activation, const float* d_params, size_t n_params, double strength,
+                                  double* d_work, size_t work_bytes, double* d_energy, double* d_cv, int64_t ldo,
+                                  double* d_force) {
+    if (!ctx) return MSM_ERR_INVALID;
+    const char* who = "msm_bias_energy_forces";
+    // everything the three steps would refuse is refused here, before the first of them launches
+    MSM_REQUIRE(ctx, h_widths, "%s: NULL widths", who);
+    const int F = h_widths[0];
+    MlpPlan p;
+    if (msm_status st = mlp_make_plan(ctx, who, F, n_linear, h_widths, activation, ln_in, ln_hidden, head_activation,
+                                      n_params, &p))
+        return st;
+    MSM_REQUIRE(ctx, n >= 0 && A >= 1 && n_rec >= 1, "%s: need n >= 0, A >= 1, at least one record", who);
+    MSM_REQUIRE(ctx, mic == MSM_MIC_ROUND || mic == MSM_MIC_SEARCH, "%s: mic must be MSM_MIC_ROUND or MSM_MIC_SEARCH, got %d",
+                who, mic);
+    MSM_REQUIRE(ctx, d_box ? (n_box == 1 || n_box == n) : n_box == 0,
+                "%s: n_box=%lld must be 1 or n=%lld with a box, 0 without", who, (long long)n_box, (long long)n);
+    MSM_REQUIRE(ctx, (d_mean == nullptr) == (d_scale == nullptr), "%s: scaler mean and scale go together", who);
+    MSM_REQUIRE(ctx, !d_cv || ldo >= p.width[n_linear], "%s: row stride %lld for %d outputs", who, (long long)ldo,
+                p.width[n_linear]);
+    if (n == 0) return MSM_OK;
+    MSM_REQUIRE(ctx, d_xyz && d_rec && d_param && d_inc_ptr && d_inc && d_params && d_work && d_energy && d_force,
+                "%s: NULL pointer", who);
+    MSM_REQUIRE(ctx, ((uintptr_t)d_rec & 15) == 0, "%s: the record table must be 16-byte aligned", who);
+    const size_t fbytes = feature_bytes(n, F), gbytes = (size_t)n * F * sizeof(double);
+    const size_t tape = (size_t)vjp_layout(p, n).total * sizeof(double);
+    MSM_REQUIRE(ctx, work_bytes >= fbytes + gbytes + tape, "%s: workspace of %zu bytes, %zu are needed", who, work_bytes,
+                fbytes + gbytes + tape);
+    float* feats = reinterpret_cast<float*>(d_work);
+    double* gfeat = reinterpret_cast<double*>(reinterpret_cast<unsigned char*>(d_work) + fbytes);
+    double* work = gfeat + (size_t)n * F;
+    if (msm_status st = featurize_spec_launch(ctx, d_xyz, n, A, d_box, n_box, d_rec, d_param, n_rec, F, mic, feats, F, 0,
+                                              true))
+        return st;
+    if (msm_status st = msm_mlp_vjp(ctx, feats, MSM_F32, n, F, F, d_mean, d_scale, n_linear, h_widths, activation, ln_in,
+                                    ln_hidden, head_activation, d_params, n_params, nullptr, 0, strength, d_energy, d_cv,
+                                    ldo, gfeat, F, work, tape))
+        return st;
+    return msm_featurize_spec_vjp(ctx, d_xyz, n, A, d_box, n_box, d_rec, d_param, n_rec, F, mic, gfeat, F, 0, d_inc_ptr,
+                                  d_inc, -1.0, d_force);
+}
+
+}  // extern "C"

@@ -17,7 +17,7 @@ import numpy as np
 from . import _lib
 from ._lib import check, lib
 
-__all__ = ["Engine", "DeviceArray", "FeatureTable", "get_engine", "segments_to_bounds"]
+__all__ = ["Engine", "DeviceArray", "FeatureTable", "build_incidence", "get_engine", "segments_to_bounds"]
 
 
 def _dtype_code(dtype: np.dtype) -> int:
@@ -145,16 +145,56 @@ class _Event:
 
 class FeatureTable:
     """The device-resident feature list of `msm_featurize_spec` (include/msmhip.h has the record layout): `rec` int32
-    [F, 8], `param` float32 [F], and what the host needs to know without reading them back."""
+    [F, 8], `param` float32 [F], and what the host needs to know without reading them back.  `incidence(A)` is the
+    atom -> (record, slot) incidence `msm_featurize_spec_vjp` walks, for frames of A atoms: built from the host copy
+    of the records and uploaded on the first call with that A, then kept."""
 
-    __slots__ = ("rec", "param", "width", "max_atom", "any_mic")
+    __slots__ = ("rec", "param", "width", "max_atom", "any_mic", "covers", "host_rec", "_inc")
 
-    def __init__(self, rec: DeviceArray, param: DeviceArray, width: int, max_atom: int, any_mic: bool):
+    def __init__(self, rec: DeviceArray, param: DeviceArray, width: int, max_atom: int, any_mic: bool,
+                 host_rec: np.ndarray | None = None):
         self.rec, self.param, self.width, self.max_atom, self.any_mic = rec, param, int(width), int(max_atom), any_mic
+        self.host_rec = host_rec
+        self._inc: dict[int, tuple[DeviceArray, DeviceArray]] = {}
+        # every column in [0, width) is written by a record: the table can feed a network of `width` inputs
+        self.covers = host_rec is not None and _written_columns(host_rec) == int(width)
 
     @property
     def n_features(self) -> int:
         return self.rec.shape[0]
+
+    def incidence(self, n_atoms: int) -> tuple[DeviceArray, DeviceArray]:
+        """(ptr int32 [A + 1], entries int32 [max(nnz, 1)]) on the device."""
+        n_atoms = int(n_atoms)
+        if n_atoms not in self._inc:
+            if self.host_rec is None:
+                raise ValueError("this FeatureTable was built without its host records: no incidence")
+            ptr, inc = build_incidence(self.host_rec, n_atoms)
+            eng = self.rec.engine
+            self._inc[n_atoms] = (eng.to_device(ptr), eng.to_device(inc if inc.size else np.zeros(1, np.int32)))
+        return self._inc[n_atoms]
+
+
+def _written_columns(rec: np.ndarray) -> int:
+    trig = (rec[:, 0] == _lib.FEAT_DIHEDRAL) & ((rec[:, 5] & _lib.FEAT_COSSIN) != 0)
+    return int(np.unique(np.concatenate([rec[:, 6], rec[trig, 7]])).size)
+
+
+def build_incidence(rec: np.ndarray, n_atoms: int) -> tuple[np.ndarray, np.ndarray]:
+    """The atom -> (record, slot) incidence of a record table in CSR form: (ptr int32 [A + 1], entries int32 [nnz]);
+    atom a's entries are entries[ptr[a]:ptr[a + 1]], each record * 4 + slot, in ascending order.  Contacts have no
+    gradient and are not listed; neither is an atom index outside [0, A) (the forward writes NaN for its record)."""
+    rec = np.asarray(rec)
+    arity = np.select([rec[:, 0] == _lib.FEAT_DISTANCE, rec[:, 0] == _lib.FEAT_ANGLE, rec[:, 0] == _lib.FEAT_DIHEDRAL],
+                      [2, 3, 4], 0)
+    slots = np.arange(4)[None, :]
+    listed = (slots < arity[:, None]) & (rec[:, 1:5] >= 0) & (rec[:, 1:5] < n_atoms)
+    f, s = np.nonzero(listed)
+    atom, code = rec[f, 1 + s].astype(np.int64), (4 * f + s).astype(np.int64)
+    order = np.lexsort((code, atom))
+    ptr = np.zeros(n_atoms + 1, np.int32)
+    ptr[1:] = np.cumsum(np.bincount(atom, minlength=n_atoms))
+    return ptr, code[order].astype(np.int32)
 
 
 def _records(kind: int, atoms, flags, params, cols, cols2=None) -> tuple[np.ndarray, np.ndarray]:
@@ -478,7 +518,7 @@ class Engine:
             rec, param, width = _table_from_indices(pairs, triplets, quads, int(dihedral_mode), contacts, float(rcut),
                                                     bool(periodic))
         return FeatureTable(self.to_device(rec), self.to_device(param), width, int(rec[:, 1:5].max(initial=-1)),
-                            bool((rec[:, 5] & _lib.FEAT_MIC).any()))
+                            bool((rec[:, 5] & _lib.FEAT_MIC).any()), host_rec=rec)
 
     def _box_arg(self, box, n: int):
         """(device box or None, n_box) from None, a host (3, 3) / (n, 3, 3) / (n_box, 9) array (checked: finite,
@@ -536,6 +576,146 @@ class Engine:
         if uploaded:
             self.sync()  # the uploaded table / box are freed on return
         return out
+
+    _MIC = {"round": _lib.MIC_ROUND, "search": _lib.MIC_SEARCH}
+
+    def featurize_spec_vjp(self, xyz: DeviceArray, table: FeatureTable, gfeat: DeviceArray, box=None,
+                           mic: str = "round", sign: float = 1.0, col0: int = 0,
+                           out: DeviceArray | None = None) -> DeviceArray:
+        """The adjoint of `featurize_spec` (msm_featurize_spec_vjp): float64 [n, A, 3] with
+        out[t, a] = sign * sum_f gfeat[t, col0 + col(f)] * d feature_f / d x_a, for the table, box and `mic` the forward
+        was run with.  gfeat: float64 [n, ld], ld >= col0 + table.width.  No upload beyond the table's incidence on its
+        first use and a host box; no host synchronisation otherwise."""
+        if xyz.dtype != np.float32 or len(xyz.shape) != 3 or xyz.shape[2] != 3:
+            raise ValueError("xyz must be float32 with shape (n_frames, n_atoms, 3)")
+        if mic not in self._MIC:
+            raise ValueError(f"mic must be 'round' or 'search', got {mic!r}")
+        if not isinstance(table, FeatureTable):
+            raise TypeError("featurize_spec_vjp needs a FeatureTable (Engine.feature_table)")
+        n, A, _ = xyz.shape
+        if table.max_atom >= A:
+            raise ValueError(f"atom index {table.max_atom} out of range [0, {A})")
+        if gfeat.dtype != np.float64 or len(gfeat.shape) != 2 or gfeat.shape[0] != n:
+            raise ValueError(f"gfeat must be float64 with shape ({n}, ld)")
+        if col0 < 0 or col0 + table.width > gfeat.shape[1]:
+            raise ValueError(f"gradient columns [{col0}, {col0 + table.width}) exceed the {gfeat.shape[1]} columns of gfeat")
+        dbox, n_box = self._box_arg(box, n)
+        uploaded = dbox is not None and dbox is not box
+        if not table.any_mic:
+            dbox, n_box = None, 0
+        out = out if out is not None else self.empty((n, A, 3), np.float64)
+        if out.dtype != np.float64 or out.size != n * A * 3:
+            raise ValueError(f"out must be float64 with shape ({n}, {A}, 3)")
+        ptr, inc = table.incidence(A)
+        check(lib.msm_featurize_spec_vjp(self.handle, xyz.ptr, n, A, dbox.ptr if dbox is not None else None, n_box,
+                                         table.rec.ptr, table.param.ptr, table.n_features, table.width, self._MIC[mic],
+                                         gfeat.ptr, gfeat.shape[1], int(col0), ptr.ptr, inc.ptr, float(sign), out.ptr),
+              self.handle)
+        if uploaded:
+            self.sync()  # the uploaded box is freed on return
+        return out
+
+    def _mlp_args(self, spec):
+        widths = np.ascontiguousarray(spec.widths, np.int32)
+        params, mean, scale = self._mlp_on_device(spec)
+        flags = (int(bool(spec.ln_in)), int(bool(spec.ln_hidden)), int(bool(spec.head_activation)))
+        return widths, params, mean, scale, flags
+
+    def mlp_vjp(self, x: DeviceArray, spec, gout: DeviceArray | None = None, strength: float = 1.0, *,
+                want_energy: bool = True, want_outputs: bool = True, ld: int | None = None,
+                work: DeviceArray | None = None) -> dict:
+        """Forward pass of the network `spec` and its vector-Jacobian product with respect to the inputs x [n, F]
+        (msm_mlp_vjp): `gx` float64 [n, F] = dE/dx, where dE/dy is `gout` (float64 [n, >= n_out]) or, without it,
+        2 strength y, the gradient of E = strength sum y^2.  Also `energy` [n] (that E) and `outputs` [n, n_out],
+        bit-identical to `mlp_forward`, and `work`, the workspace, to hand back through ``work``."""
+        n, F = x.shape
+        widths, params, mean, scale, flags = self._mlp_args(spec)
+        n_linear, d = len(widths) - 1, int(widths[-1])
+        if gout is not None and (gout.dtype != np.float64 or len(gout.shape) != 2 or gout.shape[0] != n):
+            raise ValueError(f"gout must be float64 with shape ({n}, ld)")
+        need = int(lib.msm_mlp_vjp_workspace(n, n_linear, widths.ctypes.data, *flags))
+        if work is None or work.nbytes < max(need, 8):
+            work = self.empty((max(need, 8) // 8,), np.float64)
+        energy = self.empty((n,), np.float64) if want_energy else None
+        out = self.empty((n, d), np.float64) if want_outputs else None
+        gx = self.empty((n, F), np.float64)
+        check(lib.msm_mlp_vjp(self.handle, x.ptr, _dtype_code(x.dtype), n, F, int(F if ld is None else ld),
+                              mean.ptr if mean is not None else None, scale.ptr if scale is not None else None,
+                              n_linear, widths.ctypes.data, int(spec.activation), *flags, params.ptr, params.size,
+                              gout.ptr if gout is not None else None, gout.shape[1] if gout is not None else 0,
+                              float(strength), energy.ptr if want_energy else None,
+                              out.ptr if want_outputs else None, d, gx.ptr, F, work.ptr, work.nbytes), self.handle)
+        res = {"gx": gx, "work": work}
+        if want_energy:
+            res["energy"] = energy
+        if want_outputs:
+            res["outputs"] = out
+        return res
+
+    BIAS_WORK_BUDGET = 256 << 20     # bytes of workspace one msm_bias_energy_forces call may use
+
+    def bias_energy_forces(self, xyz: DeviceArray, table: FeatureTable, spec, strength: float, box=None,
+                           mic: str = "round", *, want_cv: bool = True, energy: DeviceArray | None = None,
+                           cv: DeviceArray | None = None, force: DeviceArray | None = None,
+                           work: DeviceArray | None = None, chunk: int | None = None) -> dict:
+        """Bias energy, collective variables and forces of the frames xyz float32 [n, A, 3]
+        (msm_bias_energy_forces): `energy` float64 [n] = strength sum cv^2, `cv` float64 [n, n_out] (the raw outputs
+        of the network `spec`), `force` float64 [n, A, 3] = -dE/dx, all on the device.  `table`: the FeatureTable whose
+        columns are the network's inputs; `box`: None, one box or one per frame (a device box is used as it is).
+        The workspace of a call grows with n (features, their gradient, the network's tape: msm_bias_workspace), so n
+        is cut into chunks of frames whose workspace stays under BIAS_WORK_BUDGET = 256 MiB -- about 380 000 frames
+        for a 23 -> 32 -> 16 -> 3 network without LayerNorms, 210 000 with both -- each chunk three launches; `chunk` overrides the chunk length.  With device-resident
+        inputs and preallocated `energy`, `cv`, `force`, `work` nothing is allocated, uploaded or waited for:
+        the form an MD step, or a graph capture, uses."""
+        if xyz.dtype != np.float32 or len(xyz.shape) != 3 or xyz.shape[2] != 3:
+            raise ValueError("xyz must be float32 with shape (n_frames, n_atoms, 3)")
+        if mic not in self._MIC:
+            raise ValueError(f"mic must be 'round' or 'search', got {mic!r}")
+        if not isinstance(table, FeatureTable):
+            raise TypeError("bias_energy_forces needs a FeatureTable (Engine.feature_table)")
+        n, A, _ = xyz.shape
+        if table.max_atom >= A:
+            raise RuntimeError(f"expected at least {table.max_atom + 1} atoms, received {A}")
+        widths, params, mean, scale, flags = self._mlp_args(spec)
+        n_linear, F, d = len(widths) - 1, int(widths[0]), int(widths[-1])
+        if table.width != F or not table.covers:
+            raise RuntimeError(f"feature extractor returned {table.width} features but scaler expects {F}"
+                               if table.width != F else "a column of the feature table is written by no record")
+        dbox, n_box = self._box_arg(box, n)
+        uploaded = dbox is not None and dbox is not box
+        if not table.any_mic:
+            dbox, n_box = None, 0
+        per_frame = int(lib.msm_bias_workspace(1, F, n_linear, widths.ctypes.data, *flags))
+        if per_frame == 0:
+            spec.check_envelope()
+            raise NotImplementedError("the network lies outside msm_mlp_forward's envelope")
+        step = max(1, int(chunk) if chunk else self.BIAS_WORK_BUDGET // (per_frame + 16))
+        step = min(step, max(n, 1))
+        need = int(lib.msm_bias_workspace(step, F, n_linear, widths.ctypes.data, *flags))
+        if work is None or work.nbytes < need:
+            work = self.empty((need // 8 + 1,), np.float64)
+        energy = energy if energy is not None else self.empty((n,), np.float64)
+        cv = cv if cv is not None else (self.empty((n, d), np.float64) if want_cv else None)
+        force = force if force is not None else self.empty((n, A, 3), np.float64)
+        if energy.dtype != np.float64 or energy.size != n or force.dtype != np.float64 or force.size != n * A * 3:
+            raise ValueError(f"energy must be float64 [{n}], force float64 [{n}, {A}, 3]")
+        if cv is not None and (cv.dtype != np.float64 or len(cv.shape) != 2 or cv.shape[0] != n or cv.shape[1] < d):
+            raise ValueError(f"cv must be float64 with shape ({n}, >= {d})")
+        ptr, inc = table.incidence(A)
+        ldo = cv.shape[1] if cv is not None else d
+        for t0 in range(0, n, step):
+            m = min(step, n - t0)
+            bptr = None if dbox is None else dbox.ptr + (0 if n_box == 1 else t0 * 36)
+            check(lib.msm_bias_energy_forces(
+                self.handle, xyz.ptr + t0 * A * 12, m, A, bptr, 0 if dbox is None else (1 if n_box == 1 else m),
+                table.rec.ptr, table.param.ptr, table.n_features, ptr.ptr, inc.ptr, self._MIC[mic],
+                mean.ptr if mean is not None else None, scale.ptr if scale is not None else None, n_linear,
+                widths.ctypes.data, int(spec.activation), *flags, params.ptr, params.size, float(strength), work.ptr,
+                work.nbytes, energy.ptr + t0 * 8, cv.ptr + t0 * ldo * 8 if cv is not None else None, ldo,
+                force.ptr + t0 * A * 24), self.handle)
+        if uploaded:
+            self.sync()  # the uploaded box is freed on return
+        return {"energy": energy, "cv": cv, "force": force, "work": work}
 
     def _superpose_args(self, xyz: DeviceArray, sel, ref):
         if xyz.dtype != np.float32 or len(xyz.shape) != 3 or xyz.shape[2] != 3:
