@@ -1144,6 +1144,49 @@ msm_status msm_reactive_pathways_begin(msm_ctx* ctx, const double* d_net, int64_
 msm_status msm_reactive_pathways_run(msm_ctx* ctx, void* d_work, int n, double fraction, int maxiter, int keep,
                                      int launch_paths, double* d_caps, int32_t* d_paths, int32_t* d_len);
 
+/* ---- effective count matrix (csrc/effective.hip) ---------------------------------------------------
+ * count_mode = "effective" of the reference's counting backend (deeptime 0.4.5 TransitionCountEstimator;
+ * deeptime.markov.tools.estimation.effective_count_matrix / statistical_inefficiencies, after Noe 2015), written
+ * from the documented algorithm.  Parity with deeptime's own output is NOT pinned; the tests hold the kernels to a
+ * numpy / Python restatement of the rule below (tests/_effective_ref.py).
+ *
+ * d_labels int32 [n], n < 2^31.  Segments [start, stop) on the host: ascending, disjoint, inside [0, n], else
+ * MSM_ERR_INVALID (n_seg = 0: one segment [0, n)); every segment is one trajectory.  A start frame is a frame t of
+ * a segment with t + lag < stop and labels[t], labels[t + lag] in [0, k).  C (d_counts, int64 [k, k]) is
+ * msm_count_transitions over the same segments with stride 1.
+ * Row i: per segment the time-ordered targets labels[t + lag] of its start frames with labels[t] == i, one
+ * sub-sequence each (a segment without such a frame gives none).  N_i = sum of their lengths (the row sum of C),
+ * M_i = the longest.  For a cell c = C_ij > 0, x = (target == j) along row i, and for l = 0 .. M_i - 1, summed
+ * over the sub-sequences of length Nx:
+ *     n_l = sum max(Nx - l, 0),  S_l = sum_p x_p x_(p+l),  A_l = sum_(p < Nx - l) x_p,  B_l = sum_(p >= l) x_p,
+ *     Q_l = S_l N_i^2 - c N_i (A_l + B_l) + c^2 n_l          (exact, 128-bit integers)
+ * The truncation lag l* is the first l with Q_l <= 0, decided on the integer (deeptime compares a float), M_i
+ * when there is none.  corrsum = sum_(l = 1 .. l* - 1) Q_l (M_i - l) / (N_i^2 n_l M_i), in fp64 in ascending l;
+ * si_ij = 1 / (1 + 2 mact corrsum N_i / c).  A row with a single target has Q_0 = 0: l* = 0 and si = 1.
+ * average: ROW  Ceff_ij = w_i C_ij with w_i = sum_j C_ij si_ij / N_i (deeptime's estimator, mact = 1);
+ *          ALL  one weight sum C si / sum C;   NONE  Ceff = C o si.
+ * Outputs, all OVERWRITTEN: d_ceff f64 [k, k], d_si f64 [k, k] (0 where C = 0), d_counts int64 [k, k], d_trunc
+ * int32 [k, k] = l* (0 where C = 0).
+ *
+ * One workgroup per cell walks the lags in blocks of MSM_EFF_LAG_BLOCK with integer LDS histograms; a launch
+ * advances every unfinished cell by at most blocks_per_launch blocks (0: MSM_EFF_BLOCKS_PER_LAUNCH), writes the
+ * cell's state {corrsum, next lag, done} back to d_work and counts the cells it left unfinished; the host reads
+ * that count and launches again until it is zero (not capturable).  An autocorrelation that never decays costs
+ * O(c^2) pair visits by definition: they arrive as many bounded launches.  The cut between launches changes no
+ * operation: the same bytes for every blocks_per_launch and on every run.  *h_launches (may be NULL): how many
+ * such launches ran.  d_work: msm_effective_counts_work_bytes(n, k, n_seg) bytes; the grouping also uses the
+ * context scratch (msm_group_by_label). */
+#define MSM_EFF_LAG_BLOCK 256
+#define MSM_EFF_BLOCKS_PER_LAUNCH 8
+#define MSM_EFF_AVERAGE_ROW 0
+#define MSM_EFF_AVERAGE_ALL 1
+#define MSM_EFF_AVERAGE_NONE 2
+size_t msm_effective_counts_work_bytes(int64_t n, int k, int n_seg);
+msm_status msm_effective_counts(msm_ctx* ctx, const int32_t* d_labels, int64_t n, const int64_t* h_seg_start,
+                                const int64_t* h_seg_stop, int n_seg, int lag, int k, int average, double mact,
+                                int blocks_per_launch, void* d_work, size_t work_bytes, double* d_ceff, double* d_si,
+                                int64_t* d_counts, int32_t* d_trunc, int64_t* h_launches);
+
 /* ---- trajectory bootstrap in batch (csrc/bootstrap.hip) ----------------------------------------
  * The device side of UncertaintyQuantifier (S/conformations/uncertainty.py:31-261): every bootstrap sample
  * resamples whole trajectories with replacement and rebuilds the MSM (_rebuild_msm, :506-530).  Counts are

@@ -35,6 +35,9 @@ COMBINE_MAX_SEG, FLUX_LDS_MAX_N = 32, 127
 # reactive pathways (MSM_PATHWAYS_* in include/msmhip.h): most states, the status words of the resumable entry
 PATHWAYS_MAX_N = 2048
 PATHWAYS_RUNNING, PATHWAYS_FRACTION, PATHWAYS_NO_PATH, PATHWAYS_MAXITER = range(4)
+# effective counts (MSM_EFF_* in include/msmhip.h): lags of a block, blocks a launch takes by default, averages
+EFF_LAG_BLOCK, EFF_BLOCKS_PER_LAUNCH = 256, 8
+EFF_AVERAGE_ROW, EFF_AVERAGE_ALL, EFF_AVERAGE_NONE = range(3)
 # msm_mlp_forward's envelope: widest layer, most outputs, most Linear layers
 MLP_MAX_WIDTH, MLP_MAX_OUT, MLP_MAX_LINEAR = 256, 64, 8
 # msm_vamp2_loss's stats block (MSM_VAMP2_STATS): 16 scalars, then var_z0, var_zt, mean_z0, mean_zt of 64 entries
@@ -204,6 +207,9 @@ _PROTOTYPES: dict[str, tuple] = {
     "msm_reactive_pathways_launch_paths": (_i32, [_i32]),
     "msm_reactive_pathways_begin": (_i32, [_vp, _vp, _i64, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "msm_reactive_pathways_run": (_i32, [_vp, _vp, _i32, _f64, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "msm_effective_counts_work_bytes": (_sz, [_i64, _i32, _i32]),
+    "msm_effective_counts": (_i32, [_vp, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _f64, _i32, _vp, _sz, _vp, _vp, _vp,
+                                    _vp, C.POINTER(_i64)]),
     "msm_combine_counts": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _i64, _vp, _i32]),
     "msm_row_normalise_batched": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp]),
     "msm_reactive_flux_batched_scratch_bytes": (_sz, [_i32, _i32, _i32]),

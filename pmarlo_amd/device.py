@@ -829,6 +829,39 @@ class Engine:
                                                 int(k), out.ptr, pairs.ptr), self.handle)
         return out, pairs
 
+    def effective_counts(self, labels: DeviceArray, k: int, lag: int, *, starts=None, stops=None, average: str = "row",
+                         mact: float = 1.0, blocks_per_launch: int | None = None):
+        """Effective count matrix at `lag` (msm_effective_counts, include/msmhip.h) -> (Ceff f64 [k, k], statistical
+        inefficiencies f64 [k, k] (0 where C = 0), sliding counts C int64 [k, k], truncation lags int32 [k, k]).
+        Segments must be ascending and disjoint; every segment is one trajectory.  average: "row" (deeptime's
+        estimator), "all" or "none".  blocks_per_launch: lag blocks of EFF_LAG_BLOCK lags a launch may advance a cell
+        by (None: the library's default); the result does not depend on it.  The number of inefficiency launches of
+        the last call is kept in `last_effective_launches`."""
+        import ctypes
+
+        modes = {"row": _lib.EFF_AVERAGE_ROW, "all": _lib.EFF_AVERAGE_ALL, "none": _lib.EFF_AVERAGE_NONE}
+        if average not in modes:
+            raise ValueError(f"average must be one of {sorted(modes)}, got {average!r}")
+        if labels.dtype != np.int32:
+            raise TypeError("labels must be int32")
+        n, k = labels.size, int(k)
+        if k < 1:
+            raise ValueError(f"k must be >= 1 (got {k})")
+        if starts is None:
+            starts, stops = segments_to_bounds(None, n)
+        starts, stops = self._seg_ptrs(starts, stops)
+        ceff, si = self.empty((k, k), np.float64), self.empty((k, k), np.float64)
+        counts, trunc = self.empty((k, k), np.int64), self.empty((k, k), np.int32)
+        work = self.empty((max(int(lib.msm_effective_counts_work_bytes(n, k, len(starts))), 1),), np.uint8)
+        launches = ctypes.c_int64(0)
+        check(lib.msm_effective_counts(self.handle, labels.ptr, n, starts.ctypes.data, stops.ctypes.data, len(starts),
+                                       int(lag), k, modes[average], float(mact),
+                                       0 if blocks_per_launch is None else int(blocks_per_launch), work.ptr, work.nbytes,
+                                       ceff.ptr, si.ptr, counts.ptr, trunc.ptr, ctypes.byref(launches)), self.handle)
+        self.sync()  # the workspace is freed on return
+        self.last_effective_launches = int(launches.value)
+        return ceff, si, counts, trunc
+
     def state_counts(self, labels: DeviceArray, k: int, out: DeviceArray | None = None) -> DeviceArray:
         out = out if out is not None else self.empty((k,), np.int64)
         check(lib.msm_state_counts(self.handle, labels.ptr, labels.size, int(k), out.ptr), self.handle)

@@ -2,7 +2,8 @@
 from .ck import CKRunResult, run_ck  # noqa: F401
 from .clustering import ClusteringResult, cluster_microstates  # noqa: F401
 from .estimation import (build_msm, build_simple_msm, check_transition_matrix, compute_free_energies, count_transitions,  # noqa: F401
-                         ensure_connected_counts, finalize_transition_and_stationary, fit_reversible_msm)
+                         effective_count_matrix, ensure_connected_counts, finalize_transition_and_stationary,
+                         fit_reversible_msm, statistical_inefficiencies)
 from .features import MSMFeatures, ca_distance_pairs, compute_msm_features  # noqa: F401
 from .its import (  # noqa: F401
     DEFAULT_ITS_LAGS,
@@ -11,6 +12,7 @@ from .its import (  # noqa: F401
     detect_timescale_plateau,
     deterministic_its_from_counts,
     safe_timescales,
+    sample_bayesian_timescales,
     select_lag_from_its,
 )
 from .pcca import canonicalize_macro_labels, pcca_like_macrostates, pcca_memberships  # noqa: F401

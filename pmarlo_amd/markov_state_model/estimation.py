@@ -1,6 +1,12 @@
 """MSM estimation hooks: mirror of EstimationMixin (S/markov_state_model/_estimation.py:
 116-156 _count_transitions_deeptime, :158-188 _finalize_transition_and_stationary,
-:211-220 _compute_free_energies) and ensure_connected_counts (S/utils/msm_utils.py:129-167)."""
+:211-220 _compute_free_energies) and ensure_connected_counts (S/utils/msm_utils.py:129-167).
+
+Every count mode of the reference's counting backend is offered.  The effective count matrix (Noe 2015) is
+computed on the device (Engine.effective_counts, csrc/effective.hip) from deeptime 0.4.5's documented algorithm, with
+the truncation of every autocorrelation decided in exact integer arithmetic where deeptime compares a float.
+deeptime is not available here: parity with its own output is NOT pinned; the kernels are held to a numpy / Python
+restatement of the contract in include/msmhip.h (tests/_effective_ref.py)."""
 
 from __future__ import annotations
 
@@ -12,7 +18,7 @@ from ..device import get_engine
 from .results import ConnectedCountResult, MSMEstimate
 
 __all__ = ["count_transitions", "ensure_connected_counts", "finalize_transition_and_stationary", "build_msm",
-           "compute_free_energies"]
+           "compute_free_energies", "effective_count_matrix", "statistical_inefficiencies"]
 
 NUMERIC_MIN_POSITIVE = 1e-12
 NUMERIC_DIRICHLET_ALPHA = 1e-3
@@ -41,18 +47,75 @@ def _concat_dtrajs(dtrajs: Sequence[np.ndarray], n_states: int):
     return labels, segs
 
 
-def count_transitions(dtrajs: Sequence[np.ndarray], n_states: int, *, lag: int, count_mode: str = "sliding") -> np.ndarray:
-    """(n, n) float64 sliding-window counts; ``"strided"`` is mapped to sliding as the reference does (:152)."""
-    if count_mode not in ("sliding", "strided"):
-        raise ValueError(f"unsupported count_mode {count_mode!r} on the accelerated path")
+COUNT_MODES = ("sliding", "strided", "sample", "sliding-effective", "effective")
+
+
+def _device_segments(dtrajs: Sequence[np.ndarray], n_states: int):
     labels, segs = _concat_dtrajs(dtrajs, n_states)
-    if labels.size == 0 or not segs:
-        return np.zeros((n_states, n_states), dtype=float)
-    eng = get_engine()
     starts = np.asarray([s for s, _ in segs], np.int64)
     stops = np.asarray([e for _, e in segs], np.int64)
-    counts, _ = eng.count_transitions(eng.to_device(labels), n_states, int(max(1, lag)), starts=starts, stops=stops)
-    return counts.to_host().astype(float)
+    return labels, starts, stops
+
+
+def count_transitions(dtrajs: Sequence[np.ndarray], n_states: int, *, lag: int, count_mode: str = "sliding") -> np.ndarray:
+    """(n, n) float64 counts at `lag`.  ``"sliding"``: every pair (t, t + lag); ``"strided"`` is mapped to sliding as
+    the reference does (:152); ``"sample"``: the pairs at t = 0, lag, 2 lag, .. of every trajectory;
+    ``"sliding-effective"``: sliding / lag (deeptime's definition); ``"effective"``: the sliding counts scaled row by
+    row by the statistical inefficiency of their transitions (effective_count_matrix, average = "row", mact = 1)."""
+    if count_mode not in COUNT_MODES:
+        raise ValueError(f"unsupported count_mode {count_mode!r} on the accelerated path")
+    labels, starts, stops = _device_segments(dtrajs, n_states)
+    if labels.size == 0 or starts.size == 0:
+        return np.zeros((n_states, n_states), dtype=float)
+    eng = get_engine()
+    lag = int(max(1, lag))
+    if count_mode == "effective":
+        return eng.effective_counts(eng.to_device(labels), n_states, lag, starts=starts, stops=stops)[0].to_host()
+    counts, _ = eng.count_transitions(eng.to_device(labels), n_states, lag, starts=starts, stops=stops,
+                                      stride=lag if count_mode == "sample" else 1)
+    counts = counts.to_host().astype(float)
+    return counts / float(lag) if count_mode == "sliding-effective" else counts
+
+
+def _infer_states(dtrajs: Sequence[np.ndarray], n_states: int | None) -> int:
+    if n_states is not None:
+        return int(n_states)
+    return max((int(np.max(d)) for d in dtrajs if len(d)), default=-1) + 1
+
+
+def _effective(dtrajs, lag, average, mact, n_states):
+    if isinstance(dtrajs, np.ndarray) and dtrajs.ndim == 1:
+        dtrajs = [dtrajs]
+    k = _infer_states(dtrajs, n_states)
+    if k < 1:
+        return np.zeros((0, 0)), np.zeros((0, 0))
+    if int(lag) < 1:
+        raise ValueError("lag must be >= 1")
+    labels, starts, stops = _device_segments(dtrajs, k)
+    if labels.size == 0 or starts.size == 0:
+        return np.zeros((k, k)), np.zeros((k, k))
+    eng = get_engine()
+    ceff, si, _, _ = eng.effective_counts(eng.to_device(labels), k, int(lag), starts=starts, stops=stops,
+                                          average=average, mact=mact)
+    return ceff.to_host(), si.to_host()
+
+
+def effective_count_matrix(dtrajs: Sequence[np.ndarray], lag: int, average: str = "row", mact: float = 1.0,
+                           n_states: int | None = None) -> np.ndarray:
+    """Effective count matrix at `lag`, dense float64 [n_states, n_states] (deeptime.markov.tools.estimation
+    .effective_count_matrix, after Noe 2015): the sliding counts times the statistical inefficiencies of their
+    transitions, averaged per row (``"row"``), over the whole matrix (``"all"``) or not at all (``"none"``).
+    Labels outside [0, n_states) cut a trajectory.  Computed on the device from the documented algorithm
+    (Engine.effective_counts); agreement with deeptime's own numbers is not pinned.  The autocorrelation is always
+    truncated at its first non-positive lag (deeptime's truncate_acf=True)."""
+    return _effective(dtrajs, lag, average, mact, n_states)[0]
+
+
+def statistical_inefficiencies(dtrajs: Sequence[np.ndarray], lag: int, mact: float = 1.0,
+                               n_states: int | None = None) -> np.ndarray:
+    """Statistical inefficiency of every observed transition at `lag`, dense float64 [n_states, n_states], 0 where
+    the transition was not seen (deeptime.markov.tools.estimation.statistical_inefficiencies)."""
+    return _effective(dtrajs, lag, "none", mact, n_states)[1]
 
 
 def ensure_connected_counts(C: np.ndarray, alpha: float = NUMERIC_DIRICHLET_ALPHA,

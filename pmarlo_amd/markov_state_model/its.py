@@ -29,7 +29,7 @@ from .results import ITSResult
 logger = logging.getLogger("pmarlo")
 
 __all__ = ["format_lag_window_ps", "safe_timescales", "compute_implied_timescales", "deterministic_its_from_counts", "detect_timescale_plateau",
-           "select_lag_from_its",
+           "select_lag_from_its", "sample_bayesian_timescales",
            "candidate_lag_ladder", "DEFAULT_ITS_LAGS"]
 
 EPS = 1e-12
@@ -220,7 +220,7 @@ def compute_implied_timescales(dtrajs: Sequence[np.ndarray], n_states: int, lag_
                                plateau_epsilon: float = 0.1, time_per_frame_ps: float | None = None,
                                random_state: int | None = None, return_samples: bool = False,
                                effective_frames: int | None = None, reversible: bool = False,
-                               n_sweeps: int | None = None) -> ITSResult:
+                               n_sweeps: int | None = None, count_mode: str = "sliding") -> ITSResult:
     """Lag scan on the device (ITSMixin.compute_implied_timescales, S/markov_state_model/_its.py:137-192):
     batched counts for all lags, one packed transition matrix per lag, n_samples posterior matrices
     per lag, one batched spectrum solve over lags x samples, median / percentile band on the host.
@@ -237,7 +237,13 @@ def compute_implied_timescales(dtrajs: Sequence[np.ndarray], n_states: int, lag_
     maximum-likelihood estimate, and summarised as above; n_samples <= 1 is the deterministic spectrum of that
     estimate.  deeptime is not available, so parity with its sampler stays unpinned: what is tested is the law the
     samples are drawn from (closed-form Beta marginals, a numpy chain, detailed balance of every sample; DESIGN.md
-    section 7)."""
+    section 7).
+    count_mode="effective": every lag's estimate and posterior take that lag's effective counts
+    (Engine.effective_counts, average "row", mact 1) in place of the sliding counts, in both branches and for
+    n_samples <= 1 too.  Sliding counts at lag tau overstate the number of independent observations, so their bands
+    are too narrow; sampling with them logs the reference's warning (:296-305).  "sliding" stays the default."""
+    if count_mode not in ("sliding", "strided", "effective"):
+        raise ValueError(f"unsupported count_mode {count_mode!r} for implied timescales")
     n = int(n_timescales)
     empty = ITSResult(lag_times=np.array([], dtype=int), eigenvalues=np.empty((0, n)),
                       eigenvalues_ci=np.empty((0, n, 2)), timescales=np.empty((0, n)),
@@ -264,15 +270,26 @@ def compute_implied_timescales(dtrajs: Sequence[np.ndarray], n_states: int, lag_
     S = int(n_samples) if int(n_samples) > 1 else 0
     starts = np.asarray([s for s, _ in segs], np.int64)
     stops = np.asarray([e for _, e in segs], np.int64)
-    counts, _ = eng.count_transitions_lagscan(eng.to_device(labels), k, lags, starts=starts, stops=stops)
+    from .._lib import check, lib
+
+    if S and count_mode != "effective":
+        logger.warning("Bayesian MSM confidence sampling expects effective counts; continuing with count_mode='%s' "
+                       "may yield correlated samples", count_mode)
+    if count_mode == "effective":
+        d_labels = eng.to_device(labels)
+        counts = eng.empty((L, k, k), np.float64)
+        for i, lag in enumerate(lags):
+            ceff = eng.effective_counts(d_labels, k, lag, starts=starts, stops=stops)[0]
+            check(lib.msm_memcpy_d2d(eng.handle, counts.ptr + i * k * k * 8, ceff.ptr, k * k * 8), eng.handle)
+    else:
+        counts, _ = eng.count_transitions_lagscan(eng.to_device(labels), k, lags, starts=starts, stops=stops)
+    f64 = int(counts.dtype == np.float64)
     Tb = eng.empty((L, k, k), np.float64)
     nb = eng.empty((L,), np.int32)
     act = eng.empty((L, k), np.int32)
-    from .._lib import check, lib
-
     rows, inv = eng.empty((k,), np.float64), eng.empty((k,), np.int32)
     for i in range(L):  # per-lag active set + alpha, packed in place (device to device)
-        check(lib.msm_transition_matrix(eng.handle, counts.ptr + i * k * k * 8, 0, k, 1, float(dirichlet_alpha), 1e-12,
+        check(lib.msm_transition_matrix(eng.handle, counts.ptr + i * k * k * 8, f64, k, 1, float(dirichlet_alpha), 1e-12,
                                         Tb.ptr + i * k * k * 8, act.ptr + i * k * 4, inv.ptr, nb.ptr + 4 * i, rows.ptr,
                                         None), eng.handle)
     rev_counts = None
@@ -349,3 +366,46 @@ def compute_implied_timescales(dtrajs: Sequence[np.ndarray], n_states: int, lag_
     if return_samples:
         res.samples = samples                                       # engine extra: the per-sample spectra
     return res
+
+
+def sample_bayesian_timescales(dtrajs: Sequence[np.ndarray], n_states: int, lag_time: int, n_samples: int = 200,
+                               count_mode: str = "effective", *, dirichlet_alpha: float = 1e-3,
+                               random_state: int | None = None, n_sweeps: int | None = None) -> dict | None:
+    """Timescales and populations of n_samples reversible posterior matrices at one lag
+    (ITSMixin.sample_bayesian_timescales, S/markov_state_model/_its.py:670-740; effective counts by default).
+
+    The counts of `count_mode` at `lag_time` are reduced to the engine's regularised active set,
+    ensure_connected_counts(C, alpha=dirichlet_alpha), and sample_reversible_transition_matrices(want_pi=True)
+    draws the matrices with their stationary vectors.  deeptime's BayesianMSM instead restricts the counts to their
+    largest connected set and adds no prior; parity with its sampler is not pinned.  Per sample the device spectrum
+    gives up to five timescales (the eigenvalues after the first); the finite ones are kept in order and padded with
+    NaN to the longest row, as the reference pads them (:720-740).
+    Returns {"timescales_samples": [n_kept, <= 5], "population_samples": [n_samples, n_active]} (a key is absent
+    when nothing was collected for it), or None when there are no counts at all."""
+    from .estimation import count_transitions, ensure_connected_counts
+
+    lag = int(max(1, lag_time))
+    S = int(max(1, n_samples))
+    C = count_transitions(dtrajs, int(n_states), lag=lag, count_mode=count_mode)
+    res = ensure_connected_counts(C, alpha=float(dirichlet_alpha))
+    na = res.counts.shape[0]
+    if na == 0:
+        return None
+    eng = get_engine()
+    seed = 0 if random_state is None else int(random_state)
+    T, pi = eng.sample_reversible_transition_matrices(eng.to_device(np.ascontiguousarray(res.counts)), seed=seed,
+                                                      n_samples=S, n_sweeps=n_sweeps, want_pi=True)
+    out: dict = {"population_samples": pi.to_host().reshape(S, na)}
+    want = min(5, na - 1)
+    if want > 0:
+        nrep = eng.to_device(np.full(S, na, np.int32))
+        spec = eng.spectrum(T, n=nrep, n_its=want, lags=np.full(S, float(lag)), want_pi=False, allow_unconverged=True,
+                            p=32)
+        ts = np.asarray(spec["its_ts"], dtype=float).reshape(S, want)
+        kept = [row[np.isfinite(row)] for row in ts]
+        kept = [row for row in kept if row.size]
+        if kept:
+            width = max(row.shape[0] for row in kept)
+            out["timescales_samples"] = np.vstack([np.pad(row, (0, width - row.shape[0]), constant_values=np.nan)
+                                                   for row in kept])
+    return out
