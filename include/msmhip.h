@@ -536,9 +536,9 @@ msm_status msm_mlp_forward(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64
 
 /* ---- DeepTICA training: one step of the reference's curriculum trainer (S/ml/deeptica/trainer.py:1020-1070) ----
  *
- * VAMP-2 loss of VAMP2Loss.forward (S/features/deeptica/losses.py) with uniform weights 1/m, the only case the
- * trainer uses, and its closed-form gradient with respect to the outputs.  d_y0, d_yt [m, ld] f64: the network's
- * outputs at the t and the tau frames, n_out <= 64 columns each.
+ * VAMP-2 loss of VAMP2Loss.forward (S/features/deeptica/losses.py) with uniform weights 1/m, the case the reference's
+ * trainer uses (per-pair weights: msm_vamp2_loss_weighted below), and its closed-form gradient with respect to the
+ * outputs.  d_y0, d_yt [m, ld] f64: the network's outputs at the t and the tau frames, n_out <= 64 columns each.
  *   C00, Ctt, C0t: centred covariances of the outputs, correction 0;
  *   A = sym((1 - alpha) C00 + (alpha mu + max(mu eps, mu eps_abs)) I), mu = max(tr C00, 1e-12) / n_out; B likewise
  *       from Ctt; alpha is clamped to [0, 1], eps_abs and cond_reg to >= 0;
@@ -593,6 +593,42 @@ msm_status msm_mlp_loss_grad(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int
                              const double* h_dropout, uint64_t seed, uint64_t step, double eps, double eps_abs,
                              double alpha, double cond_reg, double* d_work, size_t work_bytes, double* d_stats,
                              double* d_grad, double* d_out, int64_t ldo);
+
+/* The same loss under per-pair weights (VAMP2Loss.forward(z0, zt, weights), losses.py:58-77).  d_w [m] f64:
+ *   w'_s = max(w_s, 0); W = sum w'_s; what_s = w'_s / W;
+ *   mu0 = sum what_s y0_s, mut likewise; C00 = sum what_s (y0_s - mu0)(y0_s - mu0)', Ctt, C0t likewise;
+ *   from there the law above, unchanged (the same solve kernel, dividing by W where it divides by m);
+ *   dloss/dZ0_s = what_s (2 (y0_s - mu0) G_00 + (yt_s - mut) G_0t'), dloss/dZt_s = what_s (2 (yt_s - mut) G_tt +
+ *   (y0_s - mu0) G_0t): the weighted means add nothing, the weighted centred sums being zero.
+ * Only the ratios of the weights matter.  The closed form is that of autograd wherever at least n_out + 2 pairs
+ * carry positive weight (with fewer the smallest eigenvalue is tied and the penalty has no direction).
+ * Divergence from the reference: W must be positive and finite, and every weight finite.  Otherwise loss, score and
+ * all else are NaN and d_stats[10] = 1; no gradient is promised.  (The reference clamps W at 1e-12 and torch's cov
+ * then raises "weights sum to zero".)
+ * d_stats as msm_vamp2_loss, and [11] = W, [12] = W^2 / sum w'^2 (Kish's effective number of pairs).
+ * Kernels: per chunk of 256 pairs the sums of w', w'^2, w' y0 and w' yt; the weighted centred second moments on the
+ * matrix cores, one operand carrying w'_s; the solve; the weighted output gradient.  Chunks are added in ascending
+ * order, no floating-point atomics: equal inputs give equal bits.  A weight past pair m is never read.
+ * d_work: msm_vamp2_weighted_workspace(m, n_out) bytes.  Envelope, NULL and stride checks: msm_vamp2_loss's. */
+size_t msm_vamp2_weighted_workspace(int64_t m, int n_out);
+msm_status msm_vamp2_loss_weighted(msm_ctx* ctx, const double* d_y0, const double* d_yt, const double* d_w, int64_t m,
+                                   int n_out, int64_t ld, double eps, double eps_abs, double alpha, double cond_reg,
+                                   double* d_work, double* d_stats, double* d_grad0, double* d_gradt, int64_t ldg);
+
+/* msm_mlp_loss_grad with the weighted loss: d_w [m] f64 is the weight of pair s (slots s and m + s).  Forward pass,
+ * backward pass and parameter contractions are msm_mlp_loss_grad's own kernels; they receive the weighted dL/dY.
+ * d_w NULL is msm_mlp_loss_grad itself (its workspace, its bits).  d_work: at least
+ * msm_mlp_train_weighted_workspace(...) bytes; messages name msm_mlp_loss_grad. */
+size_t msm_mlp_train_weighted_workspace(int64_t m, int n_linear, const int32_t* h_widths, int ln_in, int ln_hidden,
+                                        int head_activation);
+msm_status msm_mlp_loss_grad_weighted(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n, int F, int64_t ld,
+                                      const double* d_mean, const double* d_scale, int n_linear,
+                                      const int32_t* h_widths, int activation, int ln_in, int ln_hidden,
+                                      int head_activation, const float* d_params, size_t n_params,
+                                      const int64_t* d_idx_t, const int64_t* d_idx_tau, const double* d_w, int64_t m,
+                                      const double* h_dropout, uint64_t seed, uint64_t step, double eps, double eps_abs,
+                                      double alpha, double cond_reg, double* d_work, size_t work_bytes, double* d_stats,
+                                      double* d_grad, double* d_out, int64_t ldo);
 
 /* Gradient clip (trainer.py:1048-1060, torch's clip_grad_norm_) and one step of torch's AdamW with a single
  * parameter group, all in fp64:

@@ -124,6 +124,13 @@ _PROTOTYPES: dict[str, tuple] = {
     "msm_mlp_loss_grad": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _sz,
                                  _vp, _vp, _i64, _vp, C.c_uint64, C.c_uint64, _f64, _f64, _f64, _f64, _vp, _sz, _vp,
                                  _vp, _vp, _i64]),
+    "msm_vamp2_weighted_workspace": (_sz, [_i64, _i32]),
+    "msm_vamp2_loss_weighted": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i64, _f64, _f64, _f64, _f64, _vp, _vp, _vp, _vp,
+                                       _i64]),
+    "msm_mlp_train_weighted_workspace": (_sz, [_i64, _i32, _vp, _i32, _i32, _i32]),
+    "msm_mlp_loss_grad_weighted": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32,
+                                          _vp, _sz, _vp, _vp, _vp, _i64, _vp, C.c_uint64, C.c_uint64, _f64, _f64, _f64,
+                                          _f64, _vp, _sz, _vp, _vp, _vp, _i64]),
     "msm_adamw_step": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _f64, _f64, _f64, _f64, _f64, _f64, _vp]),
     "msm_mlp_vjp_workspace": (_sz, [_i64, _i32, _vp, _i32, _i32, _i32]),
     "msm_mlp_vjp": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _sz, _vp, _i64,

@@ -1,6 +1,7 @@
 // One training step of a DeepTICA network on the device: the forward pass in training mode, the VAMP-2 loss with
 // its closed-form output gradient, the backward pass, and clip + AdamW.  The law: include/msmhip.h
-// (msm_vamp2_loss, msm_mlp_loss_grad, msm_adamw_step).
+// (msm_vamp2_loss, msm_mlp_loss_grad, msm_adamw_step, and the _weighted entries, whose loss takes per-pair weights:
+// other chunk sums, moments and output gradient, the same solve).
 //
 // Frames are addressed by slot: slots 0 .. m-1 are the t frames of the batch (rows idx_t of the resident array),
 // slots m .. 2m-1 the tau frames (rows idx_tau).  As in mlp.hip a workgroup is one wave that owns 16 slots, whose
@@ -315,13 +316,14 @@ __global__ __launch_bounds__(256) void mlp_train_param_reduce_kernel(const doubl
 
 // ---- VAMP-2 loss -------------------------------------------------------------------------------------------------
 // work (doubles): psum [chunks][2 d], pmom [chunks][3][d d], G [3][d d] (G00, Gtt, G0t), mean [2 d],
-// then ten d x d matrices for the solve.
+// then ten d x d matrices for the solve; with weights also wsum [chunks][2] (sum of w', of w'^2) and wtot [2]
+// (W, sum of w'^2), -1 without.
 struct VampWork {
-    long long psum, pmom, G, mean, mats, total;
+    long long psum, pmom, G, mean, mats, wsum, wtot, total;
     int chunks;
 };
 
-inline VampWork vamp_work(int m, int d) {
+inline VampWork vamp_work(int m, int d, bool weighted = false) {
     VampWork w;
     w.chunks = (m + kChunk - 1) / kChunk;
     const long long dd = (long long)d * d;
@@ -331,6 +333,12 @@ inline VampWork vamp_work(int m, int d) {
     w.mean = w.G + 3 * dd;
     w.mats = w.mean + 2 * d;
     w.total = w.mats + 10 * dd;
+    w.wsum = w.wtot = -1;
+    if (weighted) {
+        w.wsum = w.total;
+        w.wtot = w.wsum + (long long)w.chunks * 2;
+        w.total = w.wtot + 2;
+    }
     return w;
 }
 
@@ -344,11 +352,61 @@ __global__ __launch_bounds__(128) void vamp2_colsum_kernel(const double* __restr
     psum[(size_t)blockIdx.x * 2 * d + c] = ordered_sum(src, ld, nr);
 }
 
-// the mean of column c (0 .. 2d-1): the chunks' sums in ascending order, over m
-__device__ __forceinline__ double vamp_mean(const double* __restrict__ psum, int chunks, int d, int m, int c) {
+// the mean of column c (0 .. 2d-1): the chunks' sums in ascending order, over div (m, or the total weight W)
+__device__ __forceinline__ double vamp_mean(const double* __restrict__ psum, int chunks, int d, double div, int c) {
     double s = 0.0;
     for (int k = 0; k < chunks; ++k) s += psum[(size_t)k * 2 * d + c];
-    return s / (double)m;
+    return s / div;
+}
+
+// w' of a pair: max(w, 0); a weight that is not finite stays NaN, so that W is NaN and the solve raises its flag
+__device__ __forceinline__ double vamp_weight(double w) {
+    return fabs(w) <= DBL_MAX ? fmax(w, 0.0) : __longlong_as_double(0x7ff8000000000000ll);
+}
+
+// entry q (0: sum of w', 1: sum of w'^2) of the chunks' weight sums, in ascending order
+__device__ __forceinline__ double vamp_weight_total(const double* __restrict__ wsum, int chunks, int q) {
+    double s = 0.0;
+    for (int k = 0; k < chunks; ++k) s += wsum[(size_t)k * 2 + q];
+    return s;
+}
+
+// f(0) + f(1) + ... (nr terms) in ascending order, eight terms fetched together as in ordered_sum
+template <typename F>
+__device__ __forceinline__ double ordered_sum_of(int nr, F f) {
+    double s = 0.0;
+    int r = 0;
+    for (; r + 8 <= nr; r += 8) {
+        double v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = f(r + u);
+#pragma unroll
+        for (int u = 0; u < 8; ++u) s += v[u];
+    }
+    for (; r < nr; ++r) s += f(r);
+    return s;
+}
+
+// One chunk of pairs under weights: thread c < 2d sums w' Y0 (entries 0 .. d-1) and w' Yt (d .. 2d-1) into psum,
+// threads 2d and 2d + 1 sum w' and w'^2 into wsum.  2d + 2 <= 130 threads do anything, and all of them walk one
+// loop, w'_r times a second factor (the column's entry, 1, or w'_r), so that a wave holding both kinds of thread does
+// not run the chunk twice.
+__global__ __launch_bounds__(192) void vamp2_wsum_kernel(const double* __restrict__ y0, const double* __restrict__ yt,
+                                                         const double* __restrict__ wts, int m, int d, int64_t ld,
+                                                         double* __restrict__ psum, double* __restrict__ wsum) {
+    const int c = threadIdx.x;
+    if (c >= 2 * d + 2) return;
+    const int r0 = blockIdx.x * kChunk, nr = min(kChunk, m - r0);
+    const double* __restrict__ wq = wts + r0;
+    const bool col = c < 2 * d, sq = c == 2 * d + 1;
+    const double* __restrict__ src = col ? (c < d ? y0 + c : yt + (c - d)) + (size_t)r0 * ld : wq;
+    const size_t stride = col ? (size_t)ld : 1;
+    const double s = ordered_sum_of(nr, [&](int r) {
+        const double x = src[(size_t)r * stride];
+        return vamp_weight(wq[r]) * (col ? x : sq ? vamp_weight(x) : 1.0);
+    });
+    if (col) psum[(size_t)blockIdx.x * 2 * d + c] = s;
+    else wsum[(size_t)blockIdx.x * 2 + (sq ? 1 : 0)] = s;
 }
 
 // one 16 x 16 tile of the centred second moments of one chunk: matrix q = 0: Y0'Y0, 1: Yt'Yt, 2: Y0'Yt
@@ -363,12 +421,45 @@ __global__ __launch_bounds__(64) void vamp2_moments_kernel(const double* __restr
     const int r0 = blockIdx.y * kChunk, nr = min(kChunk, m - r0);
     const int ia = min(i0 + j, d - 1), ib = min(c0 + j, d - 1);
     const bool a_tau = q == 1, b_tau = q != 0;
-    const double ma = vamp_mean(psum, chunks, d, m, ia + (a_tau ? d : 0));
-    const double mb = vamp_mean(psum, chunks, d, m, ib + (b_tau ? d : 0));
+    const double ma = vamp_mean(psum, chunks, d, (double)m, ia + (a_tau ? d : 0));
+    const double mb = vamp_mean(psum, chunks, d, (double)m, ib + (b_tau ? d : 0));
     const double* __restrict__ A = (a_tau ? yt : y0) + (size_t)r0 * ld + ia;
     const double* __restrict__ B = (b_tau ? yt : y0) + (size_t)r0 * ld + ib;
     const v4f64 acc = mfma_tile_acc(
         nr, g, i0 + j < d, c0 + j < d, [&](int r) { return A[(size_t)r * ld] - ma; },
+        [&](int r) { return B[(size_t)r * ld] - mb; });
+    double* __restrict__ out = pmom + ((size_t)blockIdx.y * 3 + q) * d * d;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int i = i0 + g + 4 * r;
+        if (i < d && c0 + j < d) out[i * d + c0 + j] = acc[r];
+    }
+}
+
+// vamp2_moments_kernel under weights: the tile of sum_s w'_s (a_s - mean_a)(b_s - mean_b) over one chunk with the
+// weighted means; the first operand carries w'_s, the division by W is the solve's.  A row past the chunk's end is
+// fed as zero and its weight is not read (mfma_tile_acc asks for row 0 in its place).
+__global__ __launch_bounds__(64) void vamp2_wmoments_kernel(const double* __restrict__ y0, const double* __restrict__ yt,
+                                                            const double* __restrict__ wts, int m, int d, int64_t ld,
+                                                            const double* __restrict__ psum,
+                                                            const double* __restrict__ wsum, int chunks,
+                                                            double* __restrict__ pmom) {
+    const int lane = threadIdx.x;
+    const int j = lane & 15, g = lane >> 4;
+    const int T = (d + 15) / 16;
+    const int q = blockIdx.x / (T * T), tile = blockIdx.x % (T * T);
+    const int i0 = (tile / T) * 16, c0 = (tile % T) * 16;
+    const int r0 = blockIdx.y * kChunk, nr = min(kChunk, m - r0);
+    const int ia = min(i0 + j, d - 1), ib = min(c0 + j, d - 1);
+    const bool a_tau = q == 1, b_tau = q != 0;
+    const double W = vamp_weight_total(wsum, chunks, 0);
+    const double ma = vamp_mean(psum, chunks, d, W, ia + (a_tau ? d : 0));
+    const double mb = vamp_mean(psum, chunks, d, W, ib + (b_tau ? d : 0));
+    const double* __restrict__ A = (a_tau ? yt : y0) + (size_t)r0 * ld + ia;
+    const double* __restrict__ B = (b_tau ? yt : y0) + (size_t)r0 * ld + ib;
+    const double* __restrict__ wq = wts + r0;
+    const v4f64 acc = mfma_tile_acc(
+        nr, g, i0 + j < d, c0 + j < d, [&](int r) { return vamp_weight(wq[r]) * (A[(size_t)r * ld] - ma); },
         [&](int r) { return B[(size_t)r * ld] - mb; });
     double* __restrict__ out = pmom + ((size_t)blockIdx.y * 3 + q) * d * d;
 #pragma unroll
@@ -554,14 +645,23 @@ __device__ void solve_side(double* Cq, double* Li, double* P, int d, const VampO
 
 // The small dense algebra of the loss in one workgroup: moments from the chunks' partial sums, both sides'
 // regularisation, spectra and inverse Cholesky factors, K = La^-1 C0t Lb^-T, score, penalty, and the three
-// gradient matrices G00, Gtt, G0t.  stats: see MSM_VAMP2_* in include/msmhip.h.
+// gradient matrices G00, Gtt, G0t.  stats: see MSM_VAMP2_* in include/msmhip.h.  Under weights (w.wsum >= 0) the
+// moments and the means are divided by the total weight W instead of m; a W that is not positive and finite ends
+// the solve with NaN everywhere and stats[10] = 1.
 __global__ __launch_bounds__(kSolveThreads) void vamp2_solve_kernel(int m, int d, VampOpts o, VampWork w,
                                                                    double* __restrict__ work,
                                                                    double* __restrict__ stats) {
     extern __shared__ __attribute__((aligned(16))) unsigned char vamp_smem[];
     double* lds = reinterpret_cast<double*>(vamp_smem);   // two d x d matrices
-    __shared__ double shA[8], shB[8], red[kSolveThreads / 64];
+    __shared__ double shA[8], shB[8], shW[2], red[kSolveThreads / 64];
     __shared__ int flag[4];
+    const bool weighted = w.wsum >= 0;
+    if (threadIdx.x == 0) {
+        shW[0] = weighted ? vamp_weight_total(work + w.wsum, w.chunks, 0) : (double)m;
+        shW[1] = weighted ? vamp_weight_total(work + w.wsum, w.chunks, 1) : (double)m;
+    }
+    __syncthreads();
+    const double div = shW[0];   // m, or W
     const long long dd = (long long)d * d;
     double* M = work + w.mats;
     double* C00 = M, *Ctt = M + dd, *C0t = M + 2 * dd, *LAi = M + 3 * dd, *LBi = M + 4 * dd, *PA = M + 5 * dd,
@@ -572,14 +672,23 @@ __global__ __launch_bounds__(kSolveThreads) void vamp2_solve_kernel(int m, int d
     for (int e = threadIdx.x; e < 3 * dd; e += blockDim.x) {
         double s = 0.0;
         for (int k = 0; k < w.chunks; ++k) s += pmom[(size_t)k * 3 * dd + e];
-        M[e] = s / (double)m;
+        M[e] = s / div;
     }
     for (int c = threadIdx.x; c < 2 * d; c += blockDim.x) {
-        const double mu = vamp_mean(psum, w.chunks, d, m, c);
+        const double mu = vamp_mean(psum, w.chunks, d, div, c);
         work[w.mean + c] = mu;
         stats[kStatsHead + 2 * kMlpMaxOut + (c < d ? c : kMlpMaxOut + c - d)] = mu;
     }
     __syncthreads();
+    if (weighted && !(div > 0.0 && div <= DBL_MAX)) {   // uniform: every thread read the same W
+        const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+        for (int e = threadIdx.x; e < 3 * dd; e += blockDim.x) work[w.G + e] = qnan;
+        for (int c = threadIdx.x; c < 2 * d; c += blockDim.x) work[w.mean + c] = qnan;
+        for (int i = threadIdx.x; i < kStatsHead + 4 * kMlpMaxOut; i += blockDim.x)
+            stats[i] = i < 2 || i >= kStatsHead ? qnan : i == 10 ? 1.0 : i == 11 ? div : 0.0;
+        if (threadIdx.x == 0) work[w.wtot] = work[w.wtot + 1] = qnan;
+        return;
+    }
     for (int c = threadIdx.x; c < d; c += blockDim.x) {
         stats[kStatsHead + c] = C00[c * d + c];
         stats[kStatsHead + kMlpMaxOut + c] = Ctt[c * d + c];
@@ -638,6 +747,11 @@ __global__ __launch_bounds__(kSolveThreads) void vamp2_solve_kernel(int m, int d
         stats[8] = shB[2];
         stats[9] = failed ? 1.0 : 0.0;
         for (int i = 10; i < kStatsHead; ++i) stats[i] = 0.0;
+        if (weighted) {
+            stats[11] = work[w.wtot] = shW[0];
+            work[w.wtot + 1] = shW[1];
+            stats[12] = shW[0] * shW[0] / shW[1];
+        }
     }
 }
 
@@ -664,13 +778,47 @@ __global__ __launch_bounds__(256) void vamp2_grad_kernel(const double* __restric
     gt[s * ldg + c] = (2.0 * at + bt) / (double)m;
 }
 
-msm_status vamp2_launch(msm_ctx* ctx, const double* y0, const double* yt, int m, int d, int64_t ld, const VampOpts& o,
-                        double* work, double* stats, double* g0, double* gt, int64_t ldg) {
-    const VampWork w = vamp_work(m, d);
+// vamp2_grad_kernel under weights: pair s carries w'_s / W (wtot[0], left by the solve) instead of 1 / m
+__global__ __launch_bounds__(256) void vamp2_wgrad_kernel(const double* __restrict__ y0, const double* __restrict__ yt,
+                                                          const double* __restrict__ wts, int m, int d, int64_t ld,
+                                                          const double* __restrict__ G, const double* __restrict__ mean,
+                                                          const double* __restrict__ wtot, double* __restrict__ g0,
+                                                          double* __restrict__ gt, int64_t ldg) {
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (long long)m * d) return;
+    const int64_t s = e / d;
+    const int c = (int)(e - s * d);
+    const long long dd = (long long)d * d;
+    const double* G00 = G, *Gtt = G + dd, *G0t = G + 2 * dd;
+    double a0 = 0.0, b0 = 0.0, at = 0.0, bt = 0.0;
+    for (int k = 0; k < d; ++k) {
+        const double v0 = y0[s * ld + k] - mean[k], vt = yt[s * ld + k] - mean[d + k];
+        a0 += v0 * G00[k * d + c];
+        b0 += vt * G0t[c * d + k];
+        at += vt * Gtt[k * d + c];
+        bt += v0 * G0t[k * d + c];
+    }
+    const double what = vamp_weight(wts[s]) / wtot[0];
+    g0[s * ldg + c] = what * (2.0 * a0 + b0);
+    gt[s * ldg + c] = what * (2.0 * at + bt);
+}
+
+// wts: the pairs' weights [m], or NULL for uniform weights (work is then vamp_work(m, d), else vamp_work(m, d, true))
+msm_status vamp2_launch(msm_ctx* ctx, const double* y0, const double* yt, const double* wts, int m, int d, int64_t ld,
+                        const VampOpts& o, double* work, double* stats, double* g0, double* gt, int64_t ldg) {
+    const VampWork w = vamp_work(m, d, wts != nullptr);
     const int T = (d + 15) / 16;
-    hipLaunchKernelGGL(vamp2_colsum_kernel, dim3(w.chunks), dim3(128), 0, ctx->stream, y0, yt, m, d, ld, work + w.psum);
-    hipLaunchKernelGGL(vamp2_moments_kernel, dim3(3 * T * T, w.chunks), dim3(64), 0, ctx->stream, y0, yt, m, d, ld,
-                       work + w.psum, w.chunks, work + w.pmom);
+    if (wts) {
+        hipLaunchKernelGGL(vamp2_wsum_kernel, dim3(w.chunks), dim3(192), 0, ctx->stream, y0, yt, wts, m, d, ld,
+                           work + w.psum, work + w.wsum);
+        hipLaunchKernelGGL(vamp2_wmoments_kernel, dim3(3 * T * T, w.chunks), dim3(64), 0, ctx->stream, y0, yt, wts, m, d,
+                           ld, work + w.psum, work + w.wsum, w.chunks, work + w.pmom);
+    } else {
+        hipLaunchKernelGGL(vamp2_colsum_kernel, dim3(w.chunks), dim3(128), 0, ctx->stream, y0, yt, m, d, ld,
+                           work + w.psum);
+        hipLaunchKernelGGL(vamp2_moments_kernel, dim3(3 * T * T, w.chunks), dim3(64), 0, ctx->stream, y0, yt, m, d, ld,
+                           work + w.psum, w.chunks, work + w.pmom);
+    }
     const size_t lds = (size_t)2 * d * d * sizeof(double);   // <= 64 KiB
     if (lds > 48 * 1024)
         MSM_HIP(ctx, hipFuncSetAttribute((const void*)vamp2_solve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -678,14 +826,19 @@ msm_status vamp2_launch(msm_ctx* ctx, const double* y0, const double* yt, int m,
     hipLaunchKernelGGL(vamp2_solve_kernel, dim3(1), dim3(kSolveThreads), lds, ctx->stream, m, d, o, w, work, stats);
     if (g0) {
         const long long total = (long long)m * d;
-        hipLaunchKernelGGL(vamp2_grad_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, y0, yt,
-                           m, d, ld, work + w.G, work + w.mean, g0, gt, ldg);
+        const dim3 grid((unsigned)((total + 255) / 256));
+        if (wts)
+            hipLaunchKernelGGL(vamp2_wgrad_kernel, grid, dim3(256), 0, ctx->stream, y0, yt, wts, m, d, ld, work + w.G,
+                               work + w.mean, work + w.wtot, g0, gt, ldg);
+        else
+            hipLaunchKernelGGL(vamp2_grad_kernel, grid, dim3(256), 0, ctx->stream, y0, yt, m, d, ld, work + w.G,
+                               work + w.mean, g0, gt, ldg);
     }
     MSM_CHECK_LAUNCH(ctx);
     return MSM_OK;
 }
 
-TrainLayout train_layout(const MlpPlan& p, int m, size_t n_params) {
+TrainLayout train_layout(const MlpPlan& p, int m, size_t n_params, bool weighted = false) {
     TrainLayout t;
     const long long S2 = 2LL * m;
     long long off = 0;
@@ -719,7 +872,7 @@ TrainLayout train_layout(const MlpPlan& p, int m, size_t n_params) {
     t.partial = off;
     off += (long long)((S2 + kChunk - 1) / kChunk) * (long long)n_params;
     t.loss = off;
-    off += vamp_work(m, p.width[L]).total;
+    off += vamp_work(m, p.width[L], weighted).total;
     t.total = off;
     return t;
 }
@@ -764,6 +917,35 @@ __global__ __launch_bounds__(256) void adamw_update_kernel(float* __restrict__ p
     prm[e] = (float)w;
 }
 
+// msm_vamp2_loss (d_w NULL) and msm_vamp2_loss_weighted: one envelope, one set of checks
+msm_status vamp2_entry(msm_ctx* ctx, const char* fn, const double* d_y0, const double* d_yt, const double* d_w,
+                       int64_t m, int n_out, int64_t ld, double eps, double eps_abs, double alpha, double cond_reg,
+                       double* d_work, double* d_stats, double* d_grad0, double* d_gradt, int64_t ldg) {
+    if (!ctx) return MSM_ERR_INVALID;
+    MSM_REQUIRE(ctx, m >= 1 && m <= (1 << 29), "%s: %lld frame pairs", fn, (long long)m);
+    MSM_REQUIRE(ctx, n_out >= 1, "%s: %d outputs", fn, n_out);
+    if (n_out > kMlpMaxOut)
+        return msm_fail(ctx, MSM_ERR_UNSUPPORTED, "%s: %d outputs (at most %d are supported)", fn, n_out, kMlpMaxOut);
+    MSM_REQUIRE(ctx, ld >= n_out, "%s: row stride %lld for %d outputs", fn, (long long)ld, n_out);
+    MSM_REQUIRE(ctx, d_y0 && d_yt && d_work && d_stats, "%s: NULL pointer", fn);
+    MSM_REQUIRE(ctx, (d_grad0 == nullptr) == (d_gradt == nullptr), "%s: the two gradients go together", fn);
+    MSM_REQUIRE(ctx, !d_grad0 || ldg >= n_out, "%s: gradient row stride %lld for %d outputs", fn, (long long)ldg, n_out);
+    const VampOpts o = {eps, std::max(eps_abs, 0.0), std::min(std::max(alpha, 0.0), 1.0), std::max(cond_reg, 0.0)};
+    return vamp2_launch(ctx, d_y0, d_yt, d_w, (int)m, n_out, ld, o, d_work, d_stats, d_grad0, d_gradt, ldg);
+}
+
+// msm_mlp_train_workspace and its weighted sibling
+size_t train_workspace(int64_t m, int n_linear, const int32_t* h_widths, int ln_in, int ln_hidden, int head_activation,
+                       bool weighted) {
+    if (!h_widths || m < 2 || m > (1 << 24)) return 0;
+    MlpPlan p;
+    size_t n_params = 0;   // a refusal has nowhere to leave its message (no context): it is reported as 0
+    if (mlp_make_plan(nullptr, "msm_mlp_train_workspace", h_widths[0], n_linear, h_widths, 0, ln_in, ln_hidden,
+                      head_activation, kMlpAnyParams, &p, &n_params))
+        return 0;
+    return (size_t)train_layout(p, (int)m, n_params, weighted).total * sizeof(double);
+}
+
 }  // namespace
 
 extern "C" {
@@ -776,30 +958,32 @@ size_t msm_vamp2_workspace(int64_t m, int n_out) {
 msm_status msm_vamp2_loss(msm_ctx* ctx, const double* d_y0, const double* d_yt, int64_t m, int n_out, int64_t ld,
                           double eps, double eps_abs, double alpha, double cond_reg, double* d_work,
                           double* d_stats, double* d_grad0, double* d_gradt, int64_t ldg) {
+    return vamp2_entry(ctx, "msm_vamp2_loss", d_y0, d_yt, nullptr, m, n_out, ld, eps, eps_abs, alpha, cond_reg, d_work,
+                       d_stats, d_grad0, d_gradt, ldg);
+}
+
+size_t msm_vamp2_weighted_workspace(int64_t m, int n_out) {
+    if (m < 1 || n_out < 1 || n_out > kMlpMaxOut || m > (1 << 29)) return 0;
+    return (size_t)vamp_work((int)m, n_out, true).total * sizeof(double);
+}
+
+msm_status msm_vamp2_loss_weighted(msm_ctx* ctx, const double* d_y0, const double* d_yt, const double* d_w, int64_t m,
+                                   int n_out, int64_t ld, double eps, double eps_abs, double alpha, double cond_reg,
+                                   double* d_work, double* d_stats, double* d_grad0, double* d_gradt, int64_t ldg) {
     if (!ctx) return MSM_ERR_INVALID;
-    MSM_REQUIRE(ctx, m >= 1 && m <= (1 << 29), "msm_vamp2_loss: %lld frame pairs", (long long)m);
-    MSM_REQUIRE(ctx, n_out >= 1, "msm_vamp2_loss: %d outputs", n_out);
-    if (n_out > kMlpMaxOut)
-        return msm_fail(ctx, MSM_ERR_UNSUPPORTED, "msm_vamp2_loss: %d outputs (at most %d are supported)", n_out,
-                        kMlpMaxOut);
-    MSM_REQUIRE(ctx, ld >= n_out, "msm_vamp2_loss: row stride %lld for %d outputs", (long long)ld, n_out);
-    MSM_REQUIRE(ctx, d_y0 && d_yt && d_work && d_stats, "msm_vamp2_loss: NULL pointer");
-    MSM_REQUIRE(ctx, (d_grad0 == nullptr) == (d_gradt == nullptr), "msm_vamp2_loss: the two gradients go together");
-    MSM_REQUIRE(ctx, !d_grad0 || ldg >= n_out, "msm_vamp2_loss: gradient row stride %lld for %d outputs",
-                (long long)ldg, n_out);
-    const VampOpts o = {eps, std::max(eps_abs, 0.0), std::min(std::max(alpha, 0.0), 1.0), std::max(cond_reg, 0.0)};
-    return vamp2_launch(ctx, d_y0, d_yt, (int)m, n_out, ld, o, d_work, d_stats, d_grad0, d_gradt, ldg);
+    MSM_REQUIRE(ctx, d_w, "msm_vamp2_loss_weighted: NULL pointer");
+    return vamp2_entry(ctx, "msm_vamp2_loss_weighted", d_y0, d_yt, d_w, m, n_out, ld, eps, eps_abs, alpha, cond_reg,
+                       d_work, d_stats, d_grad0, d_gradt, ldg);
 }
 
 size_t msm_mlp_train_workspace(int64_t m, int n_linear, const int32_t* h_widths, int ln_in, int ln_hidden,
                                int head_activation) {
-    if (!h_widths || m < 2 || m > (1 << 24)) return 0;
-    MlpPlan p;
-    size_t n_params = 0;   // a refusal has nowhere to leave its message (no context): it is reported as 0
-    if (mlp_make_plan(nullptr, "msm_mlp_train_workspace", h_widths[0], n_linear, h_widths, 0, ln_in, ln_hidden,
-                      head_activation, kMlpAnyParams, &p, &n_params))
-        return 0;
-    return (size_t)train_layout(p, (int)m, n_params).total * sizeof(double);
+    return train_workspace(m, n_linear, h_widths, ln_in, ln_hidden, head_activation, false);
+}
+
+size_t msm_mlp_train_weighted_workspace(int64_t m, int n_linear, const int32_t* h_widths, int ln_in, int ln_hidden,
+                                        int head_activation) {
+    return train_workspace(m, n_linear, h_widths, ln_in, ln_hidden, head_activation, true);
 }
 
 msm_status msm_mlp_loss_grad(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n, int F, int64_t ld,
@@ -809,6 +993,20 @@ msm_status msm_mlp_loss_grad(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int
                              const double* h_dropout, uint64_t seed, uint64_t step, double eps, double eps_abs,
                              double alpha, double cond_reg, double* d_work, size_t work_bytes, double* d_stats,
                              double* d_grad, double* d_out, int64_t ldo) {
+    return msm_mlp_loss_grad_weighted(ctx, d_x, dtype, n, F, ld, d_mean, d_scale, n_linear, h_widths, activation, ln_in,
+                                      ln_hidden, head_activation, d_params, n_params, d_idx_t, d_idx_tau, nullptr, m,
+                                      h_dropout, seed, step, eps, eps_abs, alpha, cond_reg, d_work, work_bytes, d_stats,
+                                      d_grad, d_out, ldo);
+}
+
+msm_status msm_mlp_loss_grad_weighted(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n, int F, int64_t ld,
+                                      const double* d_mean, const double* d_scale, int n_linear,
+                                      const int32_t* h_widths, int activation, int ln_in, int ln_hidden,
+                                      int head_activation, const float* d_params, size_t n_params,
+                                      const int64_t* d_idx_t, const int64_t* d_idx_tau, const double* d_w, int64_t m,
+                                      const double* h_dropout, uint64_t seed, uint64_t step, double eps, double eps_abs,
+                                      double alpha, double cond_reg, double* d_work, size_t work_bytes, double* d_stats,
+                                      double* d_grad, double* d_out, int64_t ldo) {
     if (!ctx) return MSM_ERR_INVALID;
     MSM_REQUIRE(ctx, dtype == MSM_F32 || dtype == MSM_F64, "msm_mlp_loss_grad: bad dtype");
     MlpPlan p;
@@ -845,7 +1043,7 @@ msm_status msm_mlp_loss_grad(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int
             drop.scale[i] = 1.0 / (1.0 - q);
             if (drop.thr[i]) drop.on = 1;
         }
-    const TrainLayout lay = train_layout(p, (int)m, n_params);
+    const TrainLayout lay = train_layout(p, (int)m, n_params, d_w != nullptr);
     MSM_REQUIRE(ctx, work_bytes >= (size_t)lay.total * sizeof(double),
                 "msm_mlp_loss_grad: workspace of %zu bytes, %zu are needed", work_bytes,
                 (size_t)lay.total * sizeof(double));
@@ -870,8 +1068,8 @@ msm_status msm_mlp_loss_grad(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int
     double* y = d_work + lay.y;
     double* dy = d_work + lay.dy;
     const VampOpts o = {eps, std::max(eps_abs, 0.0), std::min(std::max(alpha, 0.0), 1.0), std::max(cond_reg, 0.0)};
-    if (msm_status st = vamp2_launch(ctx, y, y + (size_t)m * n_out, (int)m, n_out, n_out, o, d_work + lay.loss, d_stats,
-                                     d_grad ? dy : nullptr, d_grad ? dy + (size_t)m * n_out : nullptr, n_out))
+    if (msm_status st = vamp2_launch(ctx, y, y + (size_t)m * n_out, d_w, (int)m, n_out, n_out, o, d_work + lay.loss,
+                                     d_stats, d_grad ? dy : nullptr, d_grad ? dy + (size_t)m * n_out : nullptr, n_out))
         return st;
     if (d_out)
         MSM_HIP(ctx, hipMemcpy2DAsync(d_out, (size_t)ldo * sizeof(double), y, (size_t)n_out * sizeof(double),

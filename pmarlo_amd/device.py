@@ -1090,13 +1090,46 @@ class Engine:
                             "eig_C00_max": float(stats[6]), "eig_Ctt_min": float(stats[7]),
                             "eig_Ctt_max": float(stats[8])}}
 
+    def _pair_weights(self, weights, m: int) -> DeviceArray:
+        """Per-pair weights [m] on the device: an f64 device array as it is, a host array checked (finite, clamped
+        sum positive) and uploaded."""
+        if isinstance(weights, DeviceArray):
+            if weights.dtype != np.float64:
+                raise TypeError("pair weights on the device must be float64")
+            if weights.size != m:
+                raise ValueError(f"{weights.size} weights for {m} frame pairs")
+            return weights
+        w = np.ascontiguousarray(weights, np.float64).reshape(-1)
+        if w.size != m:
+            raise ValueError(f"{w.size} weights for {m} frame pairs")
+        if not np.all(np.isfinite(w)):
+            raise ValueError("pair weights must be finite")
+        total = float(np.clip(w, 0.0, None).sum())
+        if not (total > 0.0 and np.isfinite(total)):
+            raise ValueError("pair weights sum to zero" if total == 0.0 else "the sum of the pair weights overflows")
+        return self.to_device(w)
+
+    def _weighted_stats(self, stats: np.ndarray, d: int) -> dict:
+        """The stats block of a weighted call: the device's weight flag first, then _vamp2_stats and the two
+        weight figures."""
+        if stats[10] != 0.0:
+            raise RuntimeError("pair weights on the device are not finite or do not sum to a positive number")
+        res = self._vamp2_stats(stats, d)
+        res["total_weight"], res["effective_pairs"] = float(stats[11]), float(stats[12])
+        return res
+
     def vamp2_loss(self, z0: DeviceArray, zt: DeviceArray, *, eps: float = 1e-3, eps_abs: float = 1e-6,
-                   alpha: float = 0.15, cond_reg: float = 1e-4, want_grad: bool = True, ld: int | None = None) -> dict:
+                   alpha: float = 0.15, cond_reg: float = 1e-4, want_grad: bool = True, ld: int | None = None,
+                   weights=None) -> dict:
         """VAMP-2 loss of the outputs z0, zt [m, n_out] f64 with uniform weights (msm_vamp2_loss): a dict of loss,
         score, penalty, `metrics` (the reference's ten latest_metrics) and, with want_grad, `grad0` / `grad_t`
         [m, n_out] f64 on the device, the derivative of the loss with respect to z0 / zt.  ``ld``: row stride of
         both inputs when they are blocks of wider buffers.  A Cholesky failure after the jitter ladder raises
-        RuntimeError as the reference does."""
+        RuntimeError as the reference does.
+        ``weights``: per-pair weights [m], a host array or an f64 device array (msm_vamp2_loss_weighted: negative
+        weights count as 0, only ratios matter); the result then also has `total_weight` and `effective_pairs`
+        (Kish).  Host weights that are not finite or whose clamped sum is 0 raise ValueError; the same found on the
+        device raises RuntimeError."""
         m, d = z0.shape
         if zt.shape != z0.shape:
             raise ValueError("z0 and zt must share the same shape")
@@ -1106,14 +1139,20 @@ class Engine:
             raise ValueError("VAMP2Loss received empty batch")
         if d > _lib.MLP_MAX_OUT:
             raise NotImplementedError(f"{d} outputs (at most {_lib.MLP_MAX_OUT} are supported)")
-        work = self.empty((max(int(lib.msm_vamp2_workspace(m, d)), 8) // 8,), np.float64)
+        wts = self._pair_weights(weights, m) if weights is not None else None
+        sizer = lib.msm_vamp2_workspace if wts is None else lib.msm_vamp2_weighted_workspace
+        work = self.empty((max(int(sizer(m, d)), 8) // 8,), np.float64)
         stats = self.empty((_lib.VAMP2_STATS,), np.float64)
         g0 = self.empty((m, d), np.float64) if want_grad else None
         gt = self.empty((m, d), np.float64) if want_grad else None
-        check(lib.msm_vamp2_loss(self.handle, z0.ptr, zt.ptr, m, d, int(d if ld is None else ld), float(eps),
-                                 float(eps_abs), float(alpha), float(cond_reg), work.ptr, stats.ptr,
-                                 g0.ptr if want_grad else None, gt.ptr if want_grad else None, d), self.handle)
-        res = self._vamp2_stats(stats.to_host(), d)
+        tail = (m, d, int(d if ld is None else ld), float(eps), float(eps_abs), float(alpha), float(cond_reg), work.ptr,
+                stats.ptr, g0.ptr if want_grad else None, gt.ptr if want_grad else None, d)
+        if wts is None:
+            check(lib.msm_vamp2_loss(self.handle, z0.ptr, zt.ptr, *tail), self.handle)
+            res = self._vamp2_stats(stats.to_host(), d)
+        else:
+            check(lib.msm_vamp2_loss_weighted(self.handle, z0.ptr, zt.ptr, wts.ptr, *tail), self.handle)
+            res = self._weighted_stats(stats.to_host(), d)
         if want_grad:
             res["grad0"], res["grad_t"] = g0, gt
         return res
@@ -1131,7 +1170,7 @@ class Engine:
     def mlp_loss_grad(self, x: DeviceArray, spec, idx_t, idx_tau, *, dropout=None, seed: int = 0, step: int = 0,
                       eps: float = 1e-3, eps_abs: float = 1e-6, alpha: float = 0.15, cond_reg: float = 1e-4,
                       want_grad: bool = True, want_outputs: bool = False, ld: int | None = None,
-                      work: DeviceArray | None = None) -> dict:
+                      work: DeviceArray | None = None, weights=None) -> dict:
         """Loss and parameter gradient of the network `spec` on the lagged pairs (idx_t[i], idx_tau[i]) of the
         resident frames x [n, F] (msm_mlp_loss_grad).  idx_t, idx_tau: equally long integer arrays (host arrays are
         range-checked and uploaded; int64 device arrays are used as they are).  dropout: None for evaluation
@@ -1140,7 +1179,9 @@ class Engine:
         its output gradients, plus `grad` [n_params] f64 (want_grad) and `outputs` [2m, n_out] f64 (want_outputs:
         the t frames' outputs, then the tau frames'), both on the device, and `work`, the workspace the call used
         (msm_mlp_train_workspace bytes): hand it back through ``work`` and the next call of the same or a smaller
-        shape allocates nothing."""
+        shape allocates nothing.
+        ``weights``: per-pair weights [m] as in vamp2_loss (msm_mlp_loss_grad_weighted); the result then also has
+        `total_weight` and `effective_pairs`, and the workspace is msm_mlp_train_weighted_workspace bytes."""
         n, F = x.shape
         widths = np.ascontiguousarray(spec.widths, np.int32)
         spec.check_envelope()
@@ -1160,7 +1201,9 @@ class Engine:
                 raise ValueError(f"dropout probabilities {drop.tolist()} (0 <= p < 1)")
         params, mean, scale = self._mlp_on_device(spec)
         flags = (int(bool(spec.ln_in)), int(bool(spec.ln_hidden)), int(bool(spec.head_activation)))
-        need = int(lib.msm_mlp_train_workspace(m, n_linear, widths.ctypes.data, *flags))
+        wts = self._pair_weights(weights, m) if weights is not None else None
+        sizer = lib.msm_mlp_train_workspace if wts is None else lib.msm_mlp_train_weighted_workspace
+        need = int(sizer(m, n_linear, widths.ctypes.data, *flags))
         if need == 0:
             raise NotImplementedError(f"{m} frame pairs (at most {1 << 24} are supported)")
         if work is None or work.nbytes < need:
@@ -1169,15 +1212,18 @@ class Engine:
         stats = self.empty((_lib.VAMP2_STATS,), np.float64)
         grad = self.empty((params.size,), np.float64) if want_grad else None
         out = self.empty((2 * m, d), np.float64) if want_outputs else None
-        check(lib.msm_mlp_loss_grad(self.handle, x.ptr, _dtype_code(x.dtype), n, F, int(F if ld is None else ld),
-                                    mean.ptr if mean is not None else None, scale.ptr if scale is not None else None,
-                                    n_linear, widths.ctypes.data, int(spec.activation), *flags, params.ptr, params.size,
-                                    it.ptr, itau.ptr, m, drop.ctypes.data if drop is not None else None,
-                                    int(seed) & 0xFFFFFFFFFFFFFFFF, int(step), float(eps), float(eps_abs),
-                                    float(alpha), float(cond_reg), work.ptr, work.nbytes, stats.ptr,
-                                    grad.ptr if want_grad else None, out.ptr if want_outputs else None, d),
-              self.handle)
-        res = self._vamp2_stats(stats.to_host(), d)
+        head = (self.handle, x.ptr, _dtype_code(x.dtype), n, F, int(F if ld is None else ld),
+                mean.ptr if mean is not None else None, scale.ptr if scale is not None else None, n_linear,
+                widths.ctypes.data, int(spec.activation), *flags, params.ptr, params.size, it.ptr, itau.ptr)
+        tail = (m, drop.ctypes.data if drop is not None else None, int(seed) & 0xFFFFFFFFFFFFFFFF, int(step), float(eps),
+                float(eps_abs), float(alpha), float(cond_reg), work.ptr, work.nbytes, stats.ptr,
+                grad.ptr if want_grad else None, out.ptr if want_outputs else None, d)
+        if wts is None:
+            check(lib.msm_mlp_loss_grad(*head, *tail), self.handle)
+            res = self._vamp2_stats(stats.to_host(), d)
+        else:
+            check(lib.msm_mlp_loss_grad_weighted(*head, wts.ptr, *tail), self.handle)
+            res = self._weighted_stats(stats.to_host(), d)
         res["work"] = work
         if want_grad:
             res["grad"] = grad

@@ -18,7 +18,14 @@ Stated divergences from the reference:
     and the reference's loss of one pair is the constant 0 with a zero gradient;
   * a dropout probability of 1 or more raises ValueError;
   * device selection, checkpoint / CSV / progress files and the data-loader workers are left out (the fields
-    device, checkpoint_dir and num_workers do not exist)."""
+    device, checkpoint_dir and num_workers do not exist).
+
+Weights (this engine's addition; the reference's curriculum trainer has none).  train_step, evaluate and fit take
+per-pair / per-frame weights and run the weighted loss of VAMP2Loss.forward(z0, zt, weights) on the device
+(msm_mlp_loss_grad_weighted).  The weight of a pair is the weight of its t frame; every batch normalises its own
+weights, as VAMP2Loss.forward does; epoch aggregates and evaluate then weight a batch by its total (clamped) weight
+instead of its size.  A batch whose weights are all zero carries no information and is dropped; one whose effective
+number of pairs (Kish) is below n_out + 2 is trained on with a warning.  Without weights nothing changes."""
 
 from __future__ import annotations
 
@@ -151,6 +158,7 @@ class _EpochSums:
     def __init__(self):
         self.loss = self.score = self.cond0 = self.condt = 0.0
         self.weight = 0
+        self.effective: list[float] = []
         self.norms: list[float] = []
         self.norms_preclip: list[float] = []
         self.vectors: dict[str, np.ndarray] = {}
@@ -162,6 +170,8 @@ class _EpochSums:
         self.weight += batch
         self.norms.append(out["grad_norm"])
         self.norms_preclip.append(out["grad_norm_preclip"])
+        if "effective_pairs" in out:
+            self.effective.append(out["effective_pairs"])
         met = out["metrics"]
         self.cond0 += met["cond_C00"] * batch
         self.condt += met["cond_Ctt"] * batch
@@ -238,13 +248,17 @@ class DeepTICACurriculumTrainer:
             raise ValueError(f"frames of shape {x.shape} for a network of {self.model.spec.widths[0]} features")
         self._x = x
 
-    def _call(self, idx_t, idx_tau, train: bool) -> dict:
+    def _call(self, idx_t, idx_tau, train: bool, weights=None) -> dict:
         if self._x is None:
             raise RuntimeError("no frames are resident: call set_frames or fit first")
         res = self.engine.mlp_loss_grad(
             self._x, self.model.spec, idx_t, idx_tau, dropout=self.dropout if train else None, seed=self.seed,
-            step=self.step, want_grad=train, work=self._work, **self._loss)
+            step=self.step, want_grad=train, work=self._work, weights=weights, **self._loss)
         self._work = res.pop("work")
+        n_out = int(self.model.spec.widths[-1])
+        if weights is not None and res["effective_pairs"] < n_out + 2:
+            logger.warning("A batch has %.3g effective pairs for %d outputs (fewer than n_out + 2): its weights "
+                           "leave the loss ill-determined", res["effective_pairs"], n_out)
         return res
 
     def state(self) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -252,11 +266,13 @@ class DeepTICACurriculumTrainer:
         return self._params.to_host(), self._m.to_host(), self._v.to_host()
 
     # -- one optimisation step ------------------------------------------------
-    def train_step(self, idx_t, idx_tau) -> dict:
+    def train_step(self, idx_t, idx_tau, weights=None) -> dict:
         """One step on the pairs (idx_t[i], idx_tau[i]) of the resident frames: loss, score, metrics,
         grad_norm_preclip, grad_norm (after the clip) and batch_size.  Raises FloatingPointError when the gradient
-        norm is not finite; the parameters and the optimiser state are then untouched."""
-        res = self._call(idx_t, idx_tau, True)
+        norm is not finite; the parameters and the optimiser state are then untouched.  ``weights``: one weight per
+        pair (host array or f64 device array), normalised within the batch; the result then also has total_weight
+        and effective_pairs."""
+        res = self._call(idx_t, idx_tau, True) if weights is None else self._call(idx_t, idx_tau, True, weights)
         upd = self.engine.adamw_step(
             self._params, res.pop("grad"), self._m, self._v, self.step + 1, lr=self._current_lr, betas=_ADAM_BETAS,
             eps=_ADAM_EPS, weight_decay=float(max(self.cfg.weight_decay, 0.0)), clip=self.cfg.grad_clip_norm)
@@ -267,42 +283,89 @@ class DeepTICACurriculumTrainer:
                    batch_size=int(np.size(idx_t) if not hasattr(idx_t, "size") else idx_t.size))
         return res
 
-    def _batches(self, idx_t, idx_tau, shuffle: bool):
+    def _batches(self, idx_t, idx_tau, shuffle: bool, weights=None):
+        """(idx_t, idx_tau, weights or None, the batch's share in an aggregate) of every batch: the share is the
+        batch size without weights and the batch's total clamped weight with them."""
         order = self._rng.permutation(idx_t.size) if shuffle else np.arange(idx_t.size)
         b = int(self.cfg.batch_size)
         for start in range(0, idx_t.size, b):
             sel = order[start:start + b]
-            if sel.size >= 2:
-                yield idx_t[sel], idx_tau[sel]
+            if sel.size < 2:
+                continue
+            if weights is None:
+                yield idx_t[sel], idx_tau[sel], None, sel.size
+                continue
+            bw = weights[sel]
+            total = float(np.clip(bw, 0.0, None).sum())
+            if total > 0.0:
+                yield idx_t[sel], idx_tau[sel], bw, total
 
-    def evaluate(self, idx_t, idx_tau) -> dict:
+    @staticmethod
+    def _pair_weight_array(weights, m: int):
+        if weights is None:
+            return None
+        w = np.asarray(weights, np.float64).reshape(-1)
+        if w.size != m:
+            raise ValueError(f"{w.size} weights for {m} frame pairs")
+        if not np.all(np.isfinite(w)):
+            raise ValueError("pair weights must be finite")
+        return w
+
+    def evaluate(self, idx_t, idx_tau, weights=None) -> dict:
         """Loss and score in evaluation mode over the pairs, in batches of batch_size, weighted by batch size
-        (_evaluate, trainer.py:1072-1101)."""
+        (_evaluate, trainer.py:1072-1101); with per-pair ``weights`` every batch's loss is the weighted one and the
+        batches are weighted by their total weight."""
         idx_t, idx_tau = np.asarray(idx_t, np.int64), np.asarray(idx_tau, np.int64)
+        weights = self._pair_weight_array(weights, idx_t.size)
         loss = score = 0.0
         weight = 0
-        for bt, btau in self._batches(idx_t, idx_tau, False):
-            res = self._call(bt, btau, False)
-            loss += res["loss"] * bt.size
-            score += res["score"] * bt.size
-            weight += bt.size
+        for bt, btau, bw, share in self._batches(idx_t, idx_tau, False, weights):
+            res = self._call(bt, btau, False) if bw is None else self._call(bt, btau, False, bw)
+            loss += res["loss"] * share
+            score += res["score"] * share
+            weight += share
         if weight == 0:
             return {"loss": 0.0, "score": 0.0}
         return {"loss": loss / float(weight), "score": score / float(weight)}
 
     # -- the curriculum -------------------------------------------------------
-    def fit(self, sequences: Sequence[np.ndarray], val_sequences: Optional[Sequence[np.ndarray]] = None) -> dict:
-        """Train the model in place and return the history (also attached to model.training_history)."""
+    @staticmethod
+    def _frame_weight_arrays(weights, sequences, what: str):
+        if weights is None:
+            return None
+        out = [np.asarray(w, np.float64).reshape(-1) for w in weights]
+        if len(out) != len(sequences) or any(w.size != a.shape[0] for w, a in zip(out, sequences)):
+            raise ValueError(f"{what} must hold one 1-D array per sequence, one weight per frame")
+        if any(not np.all(np.isfinite(w)) for w in out):
+            raise ValueError(f"{what} must be finite")
+        return out
+
+    def fit(self, sequences: Sequence[np.ndarray], val_sequences: Optional[Sequence[np.ndarray]] = None,
+            frame_weights: Optional[Sequence[np.ndarray]] = None,
+            val_frame_weights: Optional[Sequence[np.ndarray]] = None) -> dict:
+        """Train the model in place and return the history (also attached to model.training_history).
+        ``frame_weights``: one 1-D array of per-frame weights per training sequence; the weight of a pair is that
+        of its t frame, and the loss of every batch is the weighted one.  With the time split the validation part
+        takes the tail of each sequence's weights; with ``val_sequences`` the validation pairs are weighted by
+        ``val_frame_weights`` (uniformly when it is None).  The history then also has weighted_loss and
+        effective_pairs_curve (per epoch, the mean over its batches of Kish's effective number of pairs)."""
         cfg = self.cfg
         train = [np.asarray(s, np.float32) for s in sequences]
         if not train:
             raise ValueError("at least one training sequence is required")
         if any(a.ndim != 2 for a in train):
             raise ValueError("training sequences must all be 2-D arrays")
+        w_train = self._frame_weight_arrays(frame_weights, train, "frame_weights")
         if val_sequences is None:
+            if val_frame_weights is not None:
+                raise ValueError("val_frame_weights needs val_sequences: the time split takes the tail of frame_weights")
             max_tau = max([*cfg.tau_schedule, int(cfg.val_tau)])
             cuts = split_train_val([a.shape[0] for a in train], max_tau, cfg.val_fraction)
             val = [a[c:] for a, c in zip(train, cuts) if c is not None]
+            w_val = None
+            if w_train is not None:
+                w_val = [w[c:] for w, c in zip(w_train, cuts) if c is not None]
+                w_train = [w[:c] for w, c in zip(w_train, cuts) if c is not None]
             train = [a[:c] for a, c in zip(train, cuts) if c is not None]
             if not train:
                 raise ValueError("no training data remained after splitting by time")
@@ -310,8 +373,13 @@ class DeepTICACurriculumTrainer:
             val = [np.asarray(s, np.float32) for s in val_sequences]
             if any(a.ndim != 2 for a in val):
                 raise ValueError("validation sequences must all be 2-D arrays")
+            w_val = self._frame_weight_arrays(val_frame_weights, val, "val_frame_weights")
         if not val:
             raise ValueError("validation sequences are empty after splitting")
+        weighted = w_train is not None or w_val is not None
+        for name, parts in (("frame_weights", w_train), ("the validation part's frame weights", w_val)):
+            if parts is not None and not any(np.any(w > 0.0) for w in parts):
+                raise ValueError(f"{name} carry no positive weight")
         # one upload: the training sequences back to back, then the validation sequences
         n_train = sum(a.shape[0] for a in train)
         self.set_frames(np.concatenate(train + val, axis=0))
@@ -320,6 +388,10 @@ class DeepTICACurriculumTrainer:
         self.val_pairs = lagged_pairs(val_lengths, cfg.val_tau, val_offsets)[:2]
         if self.val_pairs[0].size == 0:
             raise ValueError("validation dataset is empty - ensure val_tau is compatible with sequence lengths")
+        # the weight of a pair is the weight of its t frame, looked up by row of the resident array
+        wt_rows = np.concatenate(w_train) if w_train is not None else None
+        self.val_pair_weights = np.concatenate(w_val)[self.val_pairs[0] - n_train] if w_val is not None else None
+        effective_curve: list[float] = []
         blocks = [(int(tau), *lagged_pairs([a.shape[0] for a in train], tau)) for tau in cfg.tau_schedule]
         planned = sum(int(cfg.epochs_per_tau) for _, it, _, _ in blocks if it.size)
         self._schedule = lr_schedule(self._base_lr, cfg.warmup_epochs, planned)
@@ -342,12 +414,15 @@ class DeepTICACurriculumTrainer:
                 lr = self._current_lr = self._schedule[self._epoch] if self._schedule else self._base_lr
                 self._epoch += 1
                 sums = _EpochSums()
-                for b, (bt, btau) in enumerate(self._batches(idx_t, idx_tau, bool(cfg.shuffle))):
+                pair_w = wt_rows[idx_t] if wt_rows is not None else None
+                for b, (bt, btau, bw, share) in enumerate(self._batches(idx_t, idx_tau, bool(cfg.shuffle), pair_w)):
                     if cfg.max_batches_per_epoch is not None and b >= int(cfg.max_batches_per_epoch):
                         break
-                    sums.update(self.train_step(bt, btau), bt.size)
+                    sums.update(self.train_step(bt, btau, bw), share)
                 tm = sums.finalize()
-                vm = self.evaluate(*self.val_pairs)
+                vm = self.evaluate(*self.val_pairs, self.val_pair_weights)
+                if weighted:
+                    effective_curve.append(float(np.mean(sums.effective)) if sums.effective else math.nan)
                 overall_epoch = len(overall["epochs"]) + 1
                 row = {"epochs": overall_epoch, "train_loss": tm["loss"], "train_score": tm["score"],
                        "val_loss": vm["loss"], "val_score": vm["score"], "learning_rate": float(lr),
@@ -367,6 +442,9 @@ class DeepTICACurriculumTrainer:
             self._params.copy_from_host(self._best_state)
         self.model.spec.params = self._params.to_host()
         history = self._build_history(per_tau, overall, start)
+        if weighted:
+            history["weighted_loss"] = True
+            history["effective_pairs_curve"] = effective_curve
         self.grad_norm_curve = list(overall["grad_norm_mean"])
         self.history = history
         if isinstance(self.model.training_history, dict):
