@@ -194,10 +194,12 @@ msm_status msm_featurize_spec_vjp(msm_ctx* ctx, const float* d_xyz, int64_t n, i
  *         d_points float32 [P, 3] = the unit sphere points (golden spiral), fp32 throughout.
  *   hbond presence: for every (donor, hydrogen, acceptor) row of d_triplets int32 [Tn, 3] the number of frames with
  *         |H - A| < dist_cutoff and angle(D, H, A) > angle_cutoff (radians), the two criteria of
- *         mdtraj.baker_hubbard (geometry/hbond.py); the frequency threshold is the caller's.
+ *         mdtraj.baker_hubbard (geometry/hbond.py); the frequency threshold is the caller's.  A triplet without an
+ *         angle in a frame (D = H or H = A there) is absent in it, as in mdtraj.
  *   dssp: Kabsch-Sander secondary structure per frame and residue (mdtraj.compute_dssp, geometry/src/dssp.cpp):
  *         d_backbone int32 [R, 4] = atom indices of N, CA, C, O of each protein residue, d_chain int32 [R],
- *         d_proline uint8 [R]; d_codes uint8 [n, R]: 0 loop, 1 H, 2 B, 3 E, 4 G, 5 I, 6 T, 7 S. */
+ *         d_proline uint8 [R]; d_codes uint8 [n, R]: 0 loop, 1 H, 2 B, 3 E, 4 G, 5 I, 6 T, 7 S.  A row of
+ *         d_backbone that holds a -1 is a residue without a full backbone: never bonded, a chain break, code 0. */
 msm_status msm_featurize_sasa(msm_ctx* ctx, const float* d_xyz, int64_t n, int A, const float* d_radii,
                               const float* d_points, int P, float* d_out);
 msm_status msm_hbond_presence(msm_ctx* ctx, const float* d_xyz, int64_t n, int A, const int32_t* d_triplets,

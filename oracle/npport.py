@@ -1296,13 +1296,22 @@ def baker_hubbard_presence(xyz, triplets, distance_cutoff=0.25, angle_cutoff=2.0
 
 def dssp_codes(xyz, backbone, chain, proline):
     """Kabsch-Sander assignment per frame and protein residue, uint8 (n_frames, R): 0 loop, 1 H, 2 B, 3 E, 4 G, 5 I,
-    6 T, 7 S.  dssp.cpp / DSSP 2.0 structure.cpp step by step (fp32 geometry in Angstrom)."""
+    6 T, 7 S.  dssp.cpp / DSSP 2.0 structure.cpp step by step (fp32 geometry in Angstrom).  A backbone row with a -1
+    is a residue without a full backbone, as csrc/structure.hip documents it: never a donor or an acceptor, no hydrogen
+    is placed from it, every stretch of residues across it counts as broken, and its code is 0."""
+    with np.errstate(invalid="ignore", divide="ignore"):     # a degenerate frame (coincident atoms) yields 0 / 0
+        return _dssp_codes(xyz, backbone, chain, proline)
+
+
+def _dssp_codes(xyz, backbone, chain, proline):
     xyz = np.asarray(xyz, np.float32)
     bb = np.asarray(backbone, int).reshape(-1, 4)
     chain = np.asarray(chain, int)
     proline = np.asarray(proline, bool)
     R = bb.shape[0]
     n = xyz.shape[0]
+    full = (bb >= 0).all(axis=1)
+    bb = np.where(bb >= 0, bb, 0)          # rows that are not full are never read below
     out = np.zeros((n, R), np.uint8)
     f32 = np.float32
 
@@ -1315,14 +1324,14 @@ def dssp_codes(xyz, backbone, chain, proline):
         N, CA, C, O = (fr[bb[:, k]] for k in range(4))
         H = N.copy()
         for r in range(1, R):
-            if not proline[r] and chain[r - 1] == chain[r]:
+            if not proline[r] and chain[r - 1] == chain[r] and full[r] and full[r - 1]:
                 H[r] = N[r] + (C[r - 1] - O[r - 1]) / dist(C[r - 1], O[r - 1])
 
         def no_break(a, b):
             for r in range(a, b):
-                if chain[r] != chain[r + 1] or dist(C[r], N[r + 1]) > f32(2.5):
+                if chain[r] != chain[r + 1] or not full[r] or not full[r + 1] or dist(C[r], N[r + 1]) > f32(2.5):
                     return False
-            return True
+            return bool(full[a] and full[b])
 
         acc = [[-1, -1] for _ in range(R)]
         en = [[f32(0.0), f32(0.0)] for _ in range(R)]
@@ -1332,7 +1341,7 @@ def dssp_codes(xyz, backbone, chain, proline):
             if not proline[donor]:
                 dHO, dHC = dist(H[donor], O[acceptor]), dist(H[donor], C[acceptor])
                 dNC, dNO = dist(N[donor], C[acceptor]), dist(N[donor], O[acceptor])
-                if min(dHO, dHC, dNC, dNO) < f32(0.5):
+                if dHO < f32(0.5) or dHC < f32(0.5) or dNC < f32(0.5) or dNO < f32(0.5):   # as dssp.cpp: a NaN is no hit
                     res = f32(-9.9)
                 else:
                     k = f32(27.888)
@@ -1347,8 +1356,10 @@ def dssp_codes(xyz, backbone, chain, proline):
                 acc[donor][1], en[donor][1] = acceptor, res
 
         for i in range(R - 1):
+            if not full[i]:
+                continue
             for j in range(i + 1, R):
-                if dist(CA[i], CA[j]) < f32(9.0):
+                if full[j] and dist(CA[i], CA[j]) < f32(9.0):
                     energy(i, j)
                     if j != i + 1:
                         energy(j, i)

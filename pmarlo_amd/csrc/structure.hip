@@ -16,6 +16,9 @@ constexpr int kMaxNbr = 384;   // neighbours of one atom within R_i + R_j (probe
 struct F3 { float x, y, z; };
 __device__ __forceinline__ F3 ld3(const float* p) { return {p[0], p[1], p[2]}; }
 __device__ __forceinline__ float dot3(F3 a) { return a.x * a.x + a.y * a.y + a.z * a.z; }   // (x x + y y) + z z
+// np.clip as mdtraj applies it before arccos: a NaN (the 0 / 0 of a degenerate triplet or bend) stays NaN, so that the
+// comparison that follows is false and the bond or bend counts as absent.  fminf(fmaxf()) would turn it into -1.
+__device__ __forceinline__ float clamp_keep_nan(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // ---------------------------------------------------------------------------------------------------------
 // Shrake-Rupley.  One wave per (frame, atom): neighbours j with |r_i - r_j|^2 < (R_i + R_j)^2 are compacted into the
@@ -109,7 +112,7 @@ __global__ __launch_bounds__(kSThreads) void hbond_presence_kernel(const float* 
             const float aa = dist3(fr + 3 * d, fr + 3 * h);          // D - H
             const float cc = dist3(fr + 3 * a, fr + 3 * d);          // A ... D
             float cosv = (aa * aa + b * b - cc * cc) / (2.0f * aa * b);
-            cosv = fminf(fmaxf(cosv, -1.0f), 1.0f);
+            cosv = clamp_keep_nan(cosv, -1.0f, 1.0f);                // D = H or H = A: 0 / 0, no angle, no bond
             if (acosf(cosv) > acut) ++c;
         }
         if (c) atomicAdd(&counts[q], (unsigned long long)c);
@@ -134,7 +137,7 @@ struct DsspWork {
     unsigned char* hflag;          // [3][R][n]: helix flags of stride 3, 4, 5
     unsigned char* bend;           // [R][n]
     unsigned char* ss;             // [R][n]
-    int* lad;                      // ladders: [6][R][n]: i_first, i_last, j_first, j_last, type, alive
+    int* lad;                      // ladders: [6][2 R][n]: i_first, i_last, j_first, j_last, type, alive
     float* hpos;                   // [3][R][n]: amide hydrogen positions (Angstrom)
 };
 
@@ -211,7 +214,15 @@ __global__ __launch_bounds__(64) void dssp_kernel(const float* __restrict__ xyz,
     // ---- beta bridges -> ladders (sheets need not be numbered for the codes)
     for (int r = 0; r < R; ++r) w.ss[IX(r)] = SS_LOOP;
     int n_lad = 0;
-    auto L = [&](int field, int l) -> int& { return w.lad[((int64_t)field * R + l) * n + t]; };
+    // At most 2 R ladders exist.  bond(d, a) holds only for the two best acceptors of d, so there are at most 2 R bonds.
+    // Each of the four bridge patterns of (i, j), i < j, uses one bond with donor > acceptor and one with donor <
+    // acceptor.  A bond d > a serves only (a + 1, d) and (a, d - 1) as the parallel patterns' and (a, d) and
+    // (a + 1, d - 1) as the antiparallel patterns'; the two of a type are consecutive (i + 1 with j + 1, or j - 1), so
+    // the later one extends the ladder of the earlier one: a bond opens at most one ladder per type.  The same holds
+    // for the bonds d < a, and the smaller of the two sets has at most R bonds: at most 2 R ladders.  The guard on
+    // n_lad below therefore never drops a bridge; the oracle, which has no limit, computes the same.
+    const int lad_cap = 2 * R;
+    auto L = [&](int field, int l) -> int& { return w.lad[((int64_t)field * lad_cap + l) * n + t]; };
     for (int i = 1; i + 4 < R; ++i) {
         for (int j = i + 3; j + 1 < R; ++j) {
             // TestBridge(i, j): a = i-1, b = i, c = i+1; d = j-1, e = j, f = j+1
@@ -231,7 +242,7 @@ __global__ __launch_bounds__(64) void dssp_kernel(const float* __restrict__ xyz,
                 if (type == 1 && L(3, l) + 1 == j) { L(1, l) = i; L(3, l) = j; found = true; }
                 else if (type == 2 && L(2, l) - 1 == j) { L(1, l) = i; L(2, l) = j; found = true; }
             }
-            if (!found && n_lad < R) {
+            if (!found && n_lad < lad_cap) {
                 L(0, n_lad) = i; L(1, n_lad) = i; L(2, n_lad) = j; L(3, n_lad) = j; L(4, n_lad) = type; L(5, n_lad) = 1;
                 ++n_lad;
             }
@@ -286,7 +297,7 @@ __global__ __launch_bounds__(64) void dssp_kernel(const float* __restrict__ xyz,
         const F3 a = at(i - 2, 1), b = at(i, 1), c = at(i + 2, 1);
         const F3 u = {b.x - a.x, b.y - a.y, b.z - a.z}, v = {c.x - b.x, c.y - b.y, c.z - b.z};
         const float ck = (u.x * v.x + u.y * v.y + u.z * v.z) / (sqrtf(dot3(u)) * sqrtf(dot3(v)));
-        const float kappa = acosf(fminf(fmaxf(ck, -1.0f), 1.0f)) * 57.29577951308232f;
+        const float kappa = acosf(clamp_keep_nan(ck, -1.0f, 1.0f)) * 57.29577951308232f;
         w.bend[IX(i)] = kappa > 70.0f ? 1 : 0;
     }
     auto is_start = [&](int r, int s) { const unsigned char f = HF(s, r); return f == HX_START || f == HX_BOTH; };
@@ -378,8 +389,10 @@ msm_status msm_dssp(msm_ctx* ctx, const float* d_xyz, int64_t n, int A, const in
     if (n == 0 || R == 0) return MSM_OK;
     MSM_REQUIRE(ctx, d_xyz && d_backbone && d_chain && d_proline && d_codes, "msm_dssp: NULL pointer");
     // work arrays, frames in chunks so that the scratch stays bounded
-    const size_t per_frame = (size_t)R * (2 * sizeof(int) + 5 * sizeof(float) + 3 + 1 + 1 + 6 * sizeof(int)) + 128;
-    const int64_t chunk = std::max<int64_t>(64, std::min<int64_t>(n, (int64_t)((256u << 20) / per_frame) / 64 * 64));
+    const size_t per_frame = (size_t)R * (2 * sizeof(int) + 5 * sizeof(float) + 3 + 1 + 1 + 12 * sizeof(int)) + 128;
+    int64_t chunk = std::max<int64_t>(64, std::min<int64_t>(n, (int64_t)((256u << 20) / per_frame) / 64 * 64));
+    if (const char* e = getenv("MSM_DSSP_CHUNK"))   // tests: several launches at small n (read by every call)
+        chunk = std::min<int64_t>(chunk, (std::max<int64_t>(64, std::min<int64_t>(atoi(e), 1 << 30)) + 63) / 64 * 64);
     msm_status rs = msm_reserve_scratch(ctx, (size_t)chunk * per_frame + 256);
     if (rs != MSM_OK) return rs;
     for (int64_t t0 = 0; t0 < n; t0 += chunk) {
@@ -391,7 +404,7 @@ msm_status msm_dssp(msm_ctx* ctx, const float* d_xyz, int64_t n, int A, const in
         w.acc1 = (int*)take((size_t)R * m * sizeof(int));
         w.e0 = (float*)take((size_t)R * m * sizeof(float));
         w.e1 = (float*)take((size_t)R * m * sizeof(float));
-        w.lad = (int*)take((size_t)6 * R * m * sizeof(int));
+        w.lad = (int*)take((size_t)12 * R * m * sizeof(int));
         w.hpos = (float*)take((size_t)3 * R * m * sizeof(float));
         w.hflag = (unsigned char*)take((size_t)3 * R * m);
         w.bend = (unsigned char*)take((size_t)R * m);

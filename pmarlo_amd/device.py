@@ -433,14 +433,15 @@ class Engine:
         return counts.to_host().astype(np.int64)
 
     def dssp(self, xyz: DeviceArray, backbone, chain, proline) -> np.ndarray:
-        """Kabsch-Sander codes per frame and protein residue: uint8 [n, R] (0 loop, 1 H, 2 B, 3 E, 4 G, 5 I, 6 T, 7 S)."""
+        """Kabsch-Sander codes per frame and protein residue: uint8 [n, R] (0 loop, 1 H, 2 B, 3 E, 4 G, 5 I, 6 T, 7 S).
+        A backbone row that holds a -1 is a residue without a full backbone: never bonded, a chain break, code 0."""
         n, A, _ = xyz.shape
         bb = np.ascontiguousarray(backbone, np.int32).reshape(-1, 4)
         R = bb.shape[0]
         if R == 0 or n == 0:
             return np.zeros((n, R), np.uint8)
-        if bb.min() < 0 or bb.max() >= A:
-            raise ValueError(f"atom index out of range [0, {A})")
+        if bb.min() < -1 or bb.max() >= A:
+            raise ValueError(f"atom index out of range [0, {A}) (-1: atom missing)")
         bd = self.to_device(bb)
         cd = self.to_device(np.ascontiguousarray(chain, np.int32).reshape(R))
         pd_ = self.to_device(np.ascontiguousarray(proline, np.uint8).reshape(R))
