@@ -289,8 +289,31 @@ msm_status msm_count_transitions_lagscan(msm_ctx* ctx, const int32_t* d_labels, 
                                          int n_seg, const int32_t* h_lags, int n_lag, int k,
                                          int64_t* d_counts, int64_t* d_pairs);
 
+/* Which kernels a count of `total_pairs` pairs (the pair positions of all segments, valid labels or not) over k states
+ * would run on this context NOW: a read-only query of the one dispatch function the four calls above go through.  It
+ * launches and allocates nothing.  The answer depends on the device's CU count, on the MSM_COUNTS_CHUNK and
+ * MSM_COUNTS_BUCKETS environment variables and, while a capture is active, on the auxiliary scratch the context
+ * already holds (a capture cannot grow it: the privatised kernel runs instead of the bucket path).
+ *   out[0] = MSM_COUNT_PATH_*
+ *   BUCKET:      out[1] = R (rows of a bucket), out[2] = buckets, out[3] = chunk (pairs of a first-pass workgroup),
+ *                out[4] = chunks, out[5] = copies of a bucket's bins, out[6] = 1 if msm_count_transitions_normalised
+ *                normalises in the counting launch (it still needs k doubles of scratch for the diagonal, which a
+ *                capture cannot grow either)
+ *   PRIVATISED:  out[1] = rows of a row block, out[2] = row_blocks, out[3] = chunks, out[4] = pairs_per_chunk,
+ *                out[5] = lds_bytes
+ *   GLOBAL:      out[3] = chunks (workgroups)
+ *   NONE:        no pairs, the outputs are only cleared
+ * Entries not named are zero.  weighted != 0: msm_count_transitions_weighted. */
+#define MSM_COUNT_PATH_BUCKET 0
+#define MSM_COUNT_PATH_PRIVATISED 1
+#define MSM_COUNT_PATH_GLOBAL 2
+#define MSM_COUNT_PATH_NONE 3
+msm_status msm_count_transitions_plan(msm_ctx* ctx, int k, int64_t total_pairs, int weighted, int64_t out[8]);
+
 /* Visits per state: np.bincount(labels[0<=l<k], minlength=k)
- * (S/analysis/discretize.py:648-667, weights=None).  d_visits int64 [k]. */
+ * (S/analysis/discretize.py:648-667, weights=None).  d_visits int64 [k].  Up to MSM_STATE_COUNTS_LDS_MAX_K states a
+ * workgroup bins in its LDS; above, every frame is one global atomic. */
+#define MSM_STATE_COUNTS_LDS_MAX_K 16384
 msm_status msm_state_counts(msm_ctx* ctx, const int32_t* d_labels, int64_t n, int k,
                             int64_t* d_visits);
 
@@ -757,7 +780,10 @@ msm_status msm_kmeans_fit(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_
  * max |z| in d_state[2]) this replaces the k centres by frames drawn with probability proportional to the squared
  * distance to the nearest centre already drawn.  Integer weights and splitmix64 draws (csrc/kmeanspp.hip): the
  * frames drawn are a function of the data and the seed alone, and oracle/npport.kmeans_plusplus repeats them bit
- * for bit.  d_picked (int64 [k], may be NULL) receives the frame numbers. */
+ * for bit.  d_picked (int64 [k], may be NULL) receives the frame numbers.  The weights are summed per block of
+ * MSM_KPP_BLOCK frames; the one workgroup that draws gives each of its MSM_KPP_BLOCK threads
+ * ceil(blocks / MSM_KPP_BLOCK) consecutive block sums. */
+#define MSM_KPP_BLOCK 1024
 msm_status msm_kmeans_init_plusplus(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n, int d, int64_t ld,
                                     const double* d_mean, const double* d_std, int k, uint64_t seed, double n_total,
                                     double* d_centers, const double* d_state, int64_t* d_picked);
@@ -1064,7 +1090,8 @@ msm_status msm_diff_norms(msm_ctx* ctx, const double* d_P, int64_t ldp, const do
 /* Exact order statistics: h_out[q] = the h_ranks[q]-th smallest (0-based) of the n strided samples, by radix
  * selection on the order-preserving integer image of the doubles (six 12-bit histogram passes per rank; no
  * sort).  Feeds the quantile rules of the free-energy grids (mquantiles / iqr in generate_2d_fes,
- * S/markov_state_model/free_energy.py:494-590) and medians.  Samples must not be NaN.  Polls the host
+ * S/markov_state_model/free_energy.py:494-590) and medians.  NaN samples of either sign sort last, as in np.sort (a
+ * rank among them returns a NaN); -0.0 sorts before +0.0.  Polls the host
  * between passes: synchronises the stream, cannot be captured. */
 msm_status msm_order_statistics(msm_ctx* ctx, const double* d_x, int64_t stride, int64_t n, const int64_t* h_ranks,
                                 int n_ranks, double* h_out);

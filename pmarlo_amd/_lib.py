@@ -38,6 +38,10 @@ PATHWAYS_RUNNING, PATHWAYS_FRACTION, PATHWAYS_NO_PATH, PATHWAYS_MAXITER = range(
 # effective counts (MSM_EFF_* in include/msmhip.h): lags of a block, blocks a launch takes by default, averages
 EFF_LAG_BLOCK, EFF_BLOCKS_PER_LAUNCH = 256, 8
 EFF_AVERAGE_ROW, EFF_AVERAGE_ALL, EFF_AVERAGE_NONE = range(3)
+# count dispatch (MSM_COUNT_PATH_* in include/msmhip.h), the largest k msm_state_counts bins in the LDS
+# (MSM_STATE_COUNTS_LDS_MAX_K), frames per block sum of the k-means++ draw (MSM_KPP_BLOCK)
+COUNT_PATH_BUCKET, COUNT_PATH_PRIVATISED, COUNT_PATH_GLOBAL, COUNT_PATH_NONE = range(4)
+STATE_COUNTS_LDS_MAX_K, KPP_BLOCK = 16384, 1024
 # msm_mlp_forward's envelope: widest layer, most outputs, most Linear layers
 MLP_MAX_WIDTH, MLP_MAX_OUT, MLP_MAX_LINEAR = 256, 64, 8
 # msm_vamp2_loss's stats block (MSM_VAMP2_STATS): 16 scalars, then var_z0, var_zt, mean_z0, mean_zt of 64 entries
@@ -95,6 +99,7 @@ _PROTOTYPES: dict[str, tuple] = {
     "msm_count_transitions_weighted": (
         _i32, [_vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "msm_count_transitions_lagscan": (_i32, [_vp, _vp, _i64, _vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp]),
+    "msm_count_transitions_plan": (_i32, [_vp, _i32, _i64, _i32, _vp]),
     "msm_state_counts": (_i32, [_vp, _vp, _i64, _i32, _vp]),
     "msm_column_moments_partial": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _vp, _vp]),
     "msm_moments_finalize": (_i32, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),

@@ -396,7 +396,7 @@ __global__ __launch_bounds__(kThreads) void state_counts_kernel(
     const int32_t* __restrict__ labels, int64_t n, int k, unsigned long long* __restrict__ visits) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     unsigned int* bins = reinterpret_cast<unsigned int*>(smem_raw);
-    const bool use_lds = k <= 16384;
+    const bool use_lds = k <= MSM_STATE_COUNTS_LDS_MAX_K;
     if (use_lds) {
         for (int i = threadIdx.x; i < k; i += kThreads) bins[i] = 0;
         __syncthreads();
@@ -424,16 +424,57 @@ bool count_buckets_enabled() {
     return on;
 }
 
+// The decision launch_counts makes, in one place (msm_count_transitions_plan reports it).
 struct CountPlan {
-    bool global_path;
+    int path;                 // MSM_COUNT_PATH_*
+    // bucket path
+    int R, buckets, chunk, chunks_b, slots, copies;
+    bool can_fuse;            // the second pass can also normalise its rows
+    size_t elem_bytes, aux_need;
+    // privatised / global path
     int rows, row_blocks, chunks;
     size_t lds_bytes;
     int64_t pairs_per_chunk;
 };
 
-CountPlan plan_counts(const msm_ctx* ctx, int k, int64_t total_pairs, size_t bin_bytes) {
+CountPlan plan_counts(const msm_ctx* ctx, int k, int64_t total_pairs, bool weighted) {
     CountPlan pl{};
-    const size_t row_bytes = (size_t)k * bin_bytes;
+    if (!weighted) {
+        // dense regime, a bucket of rows fits the LDS: two passes without global atomics (see count_bucket_*)
+        const int R = msm_ceil_div(k, kBucketsMax), buckets = msm_ceil_div(k, R);
+        const size_t bin_bytes = (size_t)R * k * sizeof(unsigned int);
+        if (count_buckets_enabled() && bin_bytes <= (size_t)kBinCopiesBytes && total_pairs >= (int64_t)k * k &&
+            total_pairs < ((int64_t)1 << 31)) {
+            int chunk = (int)std::min<int64_t>(kChunkMax, std::max<int64_t>(2048, msm_ceil_div(total_pairs, ctx->n_cu)));
+            if (const char* e = getenv("MSM_COUNTS_CHUNK")) chunk = std::max(64, std::min(kChunkMax, atoi(e)));   // tests: many chunks at small n
+            chunk = (chunk + 63) & ~63;
+            const int chunks = msm_ceil_div(total_pairs, chunk);
+            int slots = 128;
+            while (slots < 2 * chunk) slots *= 2;
+            const size_t elem_bytes = ((size_t)chunks * chunk * sizeof(unsigned short) + 255) & ~(size_t)255;
+            const size_t need = elem_bytes + (size_t)(buckets + 2) * chunks * sizeof(unsigned int);
+            if (!(ctx->capturing && need > ctx->aux_bytes)) {      // (a capture cannot grow the scratch: privatised kernel)
+                int copies = 1;
+                while (copies < kThreads / 64 && (size_t)2 * copies * bin_bytes <= (size_t)kBinCopiesBytes) copies *= 2;
+                pl.path = MSM_COUNT_PATH_BUCKET;
+                pl.R = R;
+                pl.buckets = buckets;
+                pl.chunk = chunk;
+                pl.chunks_b = chunks;
+                pl.slots = slots;
+                pl.copies = copies;
+                pl.can_fuse = R <= kNormRowsMax;
+                pl.elem_bytes = elem_bytes;
+                pl.aux_need = need;
+                return pl;
+            }
+        }
+    }
+    if (total_pairs == 0) {
+        pl.path = MSM_COUNT_PATH_NONE;
+        return pl;
+    }
+    const size_t row_bytes = (size_t)k * (weighted ? sizeof(double) : sizeof(unsigned int));
     size_t budget = (row_bytes * k <= (size_t)kLdsBudgetSmall) ? kLdsBudgetSmall : kLdsBudgetLarge;
     int rows = (int)(budget / row_bytes);
     if (rows > k) rows = k;
@@ -441,12 +482,12 @@ CountPlan plan_counts(const msm_ctx* ctx, int k, int64_t total_pairs, size_t bin
     rows = 0;
 #endif
     if (rows < 1 || msm_ceil_div(k, rows) > kMaxRowBlocks) {
-        pl.global_path = true;
+        pl.path = MSM_COUNT_PATH_GLOBAL;
         pl.chunks = (int)std::min<int64_t>(std::max<int64_t>(1, msm_ceil_div(total_pairs, kThreads * 8)),
                                            (int64_t)ctx->n_cu * 8);
         return pl;
     }
-    pl.global_path = false;
+    pl.path = MSM_COUNT_PATH_PRIVATISED;
     pl.row_blocks = msm_ceil_div(k, rows);
     pl.rows = msm_ceil_div(k, pl.row_blocks);  // balance the blocks
     pl.lds_bytes = (size_t)pl.rows * row_bytes;
@@ -467,56 +508,42 @@ msm_status launch_counts(msm_ctx* ctx, const int32_t* d_labels, const double* d_
     // norm: the bucket path also leaves the row-normalised matrix (*normalised tells whether it did; every other path
     // leaves that to the caller)
     using out_t = typename BinT<WEIGHTED>::out_t;
-    using lds_t = typename BinT<WEIGHTED>::lds_t;
     if (normalised) *normalised = false;
+    const CountPlan pl = plan_counts(ctx, k, st.total_pairs, WEIGHTED);
     if constexpr (!WEIGHTED) {
-        // dense regime, a bucket of rows fits the LDS: two passes without global atomics (see count_bucket_*)
-        const int R = msm_ceil_div(k, kBucketsMax), buckets = msm_ceil_div(k, R);
-        const size_t bin_bytes = (size_t)R * k * sizeof(unsigned int);
-        if (count_buckets_enabled() && bin_bytes <= (size_t)kBinCopiesBytes && st.total_pairs >= (int64_t)k * k &&
-            st.total_pairs < ((int64_t)1 << 31)) {
-            int chunk = (int)std::min<int64_t>(kChunkMax, std::max<int64_t>(2048, msm_ceil_div(st.total_pairs, ctx->n_cu)));
-            if (const char* e = getenv("MSM_COUNTS_CHUNK")) chunk = std::max(64, std::min(kChunkMax, atoi(e)));   // tests: many chunks at small n
-            chunk = (chunk + 63) & ~63;
-            const int chunks = msm_ceil_div(st.total_pairs, chunk);
-            int slots = 128;
-            while (slots < 2 * chunk) slots *= 2;
-            const size_t elem_bytes = ((size_t)chunks * chunk * sizeof(unsigned short) + 255) & ~(size_t)255;
-            const size_t need = elem_bytes + (size_t)(buckets + 2) * chunks * sizeof(unsigned int);
-            if (!(ctx->capturing && need > ctx->aux_bytes)) {      // (a capture cannot grow the scratch: privatised kernel)
-                msm_status rs = msm_reserve_aux(ctx, need);
-                if (rs != MSM_OK) return rs;
-                unsigned short* elems = (unsigned short*)ctx->aux;
-                unsigned int* offs = (unsigned int*)((char*)ctx->aux + elem_bytes);
-                unsigned int* valid = offs + (size_t)(buckets + 1) * chunks;
-                const size_t lds1 = (size_t)slots * 8 + (size_t)(2 * kBucketsMax + 2) * sizeof(unsigned int) + (size_t)chunk * 2;
-                if (lds1 > 48 * 1024)
-                    MSM_HIP(ctx, hipFuncSetAttribute((const void*)count_bucket_scatter_kernel,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-                hipLaunchKernelGGL(count_bucket_scatter_kernel, dim3(chunks), dim3(kThreads), lds1, ctx->stream, d_labels, st,
-                                   k, R, buckets, chunk, slots, elems, offs, valid);
-                int copies = 1;
-                while (copies < kThreads / 64 && (size_t)2 * copies * bin_bytes <= (size_t)kBinCopiesBytes) copies *= 2;
-                const size_t lds2 = (size_t)copies * bin_bytes + (size_t)(2 * kThreads + 1) * sizeof(unsigned int);
-                const bool fuse = norm && R <= kNormRowsMax;
-                auto kern = fuse ? count_bucket_bin_kernel<true> : count_bucket_bin_kernel<false>;
-                if (lds2 > 48 * 1024)
-                    MSM_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-                hipLaunchKernelGGL(kern, dim3(8 * ((buckets + 7) / 8)), dim3(kThreads), lds2, ctx->stream,
-                                   (const unsigned short*)elems, (const unsigned int*)offs, chunks, chunk, k, R, buckets, copies,
-                                   (unsigned long long*)d_counts, (const unsigned int*)valid, (unsigned long long*)d_pairs,
-                                   fuse ? *norm : RowNorm{});
-                MSM_CHECK_LAUNCH(ctx);
-                if (normalised) *normalised = fuse;
-                return MSM_OK;
-            }
+        if (pl.path == MSM_COUNT_PATH_BUCKET) {
+            const int R = pl.R, buckets = pl.buckets, chunk = pl.chunk, chunks = pl.chunks_b, slots = pl.slots;
+            const size_t bin_bytes = (size_t)R * k * sizeof(unsigned int);
+            msm_status rs = msm_reserve_aux(ctx, pl.aux_need);
+            if (rs != MSM_OK) return rs;
+            unsigned short* elems = (unsigned short*)ctx->aux;
+            unsigned int* offs = (unsigned int*)((char*)ctx->aux + pl.elem_bytes);
+            unsigned int* valid = offs + (size_t)(buckets + 1) * chunks;
+            const size_t lds1 = (size_t)slots * 8 + (size_t)(2 * kBucketsMax + 2) * sizeof(unsigned int) + (size_t)chunk * 2;
+            if (lds1 > 48 * 1024)
+                MSM_HIP(ctx, hipFuncSetAttribute((const void*)count_bucket_scatter_kernel,
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
+            hipLaunchKernelGGL(count_bucket_scatter_kernel, dim3(chunks), dim3(kThreads), lds1, ctx->stream, d_labels, st,
+                               k, R, buckets, chunk, slots, elems, offs, valid);
+            const int copies = pl.copies;
+            const size_t lds2 = (size_t)copies * bin_bytes + (size_t)(2 * kThreads + 1) * sizeof(unsigned int);
+            const bool fuse = norm && pl.can_fuse;
+            auto kern = fuse ? count_bucket_bin_kernel<true> : count_bucket_bin_kernel<false>;
+            if (lds2 > 48 * 1024)
+                MSM_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
+            hipLaunchKernelGGL(kern, dim3(8 * ((buckets + 7) / 8)), dim3(kThreads), lds2, ctx->stream,
+                               (const unsigned short*)elems, (const unsigned int*)offs, chunks, chunk, k, R, buckets, copies,
+                               (unsigned long long*)d_counts, (const unsigned int*)valid, (unsigned long long*)d_pairs,
+                               fuse ? *norm : RowNorm{});
+            MSM_CHECK_LAUNCH(ctx);
+            if (normalised) *normalised = fuse;
+            return MSM_OK;
         }
     }
     MSM_HIP(ctx, hipMemsetAsync(d_counts, 0, (size_t)k * k * sizeof(out_t), ctx->stream));
     if (d_pairs) MSM_HIP(ctx, hipMemsetAsync(d_pairs, 0, sizeof(int64_t), ctx->stream));
-    if (st.total_pairs == 0) return MSM_OK;
-    CountPlan pl = plan_counts(ctx, k, st.total_pairs, sizeof(lds_t));
-    if (pl.global_path) {
+    if (pl.path == MSM_COUNT_PATH_NONE) return MSM_OK;
+    if (pl.path == MSM_COUNT_PATH_GLOBAL) {
         hipLaunchKernelGGL(count_global_kernel<WEIGHTED>, dim3(pl.chunks), dim3(kThreads), 0, ctx->stream,
                            d_labels, d_weights, st, k, (out_t*)d_counts, (unsigned long long*)d_pairs);
     } else {
@@ -625,6 +652,31 @@ msm_status msm_count_transitions_weighted(msm_ctx* ctx, const int32_t* d_labels,
     return launch_counts<true>(ctx, d_labels, d_weights, st, k, d_counts, d_pairs);
 }
 
+msm_status msm_count_transitions_plan(msm_ctx* ctx, int k, int64_t total_pairs, int weighted, int64_t out[8]) {
+    if (!ctx) return MSM_ERR_INVALID;
+    MSM_REQUIRE(ctx, out && k >= 1 && k <= 46340 && total_pairs >= 0, "msm_count_transitions_plan: bad arguments");
+    const CountPlan pl = plan_counts(ctx, k, total_pairs, weighted != 0);
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    out[0] = pl.path;
+    if (pl.path == MSM_COUNT_PATH_BUCKET) {
+        out[1] = pl.R;
+        out[2] = pl.buckets;
+        out[3] = pl.chunk;
+        out[4] = pl.chunks_b;
+        out[5] = pl.copies;
+        out[6] = pl.can_fuse ? 1 : 0;
+    } else if (pl.path == MSM_COUNT_PATH_PRIVATISED) {
+        out[1] = pl.rows;
+        out[2] = pl.row_blocks;
+        out[3] = pl.chunks;
+        out[4] = pl.pairs_per_chunk;
+        out[5] = (int64_t)pl.lds_bytes;
+    } else if (pl.path == MSM_COUNT_PATH_GLOBAL) {
+        out[3] = pl.chunks;
+    }
+    return MSM_OK;
+}
+
 msm_status msm_count_transitions_lagscan(msm_ctx* ctx, const int32_t* d_labels, int64_t n,
                                          const int64_t* h_seg_start, const int64_t* h_seg_stop,
                                          int n_seg, const int32_t* h_lags, int n_lag, int k,
@@ -654,7 +706,7 @@ msm_status msm_state_counts(msm_ctx* ctx, const int32_t* d_labels, int64_t n, in
     if (n == 0) return MSM_OK;
     const int blocks = (int)std::min<int64_t>(std::max<int64_t>(1, msm_ceil_div(n, kThreads * 16)),
                                               (int64_t)ctx->n_cu * 2);
-    const size_t lds = k <= 16384 ? (size_t)k * sizeof(unsigned int) : 0;
+    const size_t lds = k <= MSM_STATE_COUNTS_LDS_MAX_K ? (size_t)k * sizeof(unsigned int) : 0;
     hipLaunchKernelGGL(state_counts_kernel, dim3(blocks), dim3(kThreads), lds, ctx->stream, d_labels, n, k,
                        (unsigned long long*)d_visits);
     MSM_CHECK_LAUNCH(ctx);

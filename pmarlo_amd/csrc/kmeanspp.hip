@@ -23,7 +23,7 @@
 
 namespace {
 
-constexpr int kBlock = 1024;   // frames per block sum
+constexpr int kBlock = MSM_KPP_BLOCK;   // frames per block sum
 
 __device__ __forceinline__ unsigned long long kpp_hash(unsigned long long seed, unsigned long long j) {
     unsigned long long h = (seed ^ 0x6B2B2B6B6D65616Eull) + 0x9E3779B97F4A7C15ull * (j + 1);   // splitmix64

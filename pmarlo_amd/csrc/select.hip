@@ -20,6 +20,8 @@ constexpr int kBins = 1 << kDigitBits;
 
 __device__ __forceinline__ unsigned long long sortable_key(double v) {
     const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    // every NaN sorts last, as np.sort has it: with the sign bit set (x86's inf - inf) the flipped bits would sort FIRST
+    if ((b & 0x7FFFFFFFFFFFFFFFull) > 0x7FF0000000000000ull) return ~0ull;
     return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
 

@@ -830,6 +830,25 @@ class Engine:
                                                 int(k), out.ptr, pairs.ptr), self.handle)
         return out, pairs
 
+    def count_plan(self, k: int, total_pairs: int, weighted: bool = False) -> dict:
+        """The kernels a count of `total_pairs` pair positions over k states would run on this engine now
+        (msm_count_transitions_plan, include/msmhip.h): {"path": "bucket" | "privatised" | "global" | "none", ...}
+        with the path's launch shape.  Launches nothing."""
+        import ctypes
+
+        out = (ctypes.c_int64 * 8)()
+        check(lib.msm_count_transitions_plan(self.handle, int(k), int(total_pairs), int(bool(weighted)), out), self.handle)
+        v = [int(x) for x in out]
+        if v[0] == _lib.COUNT_PATH_BUCKET:
+            return {"path": "bucket", "R": v[1], "buckets": v[2], "chunk": v[3], "chunks": v[4], "copies": v[5],
+                    "fuses_normalisation": bool(v[6])}
+        if v[0] == _lib.COUNT_PATH_PRIVATISED:
+            return {"path": "privatised", "rows": v[1], "row_blocks": v[2], "chunks": v[3], "pairs_per_chunk": v[4],
+                    "lds_bytes": v[5]}
+        if v[0] == _lib.COUNT_PATH_GLOBAL:
+            return {"path": "global", "chunks": v[3]}
+        return {"path": "none"}
+
     def effective_counts(self, labels: DeviceArray, k: int, lag: int, *, starts=None, stops=None, average: str = "row",
                          mact: float = 1.0, blocks_per_launch: int | None = None):
         """Effective count matrix at `lag` (msm_effective_counts, include/msmhip.h) -> (Ceff f64 [k, k], statistical

@@ -58,10 +58,13 @@ def test_weighted_integer_weights_exact(engine):
 
 
 @pytest.mark.parametrize("n,k,lag", [
-    (1_000_000, 500, 10),     # C3: row-blocked LDS path
-    (100_000, 100, 10),       # C2: single row block
-    (300_000, 200, 1),        # C4
-    (400_000, 2000, 10),      # C5: k too large for LDS rows -> global atomics
+    # (which kernels a shape runs: Engine.count_plan; tests/test_gpu_counts_paths.py asserts it case by case)
+    (1_000_000, 500, 10),     # C3: pairs >= k^2 -> two-pass bucket path, 2 rows per bucket
+    (100_000, 100, 10),       # C2: bucket path, 1 row per bucket
+    (300_000, 200, 1),        # C4: bucket path
+    (400_000, 2000, 10),      # C5: pairs < k^2 and more than 16 row blocks -> global atomics
+    # (1000, 3, 999) and (17, 20, 1): fewer pairs than bins -> the privatised LDS kernel, one chunk, no unrolled trip;
+    # the other three have no pair: the outputs are only cleared
     (1000, 3, 999), (1000, 3, 1000), (17, 20, 1), (1, 2, 1), (0, 4, 1)])
 def test_counts_vs_oracle_sizes(engine, n, k, lag):
     lab_h = _gen.markov_labels(n, k, seed=n % 97 + k) if n else np.zeros(0, np.int32)
