@@ -99,11 +99,19 @@ void msm_graph_destroy(msm_graph* g);
  *       mode 0: Q columns of radians
  *       mode 1: 2Q columns [cos_0, sin_0, cos_1, sin_1, ...]  (trig_expand_periodic,
  *               S/api/features.py:138-180)
- *       mode 2: 2Q columns [cos_0..cos_{Q-1} | sin_0..sin_{Q-1}] (_features.py:131-142) */
+ *       mode 2: 2Q columns [cos_0..cos_{Q-1} | sin_0..sin_{Q-1}] (_features.py:131-142)
+ * Non-finite coordinates follow the reference's torch operations (clamp_min and clamp keep NaN): a
+ * distance or an angle that reads a NaN coordinate is NaN; a dihedral that reads one is 0 (the
+ * extractor's mask |x| + |y| >= eps is false for NaN), i.e. (cos, sin) = (1, 0) in modes 1 and 2; a
+ * lone infinite coordinate gives a +inf distance, a NaN angle and a dihedral of 0; inf - inf is NaN.
+ * Records and frames that read no such coordinate are not affected. */
 msm_status msm_featurize_distances(msm_ctx* ctx, const float* d_xyz, int64_t n, int A,
                                    const int32_t* d_pairs, int P, float* d_out, int64_t ld, int col_off);
-/* contacts: 1.0 where the pair distance is <= rcut (nm), else 0.0 (NaN -> 0); Rg: radius of gyration
- * with unit masses, one column (S/features/builtins.py:89-108, 252-275). */
+/* contacts: 1.0 where the pair distance is <= rcut (nm), else 0.0; a NaN or infinite distance (a
+ * non-finite coordinate of either atom) is "no contact", 0.0, as in the reference, which sets NaN to
+ * inf before it compares.  Rg: radius of gyration with unit masses, one column, fp64 accumulation and
+ * one rounding to fp32; NaN for a frame with any non-finite coordinate
+ * (S/features/builtins.py:89-108, 252-275). */
 msm_status msm_featurize_contacts(msm_ctx* ctx, const float* d_xyz, int64_t n, int A,
                                   const int32_t* d_pairs, int P, float rcut, float* d_out,
                                   int64_t ld, int col_off);
@@ -688,8 +696,8 @@ msm_status msm_adamw_step(msm_ctx* ctx, float* d_params, const double* d_grad, d
  * (msm_featurize_spec) -> scaler and network -> E = strength * sum cv^2, and the force -dE/dx on every atom.
  *   Three plain launches on the context's stream -- msm_featurize_spec, msm_mlp_vjp with d_gout = NULL,
  *   msm_featurize_spec_vjp with sign = -1 -- no host synchronisation, capturable; n = 1 is one MD step.  The
- *   features are msm_featurize_spec's bits, except that a record reading a non-finite coordinate gives NaN (that
- *   function's floors and clamps turn such a coordinate into a finite value).
+ *   features are msm_featurize_spec's bits, except that a record reading a non-finite coordinate gives NaN (in that
+ *   function a dihedral or a contact of a NaN coordinate is 0 and a lone infinite coordinate is a +inf distance).
  *   The table has n_rec records and its width is the network's F = h_widths[0]; every column in [0, F) must be
  *   written by a record (a column no record writes would be read uninitialised).  d_inc_ptr / d_inc: the table's
  *   incidence (msm_featurize_spec_vjp).  d_energy [n], d_cv [n, ldo] or NULL (the raw network outputs), d_force

@@ -439,6 +439,24 @@ def angles(xyz, triplets, eps=1e-12):
     return np.arccos(np.clip(dot / (n1 * n2), -1.0, 1.0)).astype(np.float32)
 
 
+def contacts(xyz, pairs, rcut, eps=1e-12):
+    """S/features/builtins.py:252-275 on `distances`: NaN (missing coordinates) -> inf, then d <= rcut."""
+    d = distances(xyz, pairs, eps)
+    d = np.where(np.isfinite(d), d, np.float32(np.inf))
+    return (d <= np.float32(rcut)).astype(np.float32)
+
+
+def rg(xyz):
+    """Radius of gyration with unit masses (mdtraj.compute_rg as called at S/features/builtins.py:98), float64
+    arithmetic on the fp32 coordinates, one rounding; a frame with any non-finite coordinate is NaN."""
+    x = np.asarray(xyz, dtype=np.float32).astype(np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        c = x - x.mean(axis=1, keepdims=True)
+        out = np.sqrt((c * c).sum(axis=2).mean(axis=1))
+    out[~np.isfinite(x).all(axis=(1, 2))] = np.nan
+    return out.astype(np.float32)
+
+
 def wrap_to_minus_pi_pi(a):
     """S/features/builtins.py:11-14."""
     w = ((a + np.pi) % (2 * np.pi)) - np.pi

@@ -20,22 +20,26 @@ namespace {
 constexpr int kThreads = 256;
 
 // the three geometries on bond vectors (pbc.h has V3 and kEps); every kernel below goes through these, so a
-// minimum-image vector and a plain difference meet the same operations in the same order
-__device__ __forceinline__ float distance_of(V3 v) { return sqrtf(fmaxf(dot(v, v), kEps)); }
+// minimum-image vector and a plain difference meet the same operations in the same order.  The floor and the clamp
+// are comparisons, not fmaxf / fminf, which return the operand that is not NaN: a NaN coordinate stays NaN, as with
+// torch.clamp_min / torch.clamp in the reference (finite input: the same bits either way).
+__device__ __forceinline__ float floor_keep_nan(float q) { return q < kEps ? kEps : q; }
+__device__ __forceinline__ float clamp_keep_nan(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+__device__ __forceinline__ float distance_of(V3 v) { return sqrtf(floor_keep_nan(dot(v, v))); }
 
 __device__ __forceinline__ float angle_of(V3 v1, V3 v2) {
-    const float n1 = sqrtf(fmaxf(dot(v1, v1), kEps));
-    const float n2 = sqrtf(fmaxf(dot(v2, v2), kEps));
-    float c = dot(v1, v2) / (n1 * n2);
-    c = fminf(fmaxf(c, -1.0f), 1.0f);
-    return acosf(c);
+    const float n1 = sqrtf(floor_keep_nan(dot(v1, v1)));
+    const float n2 = sqrtf(floor_keep_nan(dot(v2, v2)));
+    const float c = dot(v1, v2) / (n1 * n2);
+    return acosf(clamp_keep_nan(c, -1.0f, 1.0f));
 }
 
 __device__ __forceinline__ float dihedral_of(V3 b0, V3 b1, V3 b2) {
     V3 c0 = cross(b0, b1), c1 = cross(b1, b2);
-    const float n0 = sqrtf(fmaxf(dot(c0, c0), kEps));
-    const float n1 = sqrtf(fmaxf(dot(c1, c1), kEps));
-    const float nb = sqrtf(fmaxf(dot(b1, b1), kEps));
+    const float n0 = sqrtf(floor_keep_nan(dot(c0, c0)));
+    const float n1 = sqrtf(floor_keep_nan(dot(c1, c1)));
+    const float nb = sqrtf(floor_keep_nan(dot(b1, b1)));
     c0 = scale(c0, n0);
     c1 = scale(c1, n1);
     const V3 b1u = scale(b1, nb);
@@ -97,7 +101,8 @@ __global__ __launch_bounds__(kThreads) void dihedrals_kernel(const float* __rest
 }
 
 // contact indicator of one atom pair per column: 1.0 when the distance is <= rcut, else 0.0; a NaN
-// distance (missing coordinates) counts as "no contact" (S/features/builtins.py:252-275)
+// distance (missing coordinates; distance_of keeps the NaN) or an infinite one counts as "no contact"
+// (S/features/builtins.py:252-275 sets NaN to inf before it compares)
 __global__ __launch_bounds__(kThreads) void contacts_kernel(const float* __restrict__ xyz, int64_t n, int A,
                                                            const int* __restrict__ pairs, int P, float rcut,
                                                            float* __restrict__ out, int64_t ld, int col_off) {
@@ -149,8 +154,9 @@ __global__ __launch_bounds__(kThreads) void rg_kernel(const float* __restrict__ 
 constexpr int kTileElems = 1024;
 constexpr int kTileFrames = 256;
 
-// kNanIn (the bias potential's forward): a record that reads a non-finite coordinate writes NaN, which the floors and
-// clamps of the geometry would otherwise turn into a finite value; false: the code of msm_featurize_spec as it was.
+// kNanIn (the bias potential's forward): a record that reads a non-finite coordinate writes NaN.  Without the flag
+// (msm_featurize_spec) the geometry follows the reference's rules: a NaN coordinate gives a NaN distance or angle, but a
+// dihedral of 0 (its mask) and a contact of 0, and a lone infinite coordinate gives a +inf distance.
 __device__ __forceinline__ bool finite3(V3 v) { return fabsf(v.x) <= FLT_MAX && fabsf(v.y) <= FLT_MAX && fabsf(v.z) <= FLT_MAX; }
 
 template <bool kSearch, bool kNanIn>

@@ -90,7 +90,7 @@ class _IndexedFeature:
         if min(idx) < 0 or max(idx) >= traj.n_atoms:
             raise ValueError(f"{self.name} indices out of range")
         X = _device_features(traj, periodic, **{self.kw: [idx]}).astype(float)
-        X = np.nan_to_num(X, nan=0.0)
+        X = np.nan_to_num(X, nan=0.0, posinf=0.0, neginf=0.0)   # S/features/builtins.py:307, 346, 387
         self._periodic = np.array([self.periodic], dtype=bool)
         self.labels = [f"{self.name}:" + "-".join(str(i) for i in idx)]
         return X
