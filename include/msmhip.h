@@ -663,6 +663,27 @@ msm_status msm_mlp_loss_grad_weighted(msm_ctx* ctx, const void* d_x, msm_dtype d
                                       double alpha, double cond_reg, double* d_work, size_t work_bytes, double* d_stats,
                                       double* d_grad, double* d_out, int64_t ldo);
 
+/* The launch shape of the four per-frame network kernels, as the one host function all four launch sites call
+ * decides it on this context now.  Launches nothing (above 48 KiB of LDS it raises the kernel's dynamic LDS limit,
+ * as a launch would).
+ *   kernel: MSM_MLP_KERNEL_FORWARD (msm_mlp_forward), _VJP (msm_mlp_vjp), _TRAIN_FORWARD, _TRAIN_BACKWARD (the two
+ *       passes of msm_mlp_loss_grad); dtype: that of d_x (the backward pass has one instance, dtype is only checked);
+ *   rows: n, or the 2m slots of a training batch (even, 2 <= m <= 2^24).
+ * A workgroup is one wave that takes a group of 16 rows at a time; one round of workgroups is launched, as many as
+ * are resident at once, and a workgroup that is given more than one group reuses its two LDS images.
+ * out: [0] LDS bytes per workgroup, [1] workgroups resident per CU, [2] grid = min(groups, CUs x [1]),
+ *   [3] groups = ceil(rows / 16), [4] trips = ceil(groups / grid) (0 when rows = 0); for the training kernels also
+ *   [5] chunks of the parameter gradient = ceil(2m / MSM_MLP_CHUNK), [6] chunks of the loss's moments =
+ *   ceil(m / MSM_MLP_CHUNK), [7] jobs of the parameter kernel (its grid is [7] x [5]); otherwise zero.
+ * Envelope and codes: msm_mlp_forward's for the widths, msm_mlp_loss_grad's for m. */
+#define MSM_MLP_CHUNK 256 /* slots (pairs) per partial sum of a parameter gradient (of a loss moment) */
+#define MSM_MLP_KERNEL_FORWARD 0
+#define MSM_MLP_KERNEL_VJP 1
+#define MSM_MLP_KERNEL_TRAIN_FORWARD 2
+#define MSM_MLP_KERNEL_TRAIN_BACKWARD 3
+msm_status msm_mlp_launch_plan(msm_ctx* ctx, int kernel, msm_dtype dtype, int64_t rows, int n_linear,
+                               const int32_t* h_widths, int ln_in, int ln_hidden, int head_activation, int64_t out[8]);
+
 /* Gradient clip (trainer.py:1048-1060, torch's clip_grad_norm_) and one step of torch's AdamW with a single
  * parameter group, all in fp64:
  *   norm = |g|_2; clip > 0: g <- g min(1, clip / (norm + 1e-6)); clip <= 0: none;

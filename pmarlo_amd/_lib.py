@@ -46,6 +46,9 @@ STATE_COUNTS_LDS_MAX_K, KPP_BLOCK = 16384, 1024
 MLP_MAX_WIDTH, MLP_MAX_OUT, MLP_MAX_LINEAR = 256, 64, 8
 # msm_vamp2_loss's stats block (MSM_VAMP2_STATS): 16 scalars, then var_z0, var_zt, mean_z0, mean_zt of 64 entries
 VAMP2_STATS = 16 + 4 * MLP_MAX_OUT
+# msm_mlp_launch_plan: the kernel codes (MSM_MLP_KERNEL_*) and the slots per partial sum (MSM_MLP_CHUNK)
+MLP_KERNELS = {"forward": 0, "vjp": 1, "train_forward": 2, "train_backward": 3}
+MLP_CHUNK = 256
 
 
 class MsmError(RuntimeError):
@@ -136,6 +139,7 @@ _PROTOTYPES: dict[str, tuple] = {
     "msm_mlp_loss_grad_weighted": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32,
                                           _vp, _sz, _vp, _vp, _vp, _i64, _vp, C.c_uint64, C.c_uint64, _f64, _f64, _f64,
                                           _f64, _vp, _sz, _vp, _vp, _vp, _i64]),
+    "msm_mlp_launch_plan": (_i32, [_vp, _i32, _i32, _i64, _i32, _vp, _i32, _i32, _i32, _vp]),
     "msm_adamw_step": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _f64, _f64, _f64, _f64, _f64, _f64, _vp]),
     "msm_mlp_vjp_workspace": (_sz, [_i64, _i32, _vp, _i32, _i32, _i32]),
     "msm_mlp_vjp": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _sz, _vp, _i64,

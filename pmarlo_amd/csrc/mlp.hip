@@ -106,19 +106,11 @@ msm_status msm_mlp_forward(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64
     if (n == 0) return MSM_OK;
     MSM_REQUIRE(ctx, d_x && d_params && d_out, "msm_mlp_forward: NULL pointer");
 
-    const size_t lds = (size_t)16 * (p.stride[0] + p.stride[1]) * sizeof(double);   // <= 66 KiB
-    const int64_t n_groups = (n + 15) / 16;
+    MlpLaunch s;
+    if (msm_status st = mlp_launch_shape(ctx, mlp_forward_kernel_address(dtype), p, n, &s)) return st;
 #define MSM_MLP(T)                                                                                                  \
-    do {                                                                                                            \
-        if (lds > 48 * 1024)                                                                                        \
-            MSM_HIP(ctx, hipFuncSetAttribute((const void*)mlp_forward_kernel<T>,                                    \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                \
-        int per_cu = 0;   /* one round of workgroups: as many as are resident at once */                            \
-        MSM_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mlp_forward_kernel<T>, 64, lds));        \
-        const int grid = (int)std::min<int64_t>(n_groups, (int64_t)ctx->n_cu * std::max(per_cu, 1));                \
-        hipLaunchKernelGGL(mlp_forward_kernel<T>, dim3(grid), dim3(64), lds, ctx->stream, (const T*)d_x, n, ld,     \
-                           d_mean, d_scale, d_params, p, d_out, ldo);                                               \
-    } while (0)
+    hipLaunchKernelGGL(mlp_forward_kernel<T>, dim3(s.grid), dim3(64), s.lds, ctx->stream, (const T*)d_x, n, ld,     \
+                       d_mean, d_scale, d_params, p, d_out, ldo)
     if (dtype == MSM_F32) MSM_MLP(float);
     else MSM_MLP(double);
 #undef MSM_MLP
@@ -127,3 +119,7 @@ msm_status msm_mlp_forward(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64
 }
 
 }  // extern "C"
+
+const void* mlp_forward_kernel_address(msm_dtype dtype) {
+    return dtype == MSM_F32 ? (const void*)mlp_forward_kernel<float> : (const void*)mlp_forward_kernel<double>;
+}

@@ -16,6 +16,7 @@ namespace {
 constexpr int kMlpMaxWidth = 256;   // F, hidden widths
 constexpr int kMlpMaxOut = 64;      // apply_output_transform's limit
 constexpr int kMlpMaxLinear = 8;
+constexpr int kChunk = MSM_MLP_CHUNK;   // slots per partial sum of a parameter gradient / of a moment (mlp_train.hip)
 
 enum { kActTanh = 0, kActGelu = 1, kActRelu = 2, kActElu = 3, kActSelu = 4, kActLeakyRelu = 5, kActCount = 6 };
 
@@ -250,4 +251,37 @@ inline msm_status mlp_make_plan(msm_ctx* ctx, const char* fn, int F, int n_linea
     return MSM_OK;
 }
 
+// The launch shape of the four per-frame kernels (mlp_forward_kernel, mlp_vjp_kernel, mlp_train_forward_kernel,
+// mlp_train_backward_kernel): one wave per workgroup, a group of 16 rows at a time, one round of workgroups.
+struct MlpLaunch {
+    size_t lds;         // the two LDS images, bytes (<= 66 KiB)
+    int per_cu;         // workgroups resident per CU at that LDS size, at least 1
+    int grid;           // min(n_groups, n_cu * per_cu)
+    int64_t n_groups;   // ceil(rows / 16)
+    int64_t trips;      // ceil(n_groups / grid): from 2 on a workgroup reuses its LDS images
+};
+
+// The one place that decides it: every launch site calls this, and msm_mlp_launch_plan reports it.  `kernel`: the
+// kernel's host address; `rows`: n, or 2m of a training batch.  Above 48 KiB the kernel's dynamic LDS limit is
+// raised here, before the occupancy is asked for.
+inline msm_status mlp_launch_shape(msm_ctx* ctx, const void* kernel, const MlpPlan& p, int64_t rows, MlpLaunch* out) {
+    MlpLaunch s;
+    s.lds = (size_t)16 * (p.stride[0] + p.stride[1]) * sizeof(double);
+    if (s.lds > 48 * 1024)
+        MSM_HIP(ctx, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.lds));
+    int per_cu = 0;   // one round of workgroups: as many as are resident at once
+    MSM_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 64, s.lds));
+    s.per_cu = std::max(per_cu, 1);
+    s.n_groups = (rows + 15) / 16;
+    s.grid = (int)std::min<int64_t>(s.n_groups, (int64_t)ctx->n_cu * s.per_cu);
+    s.trips = s.grid > 0 ? (s.n_groups + s.grid - 1) / s.grid : 0;
+    *out = s;
+    return MSM_OK;
+}
+
 }  // namespace
+
+// The kernels' host addresses, for msm_mlp_launch_plan (mlp_train.hip): mlp.hip, mlp_vjp.hip, mlp_train.hip
+const void* mlp_forward_kernel_address(msm_dtype dtype);
+const void* mlp_vjp_kernel_address(msm_dtype dtype);
+const void* mlp_train_kernel_address(bool backward, msm_dtype dtype);

@@ -28,7 +28,6 @@
 
 namespace {
 
-constexpr int kChunk = 256;             // slots per partial sum of a parameter gradient / of a moment
 constexpr int kStatsHead = 16;          // scalars in front of the four vectors of the stats block
 constexpr int kSolveThreads = 256;
 
@@ -303,6 +302,17 @@ __global__ __launch_bounds__(64) void mlp_train_param_partial_kernel(MlpPlan p, 
             job -= nb;
         }
     }
+}
+
+// the jobs of mlp_train_param_partial_kernel (its gridDim.x)
+int param_jobs(const MlpPlan& p) {
+    int jobs = 0;
+    if (p.ln_in_off >= 0) jobs += 2 * ((p.width[0] + 63) / 64);
+    for (int l = 0; l < p.n_linear; ++l) {
+        const int K = p.width[l], N = p.width[l + 1];
+        jobs += ((K + 15) / 16) * ((N + 15) / 16) + ((N + 63) / 64) * (p.ln_off[l] >= 0 ? 3 : 1);
+    }
+    return jobs;
 }
 
 __global__ __launch_bounds__(256) void mlp_train_param_reduce_kernel(const double* __restrict__ partial, int chunks,
@@ -1048,19 +1058,11 @@ msm_status msm_mlp_loss_grad_weighted(msm_ctx* ctx, const void* d_x, msm_dtype d
                 "msm_mlp_loss_grad: workspace of %zu bytes, %zu are needed", work_bytes,
                 (size_t)lay.total * sizeof(double));
 
-    const size_t lds = (size_t)16 * (p.stride[0] + p.stride[1]) * sizeof(double);   // <= 66 KiB
-    const int n_groups = (int)((2 * m + 15) / 16);
+    MlpLaunch s;
+    if (msm_status st = mlp_launch_shape(ctx, mlp_train_kernel_address(false, dtype), p, 2 * m, &s)) return st;
 #define MSM_MLP_TRAIN(T)                                                                                              \
-    do {                                                                                                              \
-        if (lds > 48 * 1024)                                                                                          \
-            MSM_HIP(ctx, hipFuncSetAttribute((const void*)mlp_train_forward_kernel<T>,                                \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                  \
-        int per_cu = 0;                                                                                               \
-        MSM_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mlp_train_forward_kernel<T>, 64, lds));    \
-        const int grid = (int)std::min<int64_t>(n_groups, (int64_t)ctx->n_cu * std::max(per_cu, 1));                  \
-        hipLaunchKernelGGL(mlp_train_forward_kernel<T>, dim3(grid), dim3(64), lds, ctx->stream, (const T*)d_x, n, ld, \
-                           d_mean, d_scale, d_params, p, d_idx_t, d_idx_tau, (int)m, drop, lay, d_work);              \
-    } while (0)
+    hipLaunchKernelGGL(mlp_train_forward_kernel<T>, dim3(s.grid), dim3(64), s.lds, ctx->stream, (const T*)d_x, n, ld, \
+                       d_mean, d_scale, d_params, p, d_idx_t, d_idx_tau, (int)m, drop, lay, d_work)
     if (dtype == MSM_F32) MSM_MLP_TRAIN(float);
     else MSM_MLP_TRAIN(double);
 #undef MSM_MLP_TRAIN
@@ -1076,28 +1078,58 @@ msm_status msm_mlp_loss_grad_weighted(msm_ctx* ctx, const void* d_x, msm_dtype d
                                       (size_t)n_out * sizeof(double), (size_t)(2 * m), hipMemcpyDeviceToDevice,
                                       ctx->stream));
     if (!d_grad) return MSM_OK;
-    {
-        if (lds > 48 * 1024)
-            MSM_HIP(ctx, hipFuncSetAttribute((const void*)mlp_train_backward_kernel,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        int per_cu = 0;
-        MSM_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mlp_train_backward_kernel, 64, lds));
-        const int grid = (int)std::min<int64_t>(n_groups, (int64_t)ctx->n_cu * std::max(per_cu, 1));
-        hipLaunchKernelGGL(mlp_train_backward_kernel, dim3(grid), dim3(64), lds, ctx->stream, d_params, p, (int)m, drop,
-                           lay, d_work);
-    }
-    int jobs = 0;
-    if (ln_in) jobs += 2 * ((F + 63) / 64);
-    for (int l = 0; l < n_linear; ++l) {
-        const int K = p.width[l], N = p.width[l + 1];
-        jobs += ((K + 15) / 16) * ((N + 15) / 16) + ((N + 63) / 64) * (p.ln_off[l] >= 0 ? 3 : 1);
-    }
+    if (msm_status st = mlp_launch_shape(ctx, mlp_train_kernel_address(true, dtype), p, 2 * m, &s)) return st;
+    hipLaunchKernelGGL(mlp_train_backward_kernel, dim3(s.grid), dim3(64), s.lds, ctx->stream, d_params, p, (int)m, drop,
+                       lay, d_work);
+    const int jobs = param_jobs(p);
     const int chunks = (int)((2 * m + kChunk - 1) / kChunk);
     hipLaunchKernelGGL(mlp_train_param_partial_kernel, dim3(jobs, chunks), dim3(64), 0, ctx->stream, p, (int)m, lay,
                        (int)n_params, d_work, d_work + lay.partial);
     hipLaunchKernelGGL(mlp_train_param_reduce_kernel, dim3((unsigned)((n_params + 255) / 256)), dim3(256), 0, ctx->stream,
                        d_work + lay.partial, chunks, (int)n_params, d_grad);
     MSM_CHECK_LAUNCH(ctx);
+    return MSM_OK;
+}
+
+msm_status msm_mlp_launch_plan(msm_ctx* ctx, int kernel, msm_dtype dtype, int64_t rows, int n_linear,
+                               const int32_t* h_widths, int ln_in, int ln_hidden, int head_activation, int64_t out[8]) {
+    if (!ctx) return MSM_ERR_INVALID;
+    MSM_REQUIRE(ctx, out, "msm_mlp_launch_plan: NULL pointer");
+    MSM_REQUIRE(ctx, kernel >= MSM_MLP_KERNEL_FORWARD && kernel <= MSM_MLP_KERNEL_TRAIN_BACKWARD,
+                "msm_mlp_launch_plan: unknown kernel code %d", kernel);
+    MSM_REQUIRE(ctx, dtype == MSM_F32 || dtype == MSM_F64, "msm_mlp_launch_plan: bad dtype");
+    MSM_REQUIRE(ctx, h_widths, "msm_mlp_launch_plan: NULL widths");
+    MlpPlan p;
+    if (msm_status st = mlp_make_plan(ctx, "msm_mlp_launch_plan", h_widths[0], n_linear, h_widths, 0, ln_in, ln_hidden,
+                                      head_activation, kMlpAnyParams, &p))
+        return st;
+    const bool train = kernel == MSM_MLP_KERNEL_TRAIN_FORWARD || kernel == MSM_MLP_KERNEL_TRAIN_BACKWARD;
+    const int64_t m = rows / 2;
+    if (train) {
+        MSM_REQUIRE(ctx, rows >= 0 && rows % 2 == 0, "msm_mlp_launch_plan: %lld slots (a training batch has 2m)",
+                    (long long)rows);
+        if (m < 2 || m > (1 << 24))
+            return msm_fail(ctx, m < 2 ? MSM_ERR_INVALID : MSM_ERR_UNSUPPORTED,
+                            "msm_mlp_launch_plan: %lld frame pairs (2 to %d are supported)", (long long)m, 1 << 24);
+    } else {
+        MSM_REQUIRE(ctx, rows >= 0, "msm_mlp_launch_plan: bad shape (n = %lld)", (long long)rows);
+    }
+    const void* fn = kernel == MSM_MLP_KERNEL_FORWARD ? mlp_forward_kernel_address(dtype)
+                     : kernel == MSM_MLP_KERNEL_VJP   ? mlp_vjp_kernel_address(dtype)
+                                                      : mlp_train_kernel_address(kernel == MSM_MLP_KERNEL_TRAIN_BACKWARD, dtype);
+    MlpLaunch s;
+    if (msm_status st = mlp_launch_shape(ctx, fn, p, rows, &s)) return st;
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    out[0] = (int64_t)s.lds;
+    out[1] = s.per_cu;
+    out[2] = s.grid;
+    out[3] = s.n_groups;
+    out[4] = s.trips;
+    if (train) {
+        out[5] = (rows + kChunk - 1) / kChunk;
+        out[6] = vamp_work((int)m, p.width[n_linear]).chunks;
+        out[7] = param_jobs(p);
+    }
     return MSM_OK;
 }
 
@@ -1126,3 +1158,9 @@ msm_status msm_adamw_step(msm_ctx* ctx, float* d_params, const double* d_grad, d
 }
 
 }  // extern "C"
+
+const void* mlp_train_kernel_address(bool backward, msm_dtype dtype) {
+    if (backward) return (const void*)mlp_train_backward_kernel;
+    return dtype == MSM_F32 ? (const void*)mlp_train_forward_kernel<float>
+                            : (const void*)mlp_train_forward_kernel<double>;
+}

@@ -198,20 +198,11 @@ msm_status msm_mlp_vjp(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n
     MSM_REQUIRE(ctx, work_bytes >= (size_t)lay.total * sizeof(double), "msm_mlp_vjp: workspace of %zu bytes, %zu are needed",
                 work_bytes, (size_t)lay.total * sizeof(double));
 
-    const size_t lds = (size_t)16 * (p.stride[0] + p.stride[1]) * sizeof(double);   // <= 66 KiB
-    const int64_t n_groups = (n + 15) / 16;
+    MlpLaunch s;
+    if (msm_status st = mlp_launch_shape(ctx, mlp_vjp_kernel_address(dtype), p, n, &s)) return st;
 #define MSM_MLP_VJP(T)                                                                                               \
-    do {                                                                                                             \
-        if (lds > 48 * 1024)                                                                                         \
-            MSM_HIP(ctx, hipFuncSetAttribute((const void*)mlp_vjp_kernel<T>,                                         \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                 \
-        int per_cu = 0;   /* one round of workgroups: as many as are resident at once */                             \
-        MSM_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, mlp_vjp_kernel<T>, 64, lds));             \
-        const int grid = (int)std::min<int64_t>(n_groups, (int64_t)ctx->n_cu * std::max(per_cu, 1));                 \
-        hipLaunchKernelGGL(mlp_vjp_kernel<T>, dim3(grid), dim3(64), lds, ctx->stream, (const T*)d_x, n, ld, d_mean,  \
-                           d_scale, d_params, p, d_gout, ldgo, strength, d_energy, d_out, ldo, d_gx, ldgx, lay,      \
-                           d_work);                                                                                  \
-    } while (0)
+    hipLaunchKernelGGL(mlp_vjp_kernel<T>, dim3(s.grid), dim3(64), s.lds, ctx->stream, (const T*)d_x, n, ld, d_mean,  \
+                       d_scale, d_params, p, d_gout, ldgo, strength, d_energy, d_out, ldo, d_gx, ldgx, lay, d_work)
     if (dtype == MSM_F32) MSM_MLP_VJP(float);
     else MSM_MLP_VJP(double);
 #undef MSM_MLP_VJP
@@ -274,3 +265,7 @@ msm_status msm_bias_energy_forces(msm_ctx* ctx, const float* d_xyz, int64_t n, i
 }
 
 }  // extern "C"
+
+const void* mlp_vjp_kernel_address(msm_dtype dtype) {
+    return dtype == MSM_F32 ? (const void*)mlp_vjp_kernel<float> : (const void*)mlp_vjp_kernel<double>;
+}

@@ -1096,6 +1096,29 @@ class Engine:
                                   out.ptr, out.shape[1]), self.handle)
         return out
 
+    def mlp_plan(self, kernel: str, spec, rows: int, dtype=np.float32) -> dict:
+        """The launch shape `kernel` ("forward", "vjp", "train_forward" or "train_backward") would get on this engine
+        now for the network `spec` (an MLPSpec, or its widths with ln_in / ln_hidden / head_activation attributes) and
+        `rows` rows -- n, or the 2m slots of a training batch -- of x in `dtype` (msm_mlp_launch_plan,
+        include/msmhip.h): lds_bytes, per_cu, grid, grid_cap (= CUs x per_cu: the grid of a batch that is large
+        enough), n_groups, trips, and for the training kernels param_chunks, vamp_chunks, param_jobs.  Launches
+        nothing."""
+        import ctypes
+
+        if kernel not in _lib.MLP_KERNELS:
+            raise ValueError(f"kernel must be one of {sorted(_lib.MLP_KERNELS)}, got {kernel!r}")
+        widths = np.ascontiguousarray(spec.widths, np.int32)
+        out = (ctypes.c_int64 * 8)()
+        check(lib.msm_mlp_launch_plan(self.handle, _lib.MLP_KERNELS[kernel], _dtype_code(np.dtype(dtype)), int(rows),
+                                      len(widths) - 1, widths.ctypes.data, int(bool(spec.ln_in)),
+                                      int(bool(spec.ln_hidden)), int(bool(spec.head_activation)), out), self.handle)
+        v = [int(x) for x in out]
+        plan = {"lds_bytes": v[0], "per_cu": v[1], "grid": v[2], "grid_cap": self.info()["n_cu"] * v[1],
+                "n_groups": v[3], "trips": v[4]}
+        if kernel.startswith("train"):
+            plan.update(param_chunks=v[5], vamp_chunks=v[6], param_jobs=v[7])
+        return plan
+
     # -- DeepTICA training ------------------------------------------------------
     @staticmethod
     def _vamp2_stats(stats: np.ndarray, d: int) -> dict:

@@ -125,8 +125,11 @@ def _layer_norm(x, gamma, beta):
     return (x - mu) / np.sqrt(var + 1e-5) * gamma.astype(np.float64) + beta.astype(np.float64)
 
 
-def forward(config: dict, params: dict, mean, std, X) -> np.ndarray:
-    """Raw network outputs [n, n_out] in float64 (steps 1-4)."""
+def forward(config: dict, params: dict, mean, std, X, head_activation=None) -> np.ndarray:
+    """Raw network outputs [n, n_out] in float64 (steps 1-4).  head_activation: None follows the config (the head is
+    activated unless linear_head, which also drops the hidden layers); a bool overrides it, which is how a network
+    with hidden layers and a linear head -- one the C API allows and no config produces -- is stated."""
+    head = (not config.get("linear_head")) if head_activation is None else bool(head_activation)
     Z = (np.asarray(X, np.float64) - np.asarray(mean, np.float64)) / np.asarray(std, np.float64)
     x = Z.astype(np.float32).astype(np.float64)
     act = _activation(config.get("activation", "gelu"))
@@ -140,7 +143,7 @@ def forward(config: dict, params: dict, mean, std, X) -> np.ndarray:
             if config.get("layer_norm_hidden"):
                 x = _layer_norm(x, params[f"inner.nn.{idx + 1}.weight"], params[f"inner.nn.{idx + 1}.bias"])
             x = act(x)
-        elif not config.get("linear_head"):
+        elif head:
             x = act(x)
     return x
 

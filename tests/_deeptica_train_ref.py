@@ -165,9 +165,13 @@ def layers_of(config: dict, F: int):
     return out
 
 
-def forward_train(config, params, mean, std, X, idx_t, idx_tau, dropout=None, seed=0, step=0):
+def forward_train(config, params, mean, std, X, idx_t, idx_tau, dropout=None, seed=0, step=0, head_activation=None,
+                  masks=None):
     """Outputs [2m, n_out] of the slots (t frames, then tau frames) and what the backward pass needs.  params: fp32
-    arrays by key; dropout: None (evaluation) or [input, hidden 0, ...]."""
+    arrays by key; dropout: None (evaluation) or [input, hidden 0, ...]; head_activation: as in R.forward; masks:
+    {site: [2m, width] factors} used in place of dropout_factor's draw (a permuted route through the same law)."""
+    draw = dropout_factor if masks is None else (lambda _seed, _step, site, *_: masks[site])
+    head = (not config.get("linear_head")) if head_activation is None else bool(head_activation)
     rows = np.concatenate([np.asarray(idx_t), np.asarray(idx_tau)])
     Z = (np.asarray(X, np.float64)[rows] - np.asarray(mean, np.float64)) / np.asarray(std, np.float64)
     x = Z.astype(np.float32).astype(np.float64)
@@ -178,7 +182,7 @@ def forward_train(config, params, mean, std, X, idx_t, idx_tau, dropout=None, se
     if config.get("layer_norm_in"):
         x, tape["ln_in"] = _ln_forward(x, P["ln.weight"], P["ln.bias"])
     if dropout is not None:
-        tape["mask_in"] = dropout_factor(seed, step, 0, S2, F, dropout[0])
+        tape["mask_in"] = draw(seed, step, 0, S2, F, dropout[0])
         x = x * tape["mask_in"]
     layers = layers_of(config, F)
     for i, (kw, kb, kg, kbeta) in enumerate(layers):
@@ -187,11 +191,11 @@ def forward_train(config, params, mean, std, X, idx_t, idx_tau, dropout=None, se
         last = i == len(layers) - 1
         if kg is not None:
             x, rec["ln"] = _ln_forward(x, P[kg], P[kbeta])
-        if not last or not config.get("linear_head"):
+        if not last or head:
             rec["h"] = x
             x = act(x)
         if not last and dropout is not None:
-            rec["mask"] = dropout_factor(seed, step, i + 1, S2, x.shape[1], dropout[i + 1])
+            rec["mask"] = draw(seed, step, i + 1, S2, x.shape[1], dropout[i + 1])
             x = x * rec["mask"]
         tape["layers"].append(rec)
     return x, tape
@@ -286,13 +290,16 @@ def vamp2(Y0, Yt, eps=1e-3, eps_abs=1e-6, alpha=0.15, cond_reg=1e-4):
             "term_scale": term_scale}
 
 
-def loss_grad(name: str, X, idx_t, idx_tau, packed=None, dropout=None, seed=0, step=0, opts=None):
+def loss_grad(name, X, idx_t, idx_tau, packed=None, dropout=None, seed=0, step=0, opts=None, head_activation=None,
+              masks=None):
     """The whole of msm_mlp_loss_grad for a case: vamp2's dict plus `outputs` [2m, n_out] and `grad` (packed, fp64)
-    with `grads` (by key)."""
-    c = R.case(name)
-    F = c["X"].shape[1]
+    with `grads` (by key).  name: a case of R.CASES, or the case itself (a dict with config, params, mean, std as
+    R.recipe makes them); head_activation: as in R.forward."""
+    c = R.case(name) if isinstance(name, str) else name
+    F = np.asarray(X).shape[1]
     params = c["params"] if packed is None else unpack(c["config"], F, np.asarray(packed, np.float32))
-    Y, tape = forward_train(c["config"], params, c["mean"], c["std"], X, idx_t, idx_tau, dropout, seed, step)
+    Y, tape = forward_train(c["config"], params, c["mean"], c["std"], X, idx_t, idx_tau, dropout, seed, step,
+                            head_activation, masks)
     m = len(idx_t)
     res = vamp2(Y[:m], Y[m:], **(opts or LOSS_OPTS))
     grads = backward(c["config"], params, F, tape, np.concatenate([res["grad0"], res["grad_t"]]))

@@ -22,6 +22,7 @@ def test_header_declares_functions():
     names = _declared_functions()
     assert "msm_count_transitions" in names and "msm_kmeans_assign" in names
     assert "msm_count_transitions_plan" in names                    # the read-only view of the count dispatch
+    assert "msm_mlp_launch_plan" in names                           # the read-only view of the network launch shape
     assert len(names) >= 20
 
 
