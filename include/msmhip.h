@@ -590,7 +590,8 @@ msm_status msm_mlp_forward(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64
  *   tries (the reference raises; loss and score are then NaN), [10..15] zero; then var_z0, var_zt, mean_z0, mean_zt,
  *   64 entries each, the first n_out of each written.
  * d_grad0, d_gradt [m, ldg] f64 or both NULL.  d_work: msm_vamp2_workspace(m, n_out) bytes (0: outside the
- * envelope).  Moments are summed per chunk of 256 frames on the matrix cores and the chunks added in ascending
+ * envelope).  Envelope: 1 <= m <= 2^24 (the moments kernels take one chunk per grid row and the device admits 65536
+ * rows) and n_out <= 64; MSM_ERR_UNSUPPORTED beyond, naming the number, before anything is launched.  Moments are summed per chunk of 256 frames on the matrix cores and the chunks added in ascending
  * order, the dense algebra runs in one workgroup: equal inputs give equal bits.  Plain launches on the context's
  * stream, no host synchronisation. */
 #define MSM_VAMP2_STATS 272

@@ -333,6 +333,10 @@ struct VampWork {
     int chunks;
 };
 
+// The moments kernels take one chunk per gridDim.y entry, and gfx950 admits 65536 of them (hipDeviceProp_t's
+// maxGridSize[1]): the largest batch of the loss, which is also msm_mlp_loss_grad's 2^24 pairs.
+constexpr int64_t kVampMaxPairs = (int64_t)65536 * kChunk;
+
 inline VampWork vamp_work(int m, int d, bool weighted = false) {
     VampWork w;
     w.chunks = (m + kChunk - 1) / kChunk;
@@ -932,7 +936,10 @@ msm_status vamp2_entry(msm_ctx* ctx, const char* fn, const double* d_y0, const d
                        int64_t m, int n_out, int64_t ld, double eps, double eps_abs, double alpha, double cond_reg,
                        double* d_work, double* d_stats, double* d_grad0, double* d_gradt, int64_t ldg) {
     if (!ctx) return MSM_ERR_INVALID;
-    MSM_REQUIRE(ctx, m >= 1 && m <= (1 << 29), "%s: %lld frame pairs", fn, (long long)m);
+    MSM_REQUIRE(ctx, m >= 1, "%s: %lld frame pairs", fn, (long long)m);
+    if (m > kVampMaxPairs)
+        return msm_fail(ctx, MSM_ERR_UNSUPPORTED, "%s: %lld frame pairs (at most %lld are supported)", fn, (long long)m,
+                        (long long)kVampMaxPairs);
     MSM_REQUIRE(ctx, n_out >= 1, "%s: %d outputs", fn, n_out);
     if (n_out > kMlpMaxOut)
         return msm_fail(ctx, MSM_ERR_UNSUPPORTED, "%s: %d outputs (at most %d are supported)", fn, n_out, kMlpMaxOut);
@@ -961,7 +968,7 @@ size_t train_workspace(int64_t m, int n_linear, const int32_t* h_widths, int ln_
 extern "C" {
 
 size_t msm_vamp2_workspace(int64_t m, int n_out) {
-    if (m < 1 || n_out < 1 || n_out > kMlpMaxOut || m > (1 << 29)) return 0;
+    if (m < 1 || n_out < 1 || n_out > kMlpMaxOut || m > kVampMaxPairs) return 0;
     return (size_t)vamp_work((int)m, n_out).total * sizeof(double);
 }
 
@@ -973,7 +980,7 @@ msm_status msm_vamp2_loss(msm_ctx* ctx, const double* d_y0, const double* d_yt, 
 }
 
 size_t msm_vamp2_weighted_workspace(int64_t m, int n_out) {
-    if (m < 1 || n_out < 1 || n_out > kMlpMaxOut || m > (1 << 29)) return 0;
+    if (m < 1 || n_out < 1 || n_out > kMlpMaxOut || m > kVampMaxPairs) return 0;
     return (size_t)vamp_work((int)m, n_out, true).total * sizeof(double);
 }
 
