@@ -5,7 +5,8 @@
 // two images that the layers ping-pong between (the first as wide as the widest input of an even layer, the second
 // of an odd one); nothing but the input rows is read from and nothing but the output rows written to global memory
 // per frame.  As many waves as the LDS holds images for are resident per CU, and while one is in its LayerNorm and
-// activation phase another has the matrix cores.
+// activation phase another has the matrix cores.  The kernel is the shared forward walk (mlp_load_inputs and
+// mlp_forward_walk, mlp_common.h) with nothing kept for a backward pass.
 //
 // A Linear layer (mlp_linear, mlp_common.h) is out' (16 columns x 16 frames) = W (16 x K) . act' (K x 16 frames) per tile of 16 output
 // columns, v_mfma_f64_16x16x4_f64, four tiles (64 columns) in flight per pass over K so that one LDS read of the
@@ -33,51 +34,19 @@ __global__ __launch_bounds__(64) void mlp_forward_kernel(
     extern __shared__ __attribute__((aligned(16))) unsigned char mlp_smem[];
     const int lane = threadIdx.x;
     const int j = lane & 15, g = lane >> 4;
-    const int S = p.stride[0];
-    double* img0 = reinterpret_cast<double*>(mlp_smem);
-    double* img1 = img0 + 16 * S;
-    const int F = p.width[0];
+    double* img[2];
+    img[0] = reinterpret_cast<double*>(mlp_smem);
+    img[1] = img[0] + 16 * p.stride[0];
     const int n_out = p.width[p.n_linear];
     const int64_t n_groups = (n + 15) / 16;
     for (int64_t grp = blockIdx.x; grp < n_groups; grp += gridDim.x) {
         const int64_t t0 = grp * 16;
         const int rows = (int)min<int64_t>(16, n - t0);
         WAVE_SYNC();   // the previous group's output rows have been read
-        // Z = (x - mean) / scale in fp64, rounded to fp32 as the reference hands it to the network; rows at or past
-        // n are not read and enter as zeros
-        for (int r = 0; r < 16; ++r)
-            for (int f = lane; f < F; f += 64) {
-                double z = 0.0;
-                if (r < rows) {
-                    z = (double)x[(t0 + r) * ld + f];
-                    if (sc_mean) z = (z - sc_mean[f]) / sc_scale[f];
-                    z = (double)(float)z;
-                }
-                img0[r * S + f] = z;
-            }
-        WAVE_SYNC();
-        double* cur = img0 + j * S;   // frame j's row, current and next layer
-        double* nxt = img1 + j * p.stride[1];
-        int bad = 0;                  // a non-finite Z anywhere in the frame: all its outputs are NaN
-        for (int f = g; f < F; f += 4) bad |= !(fabs(cur[f]) <= DBL_MAX);
-        bad = xrow_reduce(bad, op_or{});
-        if (p.ln_in_off >= 0) mlp_layer_norm(cur, g, F, params + p.ln_in_off);
-
-        for (int l = 0; l < p.n_linear; ++l) {
-            const int K = p.width[l], N = p.width[l + 1];
-            const float* __restrict__ W = params + p.w_off[l];
-            const float* __restrict__ bias = params + p.b_off[l];
-            WAVE_SYNC();   // the rows of `cur` are complete: every lane reads entries other lanes wrote
-            mlp_linear(cur, nxt, W, bias, K, N, j, g);
-            // lane (j, g) wrote the entries c = g mod 4 of its row and is the one that normalises and activates them
-            const bool last = l == p.n_linear - 1;
-            if (!last && p.ln_off[l] >= 0) mlp_layer_norm(nxt, g, N, params + p.ln_off[l]);
-            if (!last || p.head_activation)
-                for (int f = g; f < N; f += 4) nxt[f] = mlp_activate(nxt[f], p.activation);
-            double* swap = cur;
-            cur = nxt;
-            nxt = swap;
-        }
+        mlp_load_inputs(img[0], p.stride[0], p.width[0], lane, rows, x, ld, sc_mean, sc_scale,
+                        [&](int r) { return t0 + r; });
+        int bad;
+        const double* cur = mlp_forward_walk<false, false>(p, params, img, lane, rows, MlpKeep{}, &bad);
         if (j < rows) {
             const double qnan = __longlong_as_double(0x7ff8000000000000ll);
             for (int c = g; c < n_out; c += 4) out[(t0 + j) * ldo + c] = bad ? qnan : cur[c];

@@ -1,14 +1,18 @@
-// What the DeepTICA network kernels share: the inference pass (mlp.hip) and the training passes (mlp_train.hip).
-// Device code plus the host-side plan builder; include after common.h.
+// What the DeepTICA network kernels share: inference (mlp.hip), the input gradient (mlp_vjp.hip) and the training
+// passes (mlp_train.hip).  Device code plus the host-side plan, tape and launch-shape builders; include after common.h.
 //
 // A wave owns 16 frames; lane (j, g) = (lane & 15, lane >> 4) works on frame j.  Activation rows sit in LDS as fp64
-// [16][stride].  mlp_linear is the Linear layer of both forward kernels: because the inference and the training
-// forward run the very same instruction sequence per frame, their outputs agree bit for bit.
+// [16][stride], two images that the layers ping-pong between.  There is one forward walk over a group
+// (mlp_load_inputs, then mlp_forward_walk) and one set of adjoints (mlp_layer_adjoint, mlp_linear_transposed); what a
+// kernel adds to them -- a tape for the adjoints, the inputs of the Linear layers, dropout -- is chosen at compile
+// time and only inserts stores and row-local factors, so every kernel runs the same arithmetic per frame and the
+// outputs of the three forward kernels agree bit for bit.
 #pragma once
 #include <algorithm>
 #include <cfloat>
 
 #include "common.h"
+#include "philox.h"
 #include "wave.h"
 
 namespace {
@@ -45,7 +49,7 @@ __device__ __forceinline__ double mlp_activate(double x, int kind) {
         case kActGelu: return 0.5 * x * (1.0 + erf(x * 0.70710678118654752440));
         case kActRelu: return x < 0.0 ? 0.0 : x;
         case kActElu: return x > 0.0 ? x : expm1(x);
-        case kActSelu: return 1.0507009873554804934193349852946 * (x > 0.0 ? x : 1.6732632423543772848170429916717 * expm1(x));
+        case kActSelu: return kSeluScale * (x > 0.0 ? x : kSeluAlpha * expm1(x));
         case kActLeakyRelu: return x < 0.0 ? 0.01 * x : x;
         default: return tanh(x);
     }
@@ -135,7 +139,199 @@ __device__ __forceinline__ void mlp_linear(const double* cur, double* nxt, const
     }
 }
 
-// ---- what the backward passes share (mlp_train.hip, mlp_vjp.hip) ----
+// rows 0 .. rows-1 of an LDS image (row stride S, w entries each) to global rows of w doubles, coalesced
+__device__ __forceinline__ void save_rows(const double* img, int S, int w, int rows, double* __restrict__ dst, int lane) {
+    for (int r = 0; r < rows; ++r)
+        for (int f = lane; f < w; f += 64) dst[(size_t)r * w + f] = img[r * S + f];
+}
+
+// The tape: what a forward walk leaves per frame, in a workspace, for the adjoints (offsets in doubles; -1: absent;
+// [rows, width] each; travels by value):
+//   z     the scaled inputs when an input LayerNorm follows: its adjoint needs the row mean, the root and xhat, which
+//         are recomputed from z (three cheap passes over a cached row) rather than stored;
+//   u[l]  the output of Linear l when a LayerNorm follows, for the same reason;
+//   h[l]  the value the activation is applied to: act'(h).  Storing h instead of recomputing it from u saves a
+//         second LayerNorm per row in the backward pass and costs one row of doubles.
+struct MlpTape {
+    long long z;
+    long long h[kMlpMaxLinear], u[kMlpMaxLinear];
+};
+
+// What the training passes keep per slot besides the tape:
+//   a[l]   the input of Linear l (after LayerNorm, activation and dropout of the layer before): dW_l = du_l' a[l];
+//   du[l]  dL/d(output of Linear l);
+//   dh[l], dhx[l] (dz, dzx for the input LayerNorm)  dL/d(LayerNorm output) and that times xhat: the beta and gamma
+//          gradients are their column sums.
+struct MlpTrainSlots {
+    long long dz, dzx;
+    long long a[kMlpMaxLinear], du[kMlpMaxLinear], dh[kMlpMaxLinear], dhx[kMlpMaxLinear];
+};
+
+// The one walk that places them, for `rows` rows each; returns the doubles taken.  Without `train` the tape alone,
+// z, then per layer u and h; with it the training workspace, the tape's tensors among the others.
+inline long long mlp_tape_layout(const MlpPlan& p, long long rows, MlpTape* t, MlpTrainSlots* train = nullptr) {
+    long long off = 0;
+    auto take = [&](bool present, long long w) {
+        if (!present) return -1LL;
+        const long long at = off;
+        off += rows * w;
+        return at;
+    };
+    MlpTrainSlots none;
+    MlpTrainSlots* x = train ? train : &none;
+    const bool tr = train != nullptr, ln_in = p.ln_in_off >= 0;
+    t->z = take(ln_in, p.width[0]);
+    x->dz = take(tr && ln_in, p.width[0]);
+    x->dzx = take(tr && ln_in, p.width[0]);
+    for (int l = 0; l < kMlpMaxLinear; ++l) t->h[l] = t->u[l] = x->a[l] = x->du[l] = x->dh[l] = x->dhx[l] = -1;
+    for (int l = 0; l < p.n_linear; ++l) {
+        const int K = p.width[l], N = p.width[l + 1];
+        const bool last = l == p.n_linear - 1;
+        const bool act = !last || p.head_activation, ln = !last && p.ln_off[l] >= 0;
+        x->a[l] = take(tr, K);
+        x->du[l] = take(tr, N);
+        if (tr) t->h[l] = take(act, N);    // the training workspace has h ahead of u, the tape alone behind it
+        t->u[l] = take(ln, N);
+        if (!tr) t->h[l] = take(act, N);
+        x->dh[l] = take(tr && ln, N);
+        x->dhx[l] = take(tr && ln, N);
+    }
+    return off;
+}
+
+// per dropout site (0: inputs, i + 1: after the activation of Linear i): keep iff word >= thr; kept values times scale
+struct DropPlan {
+    int on;
+    unsigned thr[kMlpMaxLinear + 1];
+    double scale[kMlpMaxLinear + 1];
+    unsigned k0, k1, step;
+};
+
+// Dropout of frame j's row (slot `slot`) at site `site`, forward and adjoint alike: row[f] *= keep ? scale : 0.
+// Lane g takes the column blocks g, g + 4, ... of four columns, one Philox call each; the caller synchronises
+// the wave before and after (the lanes of a row own other entries outside this function).  Masks are never stored:
+// a mask bit is a pure function of (seed, step, site, slot, column), and the backward pass draws it again.
+__device__ __forceinline__ void mlp_dropout(double* row, int g, int w, const DropPlan& d, int site, unsigned slot) {
+    const Philox rng{d.k0, d.k1};
+    const unsigned thr = d.thr[site];
+    const double scale = d.scale[site];
+    for (int cb = g; 4 * cb < w; cb += 4) {
+        uint32_t c[4] = {d.step, (uint32_t)site, slot, (uint32_t)cb};
+        rng(c);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int f = 4 * cb + u;
+            if (f < w) row[f] = row[f] * (c[u] >= thr ? scale : 0.0);
+        }
+    }
+}
+
+// The 16 input rows of a group into image 0 (row stride S): Z = (x - mean) / scale in fp64, rounded to fp32 as the
+// reference hands it to the network.  row_of(r), asked for r < rows only, names the row of x that enters as row r, or
+// is negative: that row is not read and enters as NaN (all outputs of that frame are NaN).  Rows at or past `rows`
+// are not read either and enter as zeros.
+template <typename T, typename RowOf>
+__device__ __forceinline__ void mlp_load_inputs(double* img0, int S, int F, int lane, int rows, const T* __restrict__ x,
+                                                int64_t ld, const double* __restrict__ sc_mean,
+                                                const double* __restrict__ sc_scale, RowOf row_of) {
+    for (int r = 0; r < 16; ++r) {
+        const int64_t row = r < rows ? row_of(r) : 0;
+        for (int f = lane; f < F; f += 64) {
+            double z = 0.0;
+            if (r < rows) {
+                z = __longlong_as_double(0x7ff8000000000000ll);
+                if (row >= 0) {
+                    z = (double)x[row * ld + f];
+                    if (sc_mean) z = (z - sc_mean[f]) / sc_scale[f];
+                    z = (double)(float)z;
+                }
+            }
+            img0[r * S + f] = z;
+        }
+    }
+}
+
+// where a forward walk that keeps something puts it: `ws` + the layouts' offsets, rows from `row0` on (row0 + j is
+// also frame j's slot in the dropout counter).  `train` and `drop` only with the training option.
+struct MlpKeep {
+    const MlpTape* tape;
+    const MlpTrainSlots* train;
+    const DropPlan* drop;
+    double* ws;
+    size_t row0;
+};
+
+// The forward walk of a group of 16 frames, from "the group's input rows are in image 0" (mlp_load_inputs) to "frame
+// j's output row is at the pointer returned": the non-finite flag (`bad`: a non-finite Z anywhere in the frame, all
+// of whose outputs are then NaN), the input LayerNorm, and per layer Linear, LayerNorm and activation, the two images
+// swapping roles.  What is decided at compile time, and inserts nothing into the arithmetic of a frame:
+//   TAPE   z, u[l] and h[l] are written to k.tape (see MlpTape);
+//   TRAIN  (with TAPE) dropout by k.drop at every site that has it, and a[l] written to k.train.
+// Without either (inference) `k` is not looked at, and there is no WAVE_SYNC beyond the one in front of each Linear.
+template <bool TAPE, bool TRAIN>
+__device__ __forceinline__ double* mlp_forward_walk(const MlpPlan& p, const float* __restrict__ params,
+                                                    double* const* img, int lane, int rows, const MlpKeep& k,
+                                                    int* bad_out) {
+    static_assert(TAPE || !TRAIN, "the training walk writes the tape");
+    const int j = lane & 15, g = lane >> 4;
+    const int F = p.width[0], S = p.stride[0];
+    WAVE_SYNC();   // the input rows are complete
+    if constexpr (TAPE)
+        if (k.tape->z >= 0) save_rows(img[0], S, F, rows, k.ws + k.tape->z + k.row0 * F, lane);
+    double* cur = img[0] + j * S;   // frame j's row, current and next layer
+    double* nxt = img[1] + j * p.stride[1];
+    int bad = 0;
+    for (int f = g; f < F; f += 4) bad |= !(fabs(cur[f]) <= DBL_MAX);
+    *bad_out = xrow_reduce(bad, op_or{});
+    if (p.ln_in_off >= 0) mlp_layer_norm(cur, g, F, params + p.ln_in_off);
+    if constexpr (TRAIN) {
+        if (k.drop->on && k.drop->thr[0]) {
+            WAVE_SYNC();
+            mlp_dropout(cur, g, F, *k.drop, 0, (unsigned)(k.row0 + j));
+        }
+        WAVE_SYNC();
+        save_rows(img[0], S, F, rows, k.ws + k.train->a[0] + k.row0 * F, lane);
+    }
+    for (int l = 0; l < p.n_linear; ++l) {
+        const int K = p.width[l], N = p.width[l + 1];
+        const int Sn = p.stride[(l + 1) & 1];
+        const double* image = img[(l + 1) & 1];   // the image `nxt` is a row of
+        WAVE_SYNC();   // the rows of `cur` are complete: every lane reads entries other lanes wrote
+        mlp_linear(cur, nxt, params + p.w_off[l], params + p.b_off[l], K, N, j, g);
+        // lane (j, g) wrote the entries c = g mod 4 of its row and is the one that normalises and activates them; the
+        // tape's stores read whole rows, hence their WAVE_SYNC
+        const bool last = l == p.n_linear - 1;
+        if (!last && p.ln_off[l] >= 0) {
+            if constexpr (TAPE) {
+                WAVE_SYNC();
+                save_rows(image, Sn, N, rows, k.ws + k.tape->u[l] + k.row0 * N, lane);
+            }
+            mlp_layer_norm(nxt, g, N, params + p.ln_off[l]);
+        }
+        if (!last || p.head_activation) {
+            if constexpr (TAPE) {
+                WAVE_SYNC();
+                save_rows(image, Sn, N, rows, k.ws + k.tape->h[l] + k.row0 * N, lane);
+            }
+            for (int f = g; f < N; f += 4) nxt[f] = mlp_activate(nxt[f], p.activation);
+        }
+        if constexpr (TRAIN)
+            if (!last) {
+                if (k.drop->on && k.drop->thr[l + 1]) {
+                    WAVE_SYNC();
+                    mlp_dropout(nxt, g, N, *k.drop, l + 1, (unsigned)(k.row0 + j));
+                }
+                WAVE_SYNC();
+                save_rows(image, Sn, N, rows, k.ws + k.train->a[l + 1] + k.row0 * N, lane);
+            }
+        double* swap = cur;
+        cur = nxt;
+        nxt = swap;
+    }
+    return cur;
+}
+
+// ---- the adjoints (mlp_vjp.hip, mlp_train.hip) ----
 __device__ __forceinline__ double mlp_activate_grad(double x, int kind) {
     switch (kind) {
         case kActGelu:
@@ -149,12 +345,6 @@ __device__ __forceinline__ double mlp_activate_grad(double x, int kind) {
             return 1.0 - t * t;
         }
     }
-}
-
-// rows 0 .. rows-1 of an LDS image (row stride S, w entries each) to / from global rows of w doubles, coalesced
-__device__ __forceinline__ void save_rows(const double* img, int S, int w, int rows, double* __restrict__ dst, int lane) {
-    for (int r = 0; r < rows; ++r)
-        for (int f = lane; f < w; f += 64) dst[(size_t)r * w + f] = img[r * S + f];
 }
 
 // LayerNorm adjoint of frame j's row: `grow` holds dL/d(LN output) on entry and dL/d(LN input) on exit; `xin` is
@@ -190,6 +380,48 @@ __device__ __forceinline__ void mlp_layer_norm_adjoint(double* grow, int g, int 
     for (int f = g; f < w; f += 4) {
         const double xhat = (xin[f] - mean) * rstd;
         grow[f] = rstd * (grow[f] - s1 - xhat * s2);
+    }
+}
+
+// The adjoint of layer l's activation and LayerNorm on frame j's row: `gout` holds dE/d(output of layer l) on entry
+// and du_l on exit; h[l] and u[l] come from the tape's row `row` in `ws`.  KEEP (training): dh and dhx of the row go
+// to `train`'s slots when the frame exists (`mine`).  The caller has synchronised the wave: the tape rows are in
+// place, and so are the entries of gout other lanes wrote.
+template <bool KEEP>
+__device__ __forceinline__ void mlp_layer_adjoint(double* gout, int g, const MlpPlan& p, int l,
+                                                  const float* __restrict__ params, const MlpTape& tape,
+                                                  const MlpTrainSlots* train, double* ws, size_t row, bool mine) {
+    const int N = p.width[l + 1];
+    const bool last = l == p.n_linear - 1;
+    if (!last || p.head_activation) {
+        const double* h = ws + tape.h[l] + row * N;
+        for (int f = g; f < N; f += 4) gout[f] = gout[f] * mlp_activate_grad(h[f], p.activation);
+    }
+    if (!last && p.ln_off[l] >= 0) {
+        double* dh = nullptr, *dhx = nullptr;
+        if constexpr (KEEP) {
+            dh = ws + train->dh[l] + row * N;
+            dhx = ws + train->dhx[l] + row * N;
+        }
+        mlp_layer_norm_adjoint(gout, g, N, ws + tape.u[l] + row * N, params + p.ln_off[l], dh, dhx, KEEP && mine);
+    }
+}
+
+// The transposed Linear, gin[k] = sum_n W[n][k] gout[n], k < K, for the wave's 16 frames: out' (K x 16 frames) =
+// W' (K x N) . gout' (N x 16 frames) per tile of 16 entries k on the matrix cores.  gout / gin: frame j's rows; the
+// caller has made the rows of `gout` complete (WAVE_SYNC) before the call.
+__device__ __forceinline__ void mlp_linear_transposed(const double* gout, double* gin, const float* __restrict__ W,
+                                                      int K, int N, int j, int g) {
+    for (int k0 = 0; k0 < K; k0 += 16) {
+        const int kc = min(k0 + j, K - 1);
+        const v4f64 acc = mfma_tile_acc(
+            N, g, k0 + j < K, true, [&](int nn) { return (double)W[(size_t)nn * K + kc]; },
+            [&](int nn) { return gout[nn]; });
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int k = k0 + g + 4 * r;
+            if (k < K) gin[k] = acc[r];
+        }
     }
 }
 

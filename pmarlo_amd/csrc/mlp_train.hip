@@ -7,24 +7,16 @@
 // slots m .. 2m-1 the tau frames (rows idx_tau).  As in mlp.hip a workgroup is one wave that owns 16 slots, whose
 // rows sit in two LDS images the layers ping-pong between.
 //
-// What the forward pass leaves in the workspace, per layer l (all fp64, [2m, width]):
-//   a[l]  the input of Linear l (after LayerNorm, activation and dropout of the layer before): dW_l = du_l' a[l];
-//   u[l]  the output of Linear l when a LayerNorm follows: its adjoint needs the row mean, the root and xhat, which
-//         are recomputed from u (three cheap passes over a cached row) rather than stored;
-//   h[l]  the value the activation is applied to: act'(h).  Storing h instead of recomputing it from u saves a
-//         second LayerNorm per row in the backward pass and costs one row of doubles;
-//   z     the scaled inputs when an input LayerNorm follows, for the same reason as u.
-// Dropout masks are never stored: a mask bit is a pure function of (seed, step, layer, slot, column), and the
-// backward pass draws it again from Philox.
+// The forward pass is the shared walk (mlp_forward_walk, mlp_common.h) with the tape, dropout and the inputs a[l] of
+// the Linear layers switched on; what it leaves in the workspace, all fp64 [2m, width]: MlpTape and MlpTrainSlots.
 //
-// The backward pass works per 16-slot group: dA = du . W on the matrix cores (out' (K x 16 slots) = W' (K x N) .
-// du' (N x 16 slots)), then the dropout, activation and LayerNorm adjoints row by row; du_l (and, where a LayerNorm
-// has parameters, dh and dh * xhat) go to the workspace.  Parameter gradients are contractions over the 2m slots:
-// the slots are cut into chunks of kChunk = 256 (a constant, so the summation order depends on m alone), one wave
+// The backward pass works per 16-slot group: the dropout adjoint, then the shared activation and LayerNorm adjoints
+// row by row and dA = du . W on the matrix cores (mlp_layer_adjoint, mlp_linear_transposed); du_l (and, where a
+// LayerNorm has parameters, dh and dh * xhat) go to the workspace.  Parameter gradients are contractions over the 2m
+// slots: the slots are cut into chunks of kChunk = 256 (a constant, so the summation order depends on m alone), one wave
 // sums one 16 x 16 tile of dW (or 64 entries of a bias / gamma / beta gradient) over one chunk on the matrix cores,
 // and a second kernel adds the chunks in ascending order.  No atomics anywhere: equal inputs give equal bits.
 #include "mlp_common.h"
-#include "philox.h"
 
 namespace {
 
@@ -33,37 +25,10 @@ constexpr int kSolveThreads = 256;
 
 // where everything lies in the training workspace (offsets in doubles; -1: absent); travels by value
 struct TrainLayout {
-    long long z, dz, dzx;
-    long long a[kMlpMaxLinear], h[kMlpMaxLinear], u[kMlpMaxLinear];
-    long long du[kMlpMaxLinear], dh[kMlpMaxLinear], dhx[kMlpMaxLinear];
+    MlpTape tape;
+    MlpTrainSlots keep;
     long long y, dy, partial, loss, total;
 };
-
-// per dropout site (0: inputs, i + 1: after the activation of Linear i): keep iff word >= thr; kept values times scale
-struct DropPlan {
-    int on;
-    unsigned thr[kMlpMaxLinear + 1];
-    double scale[kMlpMaxLinear + 1];
-    unsigned k0, k1, step;
-};
-
-// Dropout of frame j's row (slot `slot`) at site `site`, forward and adjoint alike: row[f] *= keep ? scale : 0.
-// Lane g takes the column blocks g, g + 4, ... of four columns, one Philox call each; the caller synchronises
-// the wave before and after (the lanes of a row own other entries outside this function).
-__device__ __forceinline__ void mlp_dropout(double* row, int g, int w, const DropPlan& d, int site, unsigned slot) {
-    const Philox rng{d.k0, d.k1};
-    const unsigned thr = d.thr[site];
-    const double scale = d.scale[site];
-    for (int cb = g; 4 * cb < w; cb += 4) {
-        uint32_t c[4] = {d.step, (uint32_t)site, slot, (uint32_t)cb};
-        rng(c);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int f = 4 * cb + u;
-            if (f < w) row[f] = row[f] * (c[u] >= thr ? scale : 0.0);
-        }
-    }
-}
 
 // src[0] + src[stride] + ... (nr terms), added in ascending order; the loads of eight terms go out together, the
 // additions keep their order, so the bits are those of the plain loop
@@ -93,7 +58,6 @@ __global__ __launch_bounds__(64) void mlp_train_forward_kernel(
     double* img[2];
     img[0] = reinterpret_cast<double*>(mlp_smem);
     img[1] = img[0] + 16 * p.stride[0];
-    const int F = p.width[0];
     const int n_out = p.width[p.n_linear];
     const int S2 = 2 * m;
     const int n_groups = (S2 + 15) / 16;
@@ -101,72 +65,15 @@ __global__ __launch_bounds__(64) void mlp_train_forward_kernel(
         const int s0 = grp * 16;
         const int rows = min(16, S2 - s0);
         WAVE_SYNC();   // the previous group's rows have been read
-        // Z as in mlp_forward_kernel, of the row the slot names; a slot past 2m, or one whose index lies outside
-        // [0, n), is not read: the first enters as zeros, the second as NaN (all its outputs are NaN)
-        const int S = p.stride[0];
-        for (int r = 0; r < 16; ++r) {
-            int64_t row = -1;
-            if (r < rows) {
-                const int s = s0 + r;
-                row = s < m ? idx_t[s] : idx_tau[s - m];
-            }
-            const bool inside = row >= 0 && row < n;
-            for (int f = lane; f < F; f += 64) {
-                double z = 0.0;
-                if (inside) {
-                    z = (double)x[row * ld + f];
-                    if (sc_mean) z = (z - sc_mean[f]) / sc_scale[f];
-                    z = (double)(float)z;
-                } else if (r < rows) {
-                    z = __longlong_as_double(0x7ff8000000000000ll);
-                }
-                img[0][r * S + f] = z;
-            }
-        }
-        WAVE_SYNC();
-        if (lay.z >= 0) save_rows(img[0], S, F, rows, ws + lay.z + (size_t)s0 * F, lane);
-        double* cur = img[0] + j * S;   // frame j's row, current and next layer
-        double* nxt = img[1] + j * p.stride[1];
-        int bad = 0;                    // a non-finite Z anywhere in the frame: all its outputs are NaN
-        for (int f = g; f < F; f += 4) bad |= !(fabs(cur[f]) <= DBL_MAX);
-        bad = xrow_reduce(bad, op_or{});
-        if (p.ln_in_off >= 0) mlp_layer_norm(cur, g, F, params + p.ln_in_off);
-        if (drop.on && drop.thr[0]) {
-            WAVE_SYNC();
-            mlp_dropout(cur, g, F, drop, 0, (unsigned)(s0 + j));
-        }
-        WAVE_SYNC();
-        save_rows(img[0], S, F, rows, ws + lay.a[0] + (size_t)s0 * F, lane);
-
-        for (int l = 0; l < p.n_linear; ++l) {
-            const int K = p.width[l], N = p.width[l + 1];
-            const int Sn = p.stride[(l + 1) & 1];
-            double* image = img[(l + 1) & 1];
-            WAVE_SYNC();   // the rows of `cur` are complete: every lane reads entries other lanes wrote
-            mlp_linear(cur, nxt, params + p.w_off[l], params + p.b_off[l], K, N, j, g);
-            const bool last = l == p.n_linear - 1;
-            if (!last && p.ln_off[l] >= 0) {
-                WAVE_SYNC();
-                save_rows(image, Sn, N, rows, ws + lay.u[l] + (size_t)s0 * N, lane);
-                mlp_layer_norm(nxt, g, N, params + p.ln_off[l]);
-            }
-            if (!last || p.head_activation) {
-                WAVE_SYNC();
-                save_rows(image, Sn, N, rows, ws + lay.h[l] + (size_t)s0 * N, lane);
-                for (int f = g; f < N; f += 4) nxt[f] = mlp_activate(nxt[f], p.activation);
-            }
-            if (!last) {
-                if (drop.on && drop.thr[l + 1]) {
-                    WAVE_SYNC();
-                    mlp_dropout(nxt, g, N, drop, l + 1, (unsigned)(s0 + j));
-                }
-                WAVE_SYNC();
-                save_rows(image, Sn, N, rows, ws + lay.a[l + 1] + (size_t)s0 * N, lane);
-            }
-            double* swap = cur;
-            cur = nxt;
-            nxt = swap;
-        }
+        // the row of x a slot names; one whose index lies outside [0, n) is not read and enters as NaN
+        mlp_load_inputs(img[0], p.stride[0], p.width[0], lane, rows, x, ld, sc_mean, sc_scale, [&](int r) {
+            const int s = s0 + r;
+            const int64_t row = s < m ? idx_t[s] : idx_tau[s - m];
+            return row < n ? row : (int64_t)-1;
+        });
+        int bad;
+        const double* cur = mlp_forward_walk<true, true>(p, params, img, lane, rows,
+                                                         MlpKeep{&lay.tape, &lay.keep, &drop, ws, (size_t)s0}, &bad);
         if (j < rows) {
             const double qnan = __longlong_as_double(0x7ff8000000000000ll);
             for (int c = g; c < n_out; c += 4) ws[lay.y + (size_t)(s0 + j) * n_out + c] = bad ? qnan : cur[c];
@@ -204,35 +111,16 @@ __global__ __launch_bounds__(64) void mlp_train_backward_kernel(const float* __r
             const int So = p.stride[(l + 1) & 1];
             double* gout = img[(l + 1) & 1] + j * So;        // dL/d(output of layer l), then du_l
             double* gin = img[l & 1] + j * p.stride[l & 1];  // dL/d(input of layer l)
-            const bool last = l == L - 1;
-            if (!last && drop.on && drop.thr[l + 1]) {
+            if (l < L - 1 && drop.on && drop.thr[l + 1]) {
                 WAVE_SYNC();
                 mlp_dropout(gout, g, N, drop, l + 1, (unsigned)(s0 + j));
             }
             WAVE_SYNC();
-            if (!last || p.head_activation) {
-                const double* __restrict__ h = ws + lay.h[l] + slot * N;
-                for (int f = g; f < N; f += 4) gout[f] = gout[f] * mlp_activate_grad(h[f], p.activation);
-            }
-            if (!last && p.ln_off[l] >= 0)
-                mlp_layer_norm_adjoint(gout, g, N, ws + lay.u[l] + slot * N, params + p.ln_off[l],
-                                       ws + lay.dh[l] + slot * N, ws + lay.dhx[l] + slot * N, mine);
+            mlp_layer_adjoint<true>(gout, g, p, l, params, lay.tape, &lay.keep, ws, slot, mine);
             WAVE_SYNC();
-            save_rows(img[(l + 1) & 1], So, N, rows, ws + lay.du[l] + (size_t)s0 * N, lane);
+            save_rows(img[(l + 1) & 1], So, N, rows, ws + lay.keep.du[l] + (size_t)s0 * N, lane);
             if (l == 0 && p.ln_in_off < 0) break;            // nothing upstream of the first Linear has parameters
-            // dL/d(input) = du . W: entry (k, frame j) = sum_n W[n][k] du[frame j][n]
-            const float* __restrict__ W = params + p.w_off[l];
-            for (int k0 = 0; k0 < K; k0 += 16) {
-                const int kc = min(k0 + j, K - 1);
-                const v4f64 acc = mfma_tile_acc(
-                    N, g, k0 + j < K, true, [&](int nn) { return (double)W[(size_t)nn * K + kc]; },
-                    [&](int nn) { return gout[nn]; });
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int k = k0 + g + 4 * r;
-                    if (k < K) gin[k] = acc[r];
-                }
-            }
+            mlp_linear_transposed(gout, gin, params + p.w_off[l], K, N, j, g);
         }
         if (p.ln_in_off >= 0) {
             const int F = p.width[0];
@@ -242,8 +130,8 @@ __global__ __launch_bounds__(64) void mlp_train_backward_kernel(const float* __r
                 mlp_dropout(gin, g, F, drop, 0, (unsigned)(s0 + j));
             }
             WAVE_SYNC();
-            mlp_layer_norm_adjoint(gin, g, F, ws + lay.z + slot * F, params + p.ln_in_off, ws + lay.dz + slot * F,
-                                   ws + lay.dzx + slot * F, mine);
+            mlp_layer_norm_adjoint(gin, g, F, ws + lay.tape.z + slot * F, params + p.ln_in_off,
+                                   ws + lay.keep.dz + slot * F, ws + lay.keep.dzx + slot * F, mine);
         }
     }
 }
@@ -270,9 +158,9 @@ __global__ __launch_bounds__(64) void mlp_train_param_partial_kernel(MlpPlan p, 
     };
     if (p.ln_in_off >= 0) {
         const int F = p.width[0], nb = (F + 63) / 64;
-        if (job < nb) return colsum(lay.dzx, F, p.ln_in_off, job);
+        if (job < nb) return colsum(lay.keep.dzx, F, p.ln_in_off, job);
         job -= nb;
-        if (job < nb) return colsum(lay.dz, F, p.ln_in_off + F, job);
+        if (job < nb) return colsum(lay.keep.dz, F, p.ln_in_off + F, job);
         job -= nb;
     }
     for (int l = 0; l < p.n_linear; ++l) {
@@ -280,8 +168,8 @@ __global__ __launch_bounds__(64) void mlp_train_param_partial_kernel(MlpPlan p, 
         const int tk = (K + 15) / 16, tn = (N + 15) / 16, nb = (N + 63) / 64;
         if (job < tn * tk) {   // dW[n][k] = sum over slots of du[slot][n] a[slot][k]
             const int n0 = (job / tk) * 16, k0 = (job % tk) * 16;
-            const double* __restrict__ du = ws + lay.du[l] + (size_t)r0 * N + min(n0 + j, N - 1);
-            const double* __restrict__ a = ws + lay.a[l] + (size_t)r0 * K + min(k0 + j, K - 1);
+            const double* __restrict__ du = ws + lay.keep.du[l] + (size_t)r0 * N + min(n0 + j, N - 1);
+            const double* __restrict__ a = ws + lay.keep.a[l] + (size_t)r0 * K + min(k0 + j, K - 1);
             const v4f64 acc = mfma_tile_acc(
                 nr, g, n0 + j < N, k0 + j < K, [&](int r) { return du[(size_t)r * N]; },
                 [&](int r) { return a[(size_t)r * K]; });
@@ -293,12 +181,12 @@ __global__ __launch_bounds__(64) void mlp_train_param_partial_kernel(MlpPlan p, 
             return;
         }
         job -= tn * tk;
-        if (job < nb) return colsum(lay.du[l], N, p.b_off[l], job);
+        if (job < nb) return colsum(lay.keep.du[l], N, p.b_off[l], job);
         job -= nb;
         if (p.ln_off[l] >= 0) {
-            if (job < nb) return colsum(lay.dhx[l], N, p.ln_off[l], job);
+            if (job < nb) return colsum(lay.keep.dhx[l], N, p.ln_off[l], job);
             job -= nb;
-            if (job < nb) return colsum(lay.dh[l], N, p.ln_off[l] + N, job);
+            if (job < nb) return colsum(lay.keep.dh[l], N, p.ln_off[l] + N, job);
             job -= nb;
         }
     }
@@ -423,10 +311,16 @@ __global__ __launch_bounds__(192) void vamp2_wsum_kernel(const double* __restric
     else wsum[(size_t)blockIdx.x * 2 + (sq ? 1 : 0)] = s;
 }
 
-// one 16 x 16 tile of the centred second moments of one chunk: matrix q = 0: Y0'Y0, 1: Yt'Yt, 2: Y0'Yt
+// One 16 x 16 tile of the centred second moments of one chunk: matrix q = 0: Y0'Y0, 1: Yt'Yt, 2: Y0'Yt.  WEIGHTED:
+// the tile of sum_s w'_s (a_s - mean_a)(b_s - mean_b) with the weighted means (the sums over the total weight W instead
+// of m); the first operand carries w'_s, the division by W is the solve's.  A row past the chunk's end is fed as zero
+// and its weight is not read (mfma_tile_acc asks for row 0 in its place).  Without weights wts and wsum are not read.
+template <bool WEIGHTED>
 __global__ __launch_bounds__(64) void vamp2_moments_kernel(const double* __restrict__ y0, const double* __restrict__ yt,
-                                                           int m, int d, int64_t ld, const double* __restrict__ psum,
-                                                           int chunks, double* __restrict__ pmom) {
+                                                           const double* __restrict__ wts, int m, int d, int64_t ld,
+                                                           const double* __restrict__ psum,
+                                                           const double* __restrict__ wsum, int chunks,
+                                                           double* __restrict__ pmom) {
     const int lane = threadIdx.x;
     const int j = lane & 15, g = lane >> 4;
     const int T = (d + 15) / 16;
@@ -435,45 +329,19 @@ __global__ __launch_bounds__(64) void vamp2_moments_kernel(const double* __restr
     const int r0 = blockIdx.y * kChunk, nr = min(kChunk, m - r0);
     const int ia = min(i0 + j, d - 1), ib = min(c0 + j, d - 1);
     const bool a_tau = q == 1, b_tau = q != 0;
-    const double ma = vamp_mean(psum, chunks, d, (double)m, ia + (a_tau ? d : 0));
-    const double mb = vamp_mean(psum, chunks, d, (double)m, ib + (b_tau ? d : 0));
+    const double div = WEIGHTED ? vamp_weight_total(wsum, chunks, 0) : (double)m;
+    const double ma = vamp_mean(psum, chunks, d, div, ia + (a_tau ? d : 0));
+    const double mb = vamp_mean(psum, chunks, d, div, ib + (b_tau ? d : 0));
     const double* __restrict__ A = (a_tau ? yt : y0) + (size_t)r0 * ld + ia;
     const double* __restrict__ B = (b_tau ? yt : y0) + (size_t)r0 * ld + ib;
+    const double* __restrict__ wq = WEIGHTED ? wts + r0 : nullptr;
     const v4f64 acc = mfma_tile_acc(
-        nr, g, i0 + j < d, c0 + j < d, [&](int r) { return A[(size_t)r * ld] - ma; },
-        [&](int r) { return B[(size_t)r * ld] - mb; });
-    double* __restrict__ out = pmom + ((size_t)blockIdx.y * 3 + q) * d * d;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int i = i0 + g + 4 * r;
-        if (i < d && c0 + j < d) out[i * d + c0 + j] = acc[r];
-    }
-}
-
-// vamp2_moments_kernel under weights: the tile of sum_s w'_s (a_s - mean_a)(b_s - mean_b) over one chunk with the
-// weighted means; the first operand carries w'_s, the division by W is the solve's.  A row past the chunk's end is
-// fed as zero and its weight is not read (mfma_tile_acc asks for row 0 in its place).
-__global__ __launch_bounds__(64) void vamp2_wmoments_kernel(const double* __restrict__ y0, const double* __restrict__ yt,
-                                                            const double* __restrict__ wts, int m, int d, int64_t ld,
-                                                            const double* __restrict__ psum,
-                                                            const double* __restrict__ wsum, int chunks,
-                                                            double* __restrict__ pmom) {
-    const int lane = threadIdx.x;
-    const int j = lane & 15, g = lane >> 4;
-    const int T = (d + 15) / 16;
-    const int q = blockIdx.x / (T * T), tile = blockIdx.x % (T * T);
-    const int i0 = (tile / T) * 16, c0 = (tile % T) * 16;
-    const int r0 = blockIdx.y * kChunk, nr = min(kChunk, m - r0);
-    const int ia = min(i0 + j, d - 1), ib = min(c0 + j, d - 1);
-    const bool a_tau = q == 1, b_tau = q != 0;
-    const double W = vamp_weight_total(wsum, chunks, 0);
-    const double ma = vamp_mean(psum, chunks, d, W, ia + (a_tau ? d : 0));
-    const double mb = vamp_mean(psum, chunks, d, W, ib + (b_tau ? d : 0));
-    const double* __restrict__ A = (a_tau ? yt : y0) + (size_t)r0 * ld + ia;
-    const double* __restrict__ B = (b_tau ? yt : y0) + (size_t)r0 * ld + ib;
-    const double* __restrict__ wq = wts + r0;
-    const v4f64 acc = mfma_tile_acc(
-        nr, g, i0 + j < d, c0 + j < d, [&](int r) { return vamp_weight(wq[r]) * (A[(size_t)r * ld] - ma); },
+        nr, g, i0 + j < d, c0 + j < d,
+        [&](int r) {
+            const double a = A[(size_t)r * ld] - ma;
+            if constexpr (WEIGHTED) return vamp_weight(wq[r]) * a;
+            else return a;
+        },
         [&](int r) { return B[(size_t)r * ld] - mb; });
     double* __restrict__ out = pmom + ((size_t)blockIdx.y * 3 + q) * d * d;
 #pragma unroll
@@ -769,10 +637,13 @@ __global__ __launch_bounds__(kSolveThreads) void vamp2_solve_kernel(int m, int d
     }
 }
 
-// dL/dZ0 = (2 Y0c G00 + Ytc G0t') / m, dL/dZt = (2 Ytc Gtt + Y0c G0t) / m with centred outputs; one thread per entry
+// dL/dZ0 = (2 Y0c G00 + Ytc G0t') / m, dL/dZt = (2 Ytc Gtt + Y0c G0t) / m with centred outputs; one thread per entry.
+// WEIGHTED: pair s carries w'_s / W (wtot[0], left by the solve) instead of 1 / m; else wts and wtot are not read.
+template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void vamp2_grad_kernel(const double* __restrict__ y0, const double* __restrict__ yt,
-                                                         int m, int d, int64_t ld, const double* __restrict__ G,
-                                                         const double* __restrict__ mean, double* __restrict__ g0,
+                                                         const double* __restrict__ wts, int m, int d, int64_t ld,
+                                                         const double* __restrict__ G, const double* __restrict__ mean,
+                                                         const double* __restrict__ wtot, double* __restrict__ g0,
                                                          double* __restrict__ gt, int64_t ldg) {
     const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= (long long)m * d) return;
@@ -788,33 +659,14 @@ __global__ __launch_bounds__(256) void vamp2_grad_kernel(const double* __restric
         at += vt * Gtt[k * d + c];
         bt += v0 * G0t[k * d + c];
     }
-    g0[s * ldg + c] = (2.0 * a0 + b0) / (double)m;
-    gt[s * ldg + c] = (2.0 * at + bt) / (double)m;
-}
-
-// vamp2_grad_kernel under weights: pair s carries w'_s / W (wtot[0], left by the solve) instead of 1 / m
-__global__ __launch_bounds__(256) void vamp2_wgrad_kernel(const double* __restrict__ y0, const double* __restrict__ yt,
-                                                          const double* __restrict__ wts, int m, int d, int64_t ld,
-                                                          const double* __restrict__ G, const double* __restrict__ mean,
-                                                          const double* __restrict__ wtot, double* __restrict__ g0,
-                                                          double* __restrict__ gt, int64_t ldg) {
-    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= (long long)m * d) return;
-    const int64_t s = e / d;
-    const int c = (int)(e - s * d);
-    const long long dd = (long long)d * d;
-    const double* G00 = G, *Gtt = G + dd, *G0t = G + 2 * dd;
-    double a0 = 0.0, b0 = 0.0, at = 0.0, bt = 0.0;
-    for (int k = 0; k < d; ++k) {
-        const double v0 = y0[s * ld + k] - mean[k], vt = yt[s * ld + k] - mean[d + k];
-        a0 += v0 * G00[k * d + c];
-        b0 += vt * G0t[c * d + k];
-        at += vt * Gtt[k * d + c];
-        bt += v0 * G0t[k * d + c];
+    if constexpr (WEIGHTED) {
+        const double what = vamp_weight(wts[s]) / wtot[0];
+        g0[s * ldg + c] = what * (2.0 * a0 + b0);
+        gt[s * ldg + c] = what * (2.0 * at + bt);
+    } else {
+        g0[s * ldg + c] = (2.0 * a0 + b0) / (double)m;
+        gt[s * ldg + c] = (2.0 * at + bt) / (double)m;
     }
-    const double what = vamp_weight(wts[s]) / wtot[0];
-    g0[s * ldg + c] = what * (2.0 * a0 + b0);
-    gt[s * ldg + c] = what * (2.0 * at + bt);
 }
 
 // wts: the pairs' weights [m], or NULL for uniform weights (work is then vamp_work(m, d), else vamp_work(m, d, true))
@@ -822,17 +674,17 @@ msm_status vamp2_launch(msm_ctx* ctx, const double* y0, const double* yt, const 
                         const VampOpts& o, double* work, double* stats, double* g0, double* gt, int64_t ldg) {
     const VampWork w = vamp_work(m, d, wts != nullptr);
     const int T = (d + 15) / 16;
-    if (wts) {
+    const double* wsum = wts ? work + w.wsum : nullptr;
+    const double* wtot = wts ? work + w.wtot : nullptr;
+    if (wts)
         hipLaunchKernelGGL(vamp2_wsum_kernel, dim3(w.chunks), dim3(192), 0, ctx->stream, y0, yt, wts, m, d, ld,
                            work + w.psum, work + w.wsum);
-        hipLaunchKernelGGL(vamp2_wmoments_kernel, dim3(3 * T * T, w.chunks), dim3(64), 0, ctx->stream, y0, yt, wts, m, d,
-                           ld, work + w.psum, work + w.wsum, w.chunks, work + w.pmom);
-    } else {
+    else
         hipLaunchKernelGGL(vamp2_colsum_kernel, dim3(w.chunks), dim3(128), 0, ctx->stream, y0, yt, m, d, ld,
                            work + w.psum);
-        hipLaunchKernelGGL(vamp2_moments_kernel, dim3(3 * T * T, w.chunks), dim3(64), 0, ctx->stream, y0, yt, m, d, ld,
-                           work + w.psum, w.chunks, work + w.pmom);
-    }
+    auto moments = wts ? vamp2_moments_kernel<true> : vamp2_moments_kernel<false>;
+    hipLaunchKernelGGL(moments, dim3(3 * T * T, w.chunks), dim3(64), 0, ctx->stream, y0, yt, wts, m, d, ld,
+                       work + w.psum, wsum, w.chunks, work + w.pmom);
     const size_t lds = (size_t)2 * d * d * sizeof(double);   // <= 64 KiB
     if (lds > 48 * 1024)
         MSM_HIP(ctx, hipFuncSetAttribute((const void*)vamp2_solve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -841,12 +693,9 @@ msm_status vamp2_launch(msm_ctx* ctx, const double* y0, const double* yt, const 
     if (g0) {
         const long long total = (long long)m * d;
         const dim3 grid((unsigned)((total + 255) / 256));
-        if (wts)
-            hipLaunchKernelGGL(vamp2_wgrad_kernel, grid, dim3(256), 0, ctx->stream, y0, yt, wts, m, d, ld, work + w.G,
-                               work + w.mean, work + w.wtot, g0, gt, ldg);
-        else
-            hipLaunchKernelGGL(vamp2_grad_kernel, grid, dim3(256), 0, ctx->stream, y0, yt, m, d, ld, work + w.G,
-                               work + w.mean, g0, gt, ldg);
+        auto grad = wts ? vamp2_grad_kernel<true> : vamp2_grad_kernel<false>;
+        hipLaunchKernelGGL(grad, grid, dim3(256), 0, ctx->stream, y0, yt, wts, m, d, ld, work + w.G, work + w.mean,
+                           wtot, g0, gt, ldg);
     }
     MSM_CHECK_LAUNCH(ctx);
     return MSM_OK;
@@ -855,38 +704,16 @@ msm_status vamp2_launch(msm_ctx* ctx, const double* y0, const double* yt, const 
 TrainLayout train_layout(const MlpPlan& p, int m, size_t n_params, bool weighted = false) {
     TrainLayout t;
     const long long S2 = 2LL * m;
-    long long off = 0;
-    auto take = [&](long long w) {
-        const long long at = off;
-        off += S2 * w;
-        return at;
-    };
-    const int F = p.width[0], L = p.n_linear;
-    t.z = t.dz = t.dzx = -1;
-    if (p.ln_in_off >= 0) {
-        t.z = take(F);
-        t.dz = take(F);
-        t.dzx = take(F);
-    }
-    for (int l = 0; l < kMlpMaxLinear; ++l) t.a[l] = t.h[l] = t.u[l] = t.du[l] = t.dh[l] = t.dhx[l] = -1;
-    for (int l = 0; l < L; ++l) {
-        const int K = p.width[l], N = p.width[l + 1];
-        const bool last = l == L - 1;
-        t.a[l] = take(K);
-        t.du[l] = take(N);
-        if (!last || p.head_activation) t.h[l] = take(N);
-        if (!last && p.ln_off[l] >= 0) {
-            t.u[l] = take(N);
-            t.dh[l] = take(N);
-            t.dhx[l] = take(N);
-        }
-    }
-    t.y = take(p.width[L]);
-    t.dy = take(p.width[L]);
+    const int n_out = p.width[p.n_linear];
+    long long off = mlp_tape_layout(p, S2, &t.tape, &t.keep);
+    t.y = off;
+    off += S2 * n_out;
+    t.dy = off;
+    off += S2 * n_out;
     t.partial = off;
     off += (long long)((S2 + kChunk - 1) / kChunk) * (long long)n_params;
     t.loss = off;
-    off += vamp_work(m, p.width[L], weighted).total;
+    off += vamp_work(m, n_out, weighted).total;
     t.total = off;
     return t;
 }

@@ -2,13 +2,12 @@
 // potential of a trained network (msm_bias_energy_forces).  The law: include/msmhip.h.
 //
 // One launch does both passes.  As in mlp.hip a workgroup is one wave that owns 16 frames whose rows sit in two LDS
-// images.  The forward pass is mlp_forward_kernel's instruction sequence (the outputs agree bit for bit) and leaves
-// per frame, in the workspace, what the adjoints need: z (the scaled inputs, when an input LayerNorm follows), u[l]
-// (the output of Linear l when a LayerNorm follows) and h[l] (the value the activation is applied to) -- the tape of
-// mlp_train.hip without a[l], which only parameter gradients read.  The backward pass of the same 16 frames follows at
-// once, so the tape comes back from L2: the adjoints of mlp_train_backward_kernel with dropout off, carried on past
-// the first Linear (dA_0 = du_0 . W_0), through the input LayerNorm, to dx = dZ / scale (the fp32 rounding of Z is
-// the identity for the derivative).
+// images.  The forward pass is the shared walk (mlp_forward_walk, mlp_common.h: the outputs agree with
+// mlp_forward_kernel's bit for bit) with the tape switched on: per frame, in the workspace, what the adjoints need
+// (MlpTape: z, u[l], h[l]; not a[l], which only parameter gradients read).  The backward pass of the same 16 frames
+// follows at once, so the tape comes back from L2: the shared adjoints (mlp_layer_adjoint, mlp_linear_transposed) with
+// nothing stored for parameter gradients, carried on past the first Linear (dA_0 = du_0 . W_0), through the input
+// LayerNorm, to dx = dZ / scale (the fp32 rounding of Z is the identity for the derivative).
 //
 // The wave reads tape rows that other lanes of it wrote to global memory; WAVE_SYNC's wavefront-scope fence orders
 // them.  Nothing depends on the launch geometry: a frame's results are a function of that frame's inputs, bit for bit.
@@ -16,30 +15,9 @@
 
 namespace {
 
-// where the tape lies in the workspace (offsets in doubles; -1: absent): [n, width] each; travels by value
-struct VjpLayout {
-    long long z;
-    long long h[kMlpMaxLinear], u[kMlpMaxLinear];
-    long long total;
-};
-
-VjpLayout vjp_layout(const MlpPlan& p, int64_t n) {
-    VjpLayout t;
-    long long off = 0;
-    auto take = [&](long long w) {
-        const long long at = off;
-        off += (long long)n * w;
-        return at;
-    };
-    t.z = p.ln_in_off >= 0 ? take(p.width[0]) : -1;
-    for (int l = 0; l < kMlpMaxLinear; ++l) t.h[l] = t.u[l] = -1;
-    for (int l = 0; l < p.n_linear; ++l) {
-        const bool last = l == p.n_linear - 1;
-        if (!last && p.ln_off[l] >= 0) t.u[l] = take(p.width[l + 1]);
-        if (!last || p.head_activation) t.h[l] = take(p.width[l + 1]);
-    }
-    t.total = std::max(off, 1LL);
-    return t;
+// the workspace is the tape of the n frames; a network without one still gets a pointer to something
+size_t vjp_tape_bytes(const MlpPlan& p, int64_t n, MlpTape* lay) {
+    return (size_t)std::max(mlp_tape_layout(p, n, lay), 1LL) * sizeof(double);
 }
 
 template <typename T>
@@ -47,7 +25,7 @@ __global__ __launch_bounds__(64, 2) void mlp_vjp_kernel(
     const T* __restrict__ x, int64_t n, int64_t ld, const double* __restrict__ sc_mean,
     const double* __restrict__ sc_scale, const float* __restrict__ params, MlpPlan p,
     const double* __restrict__ gup, int64_t ldgo, double strength, double* __restrict__ energy,
-    double* __restrict__ out, int64_t ldo, double* __restrict__ gx, int64_t ldgx, VjpLayout lay, double* ws) {
+    double* __restrict__ out, int64_t ldo, double* __restrict__ gx, int64_t ldgx, MlpTape lay, double* ws) {
     extern __shared__ __attribute__((aligned(16))) unsigned char mlp_smem[];
     const int lane = threadIdx.x;
     const int j = lane & 15, g = lane >> 4;
@@ -65,47 +43,11 @@ __global__ __launch_bounds__(64, 2) void mlp_vjp_kernel(
         const bool mine = j < rows;                               // frame j exists
         const int64_t t = min<int64_t>(t0 + j, n - 1);            // reads of a frame past n are clamped, its writes dropped
         WAVE_SYNC();   // the previous group's rows have been read
-        // ---- forward: mlp_forward_kernel, with the tape ----
-        const int S = p.stride[0];
-        for (int r = 0; r < 16; ++r)
-            for (int f = lane; f < F; f += 64) {
-                double z = 0.0;
-                if (r < rows) {
-                    z = (double)x[(t0 + r) * ld + f];
-                    if (sc_mean) z = (z - sc_mean[f]) / sc_scale[f];
-                    z = (double)(float)z;
-                }
-                img[0][r * S + f] = z;
-            }
-        WAVE_SYNC();
-        if (lay.z >= 0) save_rows(img[0], S, F, rows, ws + lay.z + (size_t)t0 * F, lane);
-        double* cur = img[0] + j * S;
-        double* nxt = img[1] + j * p.stride[1];
-        int bad = 0;                  // a non-finite Z anywhere in the frame: everything of the frame is NaN
-        for (int f = g; f < F; f += 4) bad |= !(fabs(cur[f]) <= DBL_MAX);
-        bad = xrow_reduce(bad, op_or{});
-        if (p.ln_in_off >= 0) mlp_layer_norm(cur, g, F, params + p.ln_in_off);
-        for (int l = 0; l < L; ++l) {
-            const int K = p.width[l], N = p.width[l + 1];
-            const int Sn = p.stride[(l + 1) & 1];
-            double* image = img[(l + 1) & 1];
-            WAVE_SYNC();   // the rows of `cur` are complete: every lane reads entries other lanes wrote
-            mlp_linear(cur, nxt, params + p.w_off[l], params + p.b_off[l], K, N, j, g);
-            const bool last = l == L - 1;
-            if (!last && p.ln_off[l] >= 0) {
-                WAVE_SYNC();
-                save_rows(image, Sn, N, rows, ws + lay.u[l] + (size_t)t0 * N, lane);
-                mlp_layer_norm(nxt, g, N, params + p.ln_off[l]);
-            }
-            if (!last || p.head_activation) {
-                WAVE_SYNC();
-                save_rows(image, Sn, N, rows, ws + lay.h[l] + (size_t)t0 * N, lane);
-                for (int f = g; f < N; f += 4) nxt[f] = mlp_activate(nxt[f], p.activation);
-            }
-            double* swap = cur;
-            cur = nxt;
-            nxt = swap;
-        }
+        // ---- forward, with the tape; `bad`, a non-finite Z anywhere in the frame: everything of the frame is NaN ----
+        mlp_load_inputs(img[0], p.stride[0], F, lane, rows, x, ld, sc_mean, sc_scale, [&](int r) { return t0 + r; });
+        int bad;
+        double* cur = mlp_forward_walk<true, false>(p, params, img, lane, rows,
+                                                    MlpKeep{&lay, nullptr, nullptr, ws, (size_t)t0}, &bad);
         // ---- outputs, energy, and the upstream gradient in place of the outputs ----
         double e = 0.0;
         for (int c = g; c < n_out; c += 4) e += cur[c] * cur[c];
@@ -117,36 +59,16 @@ __global__ __launch_bounds__(64, 2) void mlp_vjp_kernel(
         }
         for (int c = g; c < n_out; c += 4)
             cur[c] = !mine ? 0.0 : (gup ? gup[t * ldgo + c] : 2.0 * strength * cur[c]);
-        // ---- backward: mlp_train_backward_kernel without dropout, on to the inputs ----
+        // ---- backward: the adjoints of every layer, carried on past the first Linear to the inputs ----
         for (int l = L - 1; l >= 0; --l) {
-            const int K = p.width[l], N = p.width[l + 1];
             double* gout = img[(l + 1) & 1] + j * p.stride[(l + 1) & 1];   // dE/d(output of layer l), then du_l
             double* gin = img[l & 1] + j * p.stride[l & 1];                // dE/d(input of layer l)
-            const bool last = l == L - 1;
             WAVE_SYNC();   // the tape rows are in place, and so are the entries of gout other lanes wrote
-            if (!last || p.head_activation) {
-                const double* h = ws + lay.h[l] + (size_t)t * N;
-                for (int f = g; f < N; f += 4) gout[f] = gout[f] * mlp_activate_grad(h[f], p.activation);
-            }
-            if (!last && p.ln_off[l] >= 0)
-                mlp_layer_norm_adjoint(gout, g, N, ws + lay.u[l] + (size_t)t * N, params + p.ln_off[l], nullptr, nullptr,
-                                       false);
+            mlp_layer_adjoint<false>(gout, g, p, l, params, lay, nullptr, ws, (size_t)t, false);
             WAVE_SYNC();
-            // dE/d(input) = du . W: entry (k, frame j) = sum_n W[n][k] du[frame j][n]
-            const float* __restrict__ W = params + p.w_off[l];
-            for (int k0 = 0; k0 < K; k0 += 16) {
-                const int kc = min(k0 + j, K - 1);
-                const v4f64 acc = mfma_tile_acc(
-                    N, g, k0 + j < K, true, [&](int nn) { return (double)W[(size_t)nn * K + kc]; },
-                    [&](int nn) { return gout[nn]; });
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int k = k0 + g + 4 * r;
-                    if (k < K) gin[k] = acc[r];
-                }
-            }
+            mlp_linear_transposed(gout, gin, params + p.w_off[l], p.width[l], p.width[l + 1], j, g);
         }
-        double* gin = img[0] + j * S;
+        double* gin = img[0] + j * p.stride[0];
         if (p.ln_in_off >= 0) {
             WAVE_SYNC();
             mlp_layer_norm_adjoint(gin, g, F, ws + lay.z + (size_t)t * F, params + p.ln_in_off, nullptr, nullptr, false);
@@ -172,7 +94,8 @@ size_t msm_mlp_vjp_workspace(int64_t n, int n_linear, const int32_t* h_widths, i
     if (mlp_make_plan(nullptr, "msm_mlp_vjp_workspace", h_widths[0], n_linear, h_widths, 0, ln_in, ln_hidden,
                       head_activation, kMlpAnyParams, &p))
         return 0;
-    return (size_t)vjp_layout(p, n).total * sizeof(double);
+    MlpTape lay;
+    return vjp_tape_bytes(p, n, &lay);
 }
 
 msm_status msm_mlp_vjp(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n, int F, int64_t ld,
@@ -194,9 +117,9 @@ msm_status msm_mlp_vjp(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n
     MSM_REQUIRE(ctx, (d_mean == nullptr) == (d_scale == nullptr), "msm_mlp_vjp: scaler mean and scale go together");
     if (n == 0) return MSM_OK;
     MSM_REQUIRE(ctx, d_x && d_params && d_gx && d_work, "msm_mlp_vjp: NULL pointer");
-    const VjpLayout lay = vjp_layout(p, n);
-    MSM_REQUIRE(ctx, work_bytes >= (size_t)lay.total * sizeof(double), "msm_mlp_vjp: workspace of %zu bytes, %zu are needed",
-                work_bytes, (size_t)lay.total * sizeof(double));
+    MlpTape lay;
+    const size_t tape = vjp_tape_bytes(p, n, &lay);
+    MSM_REQUIRE(ctx, work_bytes >= tape, "msm_mlp_vjp: workspace of %zu bytes, %zu are needed", work_bytes, tape);
 
     MlpLaunch s;
     if (msm_status st = mlp_launch_shape(ctx, mlp_vjp_kernel_address(dtype), p, n, &s)) return st;
@@ -247,7 +170,8 @@ msm_status msm_bias_energy_forces(msm_ctx* ctx, const float* d_xyz, int64_t n, i
                 "%s: NULL pointer", who);
     MSM_REQUIRE(ctx, ((uintptr_t)d_rec & 15) == 0, "%s: the record table must be 16-byte aligned", who);
     const size_t fbytes = feature_bytes(n, F), gbytes = (size_t)n * F * sizeof(double);
-    const size_t tape = (size_t)vjp_layout(p, n).total * sizeof(double);
+    MlpTape lay;
+    const size_t tape = vjp_tape_bytes(p, n, &lay);
     MSM_REQUIRE(ctx, work_bytes >= fbytes + gbytes + tape, "%s: workspace of %zu bytes, %zu are needed", who, work_bytes,
                 fbytes + gbytes + tape);
     float* feats = reinterpret_cast<float*>(d_work);
