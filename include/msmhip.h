@@ -1322,7 +1322,9 @@ msm_status msm_reactive_flux_batched(msm_ctx* ctx, const double* d_T, int64_t t_
  * Replaces sklearn.metrics.silhouette_score in _auto_select_n_states (S/markov_state_model/
  * clustering.py:156-233).  d_x f64 [n, ld]: the points SORTED BY CLUSTER, cluster c = rows
  * [h_offsets[c], h_offsets[c+1]); 2 <= k <= 32.  d_samples f64 [n]: s_i = (b_i - a_i) / max(a_i,
- * b_i) (0 for singleton clusters); *d_score = mean s_i. */
+ * b_i) (0 for singleton clusters); *d_score = mean s_i.
+ * NaN rule, the one of msm_silhouette_samples below: non-finite coordinates are not dropped, the
+ * minimum in b_i and the maximum in the denominator keep NaN, and the score is then NaN. */
 msm_status msm_silhouette(msm_ctx* ctx, const double* d_x, int64_t n, int d, int64_t ld,
                           const int64_t* h_offsets, int k, double* d_samples, double* d_score);
 
@@ -1333,6 +1335,13 @@ msm_status msm_silhouette(msm_ctx* ctx, const double* d_x, int64_t n, int d, int
  * MSM_ERR_INVALID.  d_samples f64 [n] in frame order: s_i = (b_i - a_i) / max(a_i, b_i), 0 for
  * the member of a singleton cluster and where max(a_i, b_i) = 0; unused ids take no part in
  * b_i.  *d_score = mean s_i.
+ * NaN rule: a_i and the cluster means are ordinary IEEE sums; b_i is a minimum over the other
+ * clusters that have a member (decided by the counts) and max(a_i, b_i) a maximum, both of which
+ * keep a NaN operand; s_i = 0 only for a singleton, where no other cluster has a member and where
+ * max(a_i, b_i) = 0, otherwise (b_i - a_i) / max(a_i, b_i) as IEEE gives it.  One frame with a
+ * NaN coordinate so makes s_i NaN for itself, its cluster and every frame whose b_i would have
+ * to look at that cluster, and the score NaN: sklearn refuses such input, this says so in the
+ * result.  Finite input is untouched by the rule.
  * The frames are grouped on the device (msm_group_by_label), every cluster is cut into segments
  * of MSM_SIL_SEG_LEN members, workgroups of MSM_SIL_TILE_I query frames x a group of segments
  * write one partial distance sum per (query, segment), and a fold adds a cluster's pieces in
@@ -1386,7 +1395,10 @@ msm_status msm_relabel(msm_ctx* ctx, const int32_t* d_flat, int64_t n, const int
  *   (score, frame), in that order.  MSM_REP_SELECT_DIVERSE: the member with the smallest score
  *   (lowest frame on ties), then repeatedly the member farthest from everything picked so far
  *   (max-min walk, lowest frame on ties); d_scores holds centroid distances, d_mind f64 is workspace
- *   laid out like d_scores.  Uploads the state list: not capturable. */
+ *   laid out like d_scores.  A NaN never wins (np.argmin / np.argmax of the reference's host loop
+ *   return the first NaN): SMALLEST never picks a NaN score and ends the row in -1; in DIVERSE a NaN
+ *   score never wins the start (member 0 if all are NaN) and a NaN distance to a pick never wins a
+ *   round, the row ending in -1 once nothing else is left.  Uploads the state list: not capturable. */
 #define MSM_REP_MAX_D 256
 #define MSM_REP_GROUP_CHUNK 1024
 #define MSM_REP_TILE_I 128

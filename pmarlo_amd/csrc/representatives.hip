@@ -326,6 +326,8 @@ __global__ __launch_bounds__(kT) void select_smallest_kernel(const int32_t* __re
 // (scores = centroid distances), then mind_i = min(mind_i, |x_i - x_sel|) with the members already taken at -inf,
 // and the next pick is the arg-max of mind, the lowest frame on equal values.  mind is laid out like scores; a
 // thread touches only its own members' words, so the rounds need no ordering beyond the barriers of the arg-max.
+// A NaN never wins: a member whose distance to a pick is NaN keeps mind = NaN and is never picked; once only such
+// members are left the row ends in -1.
 __global__ __launch_bounds__(kT) void select_diverse_kernel(const double* __restrict__ x, int d, int64_t ld,
                                                             const int32_t* __restrict__ states,
                                                             const int64_t* __restrict__ offsets,
@@ -370,10 +372,12 @@ __global__ __launch_bounds__(kT) void select_diverse_kernel(const double* __rest
                     const double df = xi[f] - xs[f];
                     d2 = fma(df, df, d2);
                 }
-                v = fmin(v, sqrt(d2));
+                const double dist = sqrt(d2);
+                v = (dist < v || dist != dist) ? dist : v;   // a NaN distance stays in mind (fmin would drop it)
             }
             mind[o0 + m] = v;
-            if (v > best || (v == best && m < bi)) { best = v; bi = m; }
+            // a member already taken (-inf) is no candidate, so a round with nothing but NaN left finds no index
+            if (v != -INFINITY && (v > best || (v == best && m < bi))) { best = v; bi = m; }
         }
         block_argmax(best, bi, redv, redi);
         if (bi == INT_MAX) {   // every value NaN (NaN features): no index to follow, the same in every thread

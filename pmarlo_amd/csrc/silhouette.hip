@@ -41,6 +41,20 @@ constexpr int kTile = 64;
 
 struct SilOffsets { int64_t off[kMaxK + 1]; };
 
+// The NaN rule of both entry points.  A distance that is not a number (a NaN coordinate, inf - inf) makes the sums it
+// enters NaN; the minimum over the other clusters and the maximum in the denominator are compare-selects that keep a
+// NaN operand (fmin / fmax would drop it, and a poisoned cluster would silently leave b_i).  Whether another cluster
+// exists is read off the counts, never off b_i < inf.  s_i = 0 for the member of a singleton, where no other cluster
+// has a member, and where max(a_i, b_i) = 0; otherwise (b_i - a_i) / max(a_i, b_i) as IEEE gives it.  On finite
+// input every select takes the operand fmin / fmax took.
+__device__ __forceinline__ double nan_min(double run, double v) { return (v < run || v != v) ? v : run; }
+__device__ __forceinline__ double nan_max(double a, double b) { return (b > a || b != b) ? b : a; }
+__device__ __forceinline__ double sample_value(double a_i, double b_i, int64_t n_own, int64_t n) {
+    if (n_own <= 1 || n_own >= n) return 0.0;   // a singleton; no member outside i's cluster
+    const double den = nan_max(a_i, b_i);
+    return den == 0.0 ? 0.0 : (b_i - a_i) / den;
+}
+
 __global__ __launch_bounds__(kST) void silhouette_kernel(const double* __restrict__ x, int64_t n, int d, int64_t ld, int k,
                                                          SilOffsets so, double* __restrict__ s_out) {
     extern __shared__ double tile[];  // [kTile][d]
@@ -84,15 +98,10 @@ __global__ __launch_bounds__(kST) void silhouette_kernel(const double* __restric
         if (c < k) {
             const int64_t nc = so.off[c + 1] - so.off[c];
             if (c == ci) { n_ci = nc; a_i = nc > 1 ? acc[c] / (double)(nc - 1) : 0.0; }
-            else if (nc > 0) b_i = fmin(b_i, acc[c] / (double)nc);
+            else if (nc > 0) b_i = nan_min(b_i, acc[c] / (double)nc);
         }
     }
-    double s = 0.0;
-    if (n_ci > 1 && b_i < __builtin_inf()) {
-        const double den = fmax(a_i, b_i);
-        s = den > 0.0 ? (b_i - a_i) / den : 0.0;
-    }
-    s_out[i] = s;
+    s_out[i] = sample_value(a_i, b_i, n_ci, n);
 }
 
 __global__ __launch_bounds__(1024) void mean_kernel(const double* __restrict__ v, int64_t n, double* __restrict__ out) {
@@ -213,8 +222,8 @@ __global__ __launch_bounds__(kT) void silhouette_pairs_kernel(const double* __re
 // where s_i is formed instead.  A cluster without members has no segment and so takes no part in b_i.
 __global__ __launch_bounds__(kT) void silhouette_fold_kernel(const double* __restrict__ slab, const SilSeg* __restrict__ segs,
                                                              const int64_t* __restrict__ offsets,
-                                                             const int32_t* __restrict__ labels, int64_t q0, int qn,
-                                                             int s0, int s1, int n_seg, int64_t q_stride,
+                                                             const int32_t* __restrict__ labels, int64_t n, int64_t q0,
+                                                             int qn, int s0, int s1, int n_seg, int64_t q_stride,
                                                              double* __restrict__ state, double* __restrict__ s_out) {
     const int q = blockIdx.x * kT + threadIdx.x;
     if (q >= qn) return;
@@ -225,7 +234,7 @@ __global__ __launch_bounds__(kT) void silhouette_fold_kernel(const double* __res
     auto close = [&](int c) {
         const int64_t nc = offsets[c + 1] - offsets[c];
         if (c == ci) a_i = nc > 1 ? cur / (double)(nc - 1) : 0.0;
-        else b_i = fmin(b_i, cur / (double)nc);
+        else b_i = nan_min(b_i, cur / (double)nc);
         cur = 0.0;
     };
     for (int s = s0; s < s1; ++s) {
@@ -239,12 +248,7 @@ __global__ __launch_bounds__(kT) void silhouette_fold_kernel(const double* __res
         return;
     }
     if (c_prev >= 0) close(c_prev);
-    double sv = 0.0;
-    if (offsets[ci + 1] - offsets[ci] > 1 && b_i < __builtin_inf()) {
-        const double den = fmax(a_i, b_i);
-        sv = den > 0.0 ? (b_i - a_i) / den : 0.0;
-    }
-    s_out[q0 + q] = sv;
+    s_out[q0 + q] = sample_value(a_i, b_i, offsets[ci + 1] - offsets[ci], n);
 }
 
 // Mean in two steps over a fixed partition: block b sums v[b * per, (b + 1) * per) (thread t its strided share in
@@ -421,7 +425,7 @@ msm_status msm_silhouette_samples(msm_ctx* ctx, const double* d_x, int64_t n, in
                 ++gl;
             }
             hipLaunchKernelGGL(silhouette_fold_kernel, dim3(msm_ceil_div(qn, kT)), dim3(kT), 0, ctx->stream, slab, d_segs,
-                               offsets, d_labels, q0, qn, s0, s1, n_seg, plan.q_chunk, state, d_samples);
+                               offsets, d_labels, n, q0, qn, s0, s1, n_seg, plan.q_chunk, state, d_samples);
             MSM_CHECK_LAUNCH(ctx);
             g = g_end;
         }

@@ -131,7 +131,12 @@ def _auto_select_n_states(Y, random_state, *, sample_size, override_n_states, kw
                 best = (labels, inertia)
         lab = best[0]      # stays on the device; ids without members take no part in the score
         occupied = int(np.count_nonzero(eng.state_counts(lab, k).to_host()))
-        scores.append((k, eng.silhouette_samples(y64, lab, k)[0] if occupied > 1 else -1.0))
+        score = eng.silhouette_samples(y64, lab, k)[0] if occupied > 1 else -1.0
+        if not np.isfinite(score):
+            # sklearn's input check raises at this point in the reference; here the NaN rule of the kernels reports it
+            raise ValueError(f"n_states='auto': the silhouette score of the k = {k} candidate is {score}: the features "
+                             "contain non-finite values (NaN or infinity)")
+        scores.append((k, score))
     if not scores:
         raise ValueError("too few samples for the n_states='auto' scan (needs more than 4)")
     chosen, best = max(scores, key=lambda t: t[1])

@@ -12,7 +12,9 @@ import numpy as np
 def silhouette_samples_ref(X: np.ndarray, labels: np.ndarray, k: int | None = None, chunk: int = 512) -> np.ndarray:
     """s_i for dense ids 0 .. k-1 (an id may have no member): a_i = mean distance to the other members of i's
     cluster, b_i = smallest mean distance to the members of another non-empty cluster, s_i = (b_i - a_i) / max(a_i,
-    b_i); 0 for the member of a singleton cluster and where max(a_i, b_i) = 0."""
+    b_i); 0 for the member of a singleton cluster and where max(a_i, b_i) = 0.
+    NaN rule (include/msmhip.h): the sums are ordinary IEEE sums, the minimum in b_i and the maximum in the denominator
+    keep NaN, "another cluster exists" is decided by the counts; finite input gives the bits it always gave."""
     X = np.ascontiguousarray(X, np.float64)
     labels = np.asarray(labels).astype(np.int64)
     n, d = X.shape
@@ -29,9 +31,10 @@ def silhouette_samples_ref(X: np.ndarray, labels: np.ndarray, k: int | None = No
     for i0 in range(0, n, chunk):
         i1 = min(n, i0 + chunk)
         d2 = np.zeros((i1 - i0, n))
-        for f in range(d):
-            diff = X[i0:i1, f, None] - Xs[None, :, f]
-            d2 += diff * diff
+        with np.errstate(invalid="ignore", over="ignore"):
+            for f in range(d):
+                diff = X[i0:i1, f, None] - Xs[None, :, f]
+                d2 += diff * diff
         sums = np.add.reduceat(np.sqrt(d2), starts, axis=1)          # [m, occupied clusters]
         rows = np.arange(i1 - i0)
         own = col_of[labels[i0:i1]]
@@ -39,10 +42,11 @@ def silhouette_samples_ref(X: np.ndarray, labels: np.ndarray, k: int | None = No
         a = sums[rows, own] / np.maximum(n_own - 1, 1)
         mean = sums / counts[occupied][None, :]
         mean[rows, own] = np.inf
-        b = mean.min(axis=1)
+        b = mean.min(axis=1)                      # np.min and np.maximum keep NaN
         den = np.maximum(a, b)
-        ok = (n_own > 1) & np.isfinite(b) & (den > 0)
-        out[i0:i1] = np.where(ok, (b - a) / np.where(ok, den, 1.0), 0.0)
+        ok = (n_own > 1) & (occupied.size > 1) & ~(den == 0)
+        with np.errstate(invalid="ignore"):
+            out[i0:i1] = np.where(ok, (b - a) / np.where(ok, den, 1.0), 0.0)
     return out
 
 

@@ -52,3 +52,46 @@ def test_all_coincident_points_score_zero():
     X = np.full((6, 3), 2.5)
     s = silhouette_samples_ref(X, np.array([0, 0, 1, 1, 1, 2]), 3)
     np.testing.assert_array_equal(s, np.zeros(6))
+
+
+def test_restatement_keeps_nan():
+    """One NaN coordinate: its cluster does not vanish from the other frames' b_i, and the frame itself is not 0."""
+    rng = np.random.default_rng(1)
+    labels = np.repeat([0, 1, 2], [30, 30, 30])
+    X = rng.normal(size=(90, 2)) + 4.0 * labels[:, None]
+    X[40, 0] = np.nan
+    s = silhouette_samples_ref(X, labels, 3)
+    assert np.isnan(s).all() and np.isnan(s.mean())
+
+
+def test_auto_n_states_refuses_a_non_finite_score(monkeypatch):
+    """_auto_select_n_states raises where the reference raises through sklearn's input check: a candidate whose
+    silhouette score is not finite names the non-finite features.  The device is stood in for by a stub engine."""
+    from pmarlo_amd.markov_state_model import clustering
+
+    class _Arr:
+        dtype = np.dtype(np.float64)
+
+        def __init__(self, a):
+            self.a = a
+
+        def to_host(self):
+            return self.a
+
+    class _Engine:
+        def to_device(self, a):
+            return _Arr(np.asarray(a))
+
+        def state_counts(self, lab, k):
+            return _Arr(np.full(k, 5))
+
+        def silhouette_samples(self, y, lab, k):
+            return (0.5 if k < 6 else float("nan")), None
+
+    monkeypatch.setattr(clustering, "get_engine", lambda: _Engine())
+    monkeypatch.setattr(clustering, "MSMPipeline", lambda eng: None)
+    monkeypatch.setattr(clustering, "_fit_once", lambda *a, **kw: (None, None, 1.0))
+    Y = np.zeros((100, 2))
+    Y[3, 1] = np.nan
+    with pytest.raises(ValueError, match=r"k = 6 candidate is nan.*non-finite"):
+        clustering._auto_select_n_states(Y, 0, sample_size=None, override_n_states=None, kwargs={})
