@@ -1423,6 +1423,63 @@ msm_status msm_state_select(msm_ctx* ctx, const double* d_x, int64_t n, int d, i
                             const int32_t* d_members, int k, const double* d_scores, double* d_mind, int mode,
                             const int32_t* h_states, int n_states, int n_reps, int32_t* d_picks);
 
+/* ---- MBAR frame weights for multi-ensemble runs (csrc/mbar.hip) -------------------------------------
+ * The multistate Bennett acceptance ratio estimator, written from Shirts & Chodera, J. Chem. Phys. 129, 124105
+ * (2008); the reference snapshot holds no reweighter, so nothing is ported.  The tests hold the kernels to a numpy
+ * restatement of the rule below (tests/_mbar_ref.py), run in 80-bit floats.
+ *
+ * d_u [K, ld] f32 / f64, state-major: u[k, n] is the reduced potential of frame n in sampled state k, ld >= N.
+ * +inf is allowed (the frame is forbidden in that state); NaN and -inf are invalid.  d_f f64 [K] the current free
+ * energies, d_lnN f64 [K] = ln N_k.  1 <= K <= MSM_MBAR_MAX_K (MSM_ERR_UNSUPPORTED above), 1 <= N.
+ * msm_mbar_pass, per frame n, all in fp64:
+ *     m_n = min_k u_kn                                   (the per-frame shift: a no-op on W, d_n shifts back)
+ *     b_k = (f_k - (u_kn - m_n)) + lnN_k,   M = max_k b_k,   e_k = exp(b_k - M),   S = sum_k e_k  (ascending k)
+ *     d_n = (M + log S) - m_n               = logsumexp_k (f_k + ln N_k - u_kn), the log mixture denominator
+ *     W_kn = e_k * exp(-lnN_k) * (1 / S)    = exp(f_k - u_kn - d_n)
+ *   and over the frames  s_k = sum_n W_kn,  G_ij = sum_n W_in W_jn,  obj = sum_n d_n.
+ *   Outputs, all OVERWRITTEN: d_logden f64 [N] (may be NULL), d_s f64 [K], d_G f64 [K, K] (symmetric bit for bit;
+ *   NULL when !want_gram), d_obj f64 [1].  d_status int32 [1] is OR-ed into (the caller clears it): bit
+ *   MSM_MBAR_BAD_INPUT marks a NaN or -inf in u, bit MSM_MBAR_BAD_FRAME a frame whose d_n is not finite (forbidden in
+ *   every state); such a frame adds nothing to s, G and obj, and the caller must not use the results.
+ *   Launch shape: a workgroup of MSM_MBAR_THREADS lanes takes MSM_MBAR_THREADS frames per trip, one lane per frame,
+ *   in a grid-stride loop; the rows of u are read coalesced.  The workgroup's W slab [K, trip] goes through LDS; lane
+ *   k of every wave adds its wave's 64 columns of row k to s_k, and the upper 16 x 16 tiles of the Gram update (at most
+ *   10 at K = 64) are spread over the four waves and formed by v_mfma_f64_16x16x4_f64 with the accumulators in
+ *   registers.  want_gram = 0 skips the Gram work and returns the same d, s and obj bits.  No floating-point atomics:
+ *   every workgroup writes its partial s, G, obj to the context scratch and a second launch adds them in ascending
+ *   workgroup order, so the results are the same bits on every run.  max_workgroups caps the grid (0: as many as are
+ *   resident at once, three per CU, fewer when the LDS slab leaves room for fewer; the same with and without G).
+ * msm_mbar_plan: read-only; what msm_mbar_pass would launch for (K, N, dtype, max_workgroups) on this context:
+ *   out[0] = frames per workgroup trip, out[1] = grid size, out[2] = LDS bytes, out[3] = Gram tiles.
+ * msm_mbar_state_means: d_mean[k] = mean of u[k, n] over n in [h_offsets[k], h_offsets[k+1]), state k's own frames
+ *   (frames are grouped by the state that drew them), one workgroup per state, fixed order: the solver's initial
+ *   guess is f_k = mean_k - mean_0.  h_offsets int64 [K + 1] on the host, ascending, inside [0, N].
+ * msm_mbar_newton_system: with N_k = d_Nk f64 [K], the reduced Newton system of the convex objective
+ *   Phi(f) = obj - sum_k N_k f_k under the gauge f_0 = 0:  d_H f64 [K-1, K-1], H_ij = delta_ij N_i s_i -
+ *   N_i N_j G_ij and d_g f64 [K-1], g_i = N_i (s_i - 1), i, j = 1 .. K-1.  msm_solve_f64 then solves H x = g in place.
+ * msm_mbar_weights: unsampled target states, rows of d_ut [T, ld] f32 / f64, from the stored d_n:
+ *   c_n = -u_tn - d_n,  f_t = -logsumexp_n c_n,  w_tn = exp(c_n - logsumexp_n c_n)  (sum_n w_tn = 1),
+ *   ESS_t = 1 / sum_n w_tn^2 (Kish).  d_ft f64 [T], d_w f64 [T, N], d_ess f64 [T]; d_status as above
+ *   (BAD_INPUT: NaN or -inf in u_t; BAD_FRAME: a target no frame reaches, f_t = +inf).  Fixed-order reductions.
+ * msm_mbar_reduced_potentials: the replica-ladder case, d_u f64 [K, ld], u[k, n] = d_beta[k] * (d_energy[n] +
+ *   d_bias[k, n]) (d_bias f64 [K, ldb], NULL: no bias). */
+#define MSM_MBAR_MAX_K 64
+#define MSM_MBAR_THREADS 256
+#define MSM_MBAR_BAD_INPUT 1
+#define MSM_MBAR_BAD_FRAME 2
+msm_status msm_mbar_plan(msm_ctx* ctx, int K, int64_t N, msm_dtype dtype, int max_workgroups, int64_t out[4]);
+msm_status msm_mbar_pass(msm_ctx* ctx, const void* d_u, msm_dtype dtype, int K, int64_t N, int64_t ld,
+                         const double* d_f, const double* d_lnN, int want_gram, int max_workgroups, double* d_logden,
+                         double* d_s, double* d_G, double* d_obj, int32_t* d_status);
+msm_status msm_mbar_state_means(msm_ctx* ctx, const void* d_u, msm_dtype dtype, int K, int64_t N, int64_t ld,
+                                const int64_t* h_offsets, double* d_mean);
+msm_status msm_mbar_newton_system(msm_ctx* ctx, int K, const double* d_s, const double* d_G, const double* d_Nk,
+                                  double* d_H, double* d_g);
+msm_status msm_mbar_weights(msm_ctx* ctx, const void* d_ut, msm_dtype dtype, int T, int64_t N, int64_t ld,
+                            const double* d_logden, double* d_ft, double* d_w, double* d_ess, int32_t* d_status);
+msm_status msm_mbar_reduced_potentials(msm_ctx* ctx, const double* d_energy, const double* d_bias, int64_t ldb,
+                                       const double* d_beta, int K, int64_t N, int64_t ld, double* d_u);
+
 /* ------------------------------------------------------------------ */
 /* exchange steps of the sharded path (RCCL over xGMI)                  */
 /* ------------------------------------------------------------------ */

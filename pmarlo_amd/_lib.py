@@ -49,6 +49,9 @@ VAMP2_STATS = 16 + 4 * MLP_MAX_OUT
 # msm_mlp_launch_plan: the kernel codes (MSM_MLP_KERNEL_*) and the slots per partial sum (MSM_MLP_CHUNK)
 MLP_KERNELS = {"forward": 0, "vjp": 1, "train_forward": 2, "train_backward": 3}
 MLP_CHUNK = 256
+# MBAR (MSM_MBAR_* in include/msmhip.h): most sampled states, frames of a workgroup trip, the status bits
+MBAR_MAX_K, MBAR_THREADS = 64, 256
+MBAR_BAD_INPUT, MBAR_BAD_FRAME = 1, 2
 
 
 class MsmError(RuntimeError):
@@ -241,6 +244,12 @@ _PROTOTYPES: dict[str, tuple] = {
     "msm_state_centroids": (_i32, [_vp, _vp, _i64, _i32, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
     "msm_state_scores": (_i32, [_vp, _vp, _i64, _i32, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp]),
     "msm_state_select": (_i32, [_vp, _vp, _i64, _i32, _i64, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _vp]),
+    "msm_mbar_plan": (_i32, [_vp, _i32, _i64, _i32, _i32, _vp]),
+    "msm_mbar_pass": (_i32, [_vp, _vp, _i32, _i32, _i64, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "msm_mbar_state_means": (_i32, [_vp, _vp, _i32, _i32, _i64, _i64, _vp, _vp]),
+    "msm_mbar_newton_system": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "msm_mbar_weights": (_i32, [_vp, _vp, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "msm_mbar_reduced_potentials": (_i32, [_vp, _vp, _vp, _i64, _vp, _i32, _i64, _i64, _vp]),
 }
 
 DECLARED_SYMBOLS = tuple(_PROTOTYPES)

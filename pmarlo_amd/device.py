@@ -882,6 +882,100 @@ class Engine:
         self.last_effective_launches = int(launches.value)
         return ceff, si, counts, trunc
 
+    # -- MBAR (csrc/mbar.hip) -------------------------------------------------------------------
+    @staticmethod
+    def _mbar_matrix(u: DeviceArray, n: int | None, what: str) -> tuple[int, int, int]:
+        if len(u.shape) != 2:
+            raise ValueError(f"{what} must be a [states, ld] matrix, got shape {u.shape}")
+        rows, ld = u.shape
+        n = ld if n is None else int(n)
+        if not 1 <= n <= ld:
+            raise ValueError(f"{what}: need 1 <= n <= ld (n={n}, ld={ld})")
+        return rows, n, ld
+
+    @staticmethod
+    def _mbar_raise(status: int, what: str) -> None:
+        if status & _lib.MBAR_BAD_INPUT:
+            raise ValueError(f"{what}: the reduced potentials hold NaN or -inf")
+        if status & _lib.MBAR_BAD_FRAME:
+            raise ValueError(f"{what}: a frame is forbidden (+inf) in every state, its mixture denominator is zero")
+
+    def mbar_plan(self, K: int, N: int, dtype=np.float64, max_workgroups: int = 0) -> dict:
+        """What mbar_pass would launch (msm_mbar_plan, include/msmhip.h).  Launches nothing."""
+        out = (C.c_int64 * 4)()
+        check(lib.msm_mbar_plan(self.handle, int(K), int(N), _dtype_code(dtype), int(max_workgroups), out), self.handle)
+        return {"frames_per_trip": int(out[0]), "grid": int(out[1]), "lds_bytes": int(out[2]), "gram_tiles": int(out[3])}
+
+    def mbar_pass(self, u: DeviceArray, f: DeviceArray, lnN: DeviceArray, *, n: int | None = None,
+                  want_gram: bool = True, want_logden: bool = True, max_workgroups: int = 0, check_status: bool = True) -> dict:
+        """One MBAR pass at free energies f over u [K, ld] f32 / f64 (msm_mbar_pass, include/msmhip.h); the first `n`
+        columns of every row are frames (default: all ld).  Returns {"s": f64 [K], "obj": f64 [1], "G": f64 [K, K] or
+        None, "logden": f64 [n] or None, "status": int}, device arrays.  NaN / -inf in u and a frame forbidden in
+        every state raise ValueError (check_status=False: only reported in "status")."""
+        K, n, ld = self._mbar_matrix(u, n, "u")
+        if f.dtype != np.float64 or lnN.dtype != np.float64 or f.size != K or lnN.size != K:
+            raise ValueError(f"f and lnN must be float64 of {K} entries")
+        s, obj = self.empty((K,), np.float64), self.empty((1,), np.float64)
+        G = self.empty((K, K), np.float64) if want_gram and K <= _lib.MBAR_MAX_K else None
+        logden = self.empty((n,), np.float64) if want_logden else None
+        status = self.zeros((1,), np.int32)
+        check(lib.msm_mbar_pass(self.handle, u.ptr, _dtype_code(u.dtype), K, n, ld, f.ptr, lnN.ptr, int(bool(want_gram)),
+                                int(max_workgroups), logden.ptr if logden is not None else None, s.ptr,
+                                G.ptr if G is not None else None, obj.ptr, status.ptr), self.handle)
+        st = int(status.to_host()[0])
+        if check_status:
+            self._mbar_raise(st, "mbar_pass")
+        return {"s": s, "obj": obj, "G": G, "logden": logden, "status": st}
+
+    def mbar_state_means(self, u: DeviceArray, offsets, *, n: int | None = None) -> DeviceArray:
+        """Mean of row k of u over its own frames [offsets[k], offsets[k+1]) (msm_mbar_state_means) -> f64 [K]."""
+        K, n, ld = self._mbar_matrix(u, n, "u")
+        off = np.ascontiguousarray(offsets, np.int64)
+        if off.shape != (K + 1,):
+            raise ValueError(f"offsets must have {K + 1} entries")
+        mean = self.empty((K,), np.float64)
+        check(lib.msm_mbar_state_means(self.handle, u.ptr, _dtype_code(u.dtype), K, n, ld, off.ctypes.data, mean.ptr),
+              self.handle)
+        return mean
+
+    def mbar_newton_step(self, s: DeviceArray, G: DeviceArray, Nk: DeviceArray) -> np.ndarray:
+        """Solves the reduced Newton system H x = g of the MBAR objective on the device (msm_mbar_newton_system, then
+        msm_solve_f64) -> x, host f64 [K - 1].  Raises RuntimeError when H is singular."""
+        K = s.size
+        H, g = self.empty((K - 1, K - 1), np.float64), self.empty((K - 1,), np.float64)
+        check(lib.msm_mbar_newton_system(self.handle, K, s.ptr, G.ptr, Nk.ptr, H.ptr, g.ptr), self.handle)
+        info = self.solve(H, g)
+        if info:
+            raise _lib.MsmError(f"mbar: the Newton system is singular at column {info - 1}")
+        return g.to_host()
+
+    def mbar_weights(self, ut: DeviceArray, logden: DeviceArray, *, check_status: bool = True):
+        """Target-state free energies, normalised weights and Kish sample sizes from the stored log denominators
+        (msm_mbar_weights, include/msmhip.h): ut [T, ld] f32 / f64, logden f64 [N], N <= ld ->
+        (f_t f64 [T], w f64 [T, N], ess f64 [T]), device arrays."""
+        if logden.dtype != np.float64:
+            raise TypeError("logden must be float64")
+        T, n, ld = self._mbar_matrix(ut, logden.size, "ut")
+        ft, w, ess = self.empty((T,), np.float64), self.empty((T, n), np.float64), self.empty((T,), np.float64)
+        status = self.zeros((1,), np.int32)
+        check(lib.msm_mbar_weights(self.handle, ut.ptr, _dtype_code(ut.dtype), T, n, ld, logden.ptr, ft.ptr, w.ptr,
+                                   ess.ptr, status.ptr), self.handle)
+        if check_status:
+            self._mbar_raise(int(status.to_host()[0]), "mbar_weights")
+        return ft, w, ess
+
+    def mbar_reduced_potentials(self, energy: DeviceArray, beta, bias: DeviceArray | None = None) -> DeviceArray:
+        """u[k, n] = beta[k] * (energy[n] + bias[k, n]) -> f64 [K, N] (msm_mbar_reduced_potentials)."""
+        beta = np.ascontiguousarray(beta, np.float64).reshape(-1)
+        K, n = beta.size, energy.size
+        if energy.dtype != np.float64 or (bias is not None and (bias.dtype != np.float64 or bias.shape != (K, n))):
+            raise ValueError(f"energy must be float64 [N] and bias float64 [{K}, N]")
+        u = self.empty((K, n), np.float64)
+        check(lib.msm_mbar_reduced_potentials(self.handle, energy.ptr, bias.ptr if bias is not None else None, n,
+                                              self.to_device(beta).ptr, K, n, n, u.ptr), self.handle)
+        self.sync()  # beta's device copy is freed on return
+        return u
+
     def state_counts(self, labels: DeviceArray, k: int, out: DeviceArray | None = None) -> DeviceArray:
         out = out if out is not None else self.empty((k,), np.int64)
         check(lib.msm_state_counts(self.handle, labels.ptr, labels.size, int(k), out.ptr), self.handle)
