@@ -1480,6 +1480,73 @@ msm_status msm_mbar_weights(msm_ctx* ctx, const void* d_ut, msm_dtype dtype, int
 msm_status msm_mbar_reduced_potentials(msm_ctx* ctx, const double* d_energy, const double* d_bias, int64_t ldb,
                                        const double* d_beta, int K, int64_t N, int64_t ld, double* d_u);
 
+/* ---- TRAM: multi-ensemble Markov models and frame weights (csrc/tram.hip) ----------------------------
+ * The transition-based reweighting analysis method, written from Wu, Paul, Wehmeyer, Noe, PNAS 113, E3221 (2016);
+ * the reference snapshot holds no reweighter, so nothing is ported.  The tests hold the kernels to a numpy
+ * restatement of the rule below (tests/_tram_ref.py), run in 80-bit floats.
+ *
+ * K thermodynamic states (1 <= K <= MSM_MBAR_MAX_K), m Markov states (1 <= m <= MSM_TRAM_MAX_STATES), N frames;
+ * MSM_ERR_UNSUPPORTED above either limit.  d_u [K, ld] f32 / f64 as in MBAR (+inf allowed, NaN and -inf invalid),
+ * with the frames GROUPED BY MARKOV STATE: state i owns the frames [offsets[i], offsets[i+1]), every state has one.
+ * d_S f64 [K, m, m], S^k = C^k + C^k' of the lag-tau counts; d_N f64 [K, m], N_i^k = frames of state i drawn in
+ * ensemble k; d_col f64 [K, m], col_i^k = sum_j C^k_ji.  The pair (k, i) is active iff N_i^k > 0; S is zero in the
+ * rows and columns of inactive pairs.  The unknowns: d_f f64 [K, m], the local free energies, and d_v f64 [K, m],
+ * the Lagrange multipliers; g_i^k = ln v_i^k + f_i^k (-inf where v = 0).  One iteration:
+ *   1. v_i^k   = sum_j S_ij / (1 + exp(g_j - g_i))                      (old f, old v)
+ *   2. R_i^k   = sum_j S_ij / (1 + exp(g_i - g_j)) + (N_i^k - col_i^k)  (old f, new v),   tab_i^k = ln R_i^k + f_i^k
+ *   3. per frame n of state i:  m_n = min_l u_ln,  a_l = tab_i^l - (u_ln - m_n),  M = max_l a_l,
+ *      e_l = exp(a_l - M),  S = sum_l e_l (ascending l),  d_n = (M + log S) - m_n,  r_l = e_l * (1 / S);
+ *      s_i^k = sum of r_k over the frames of state i
+ *   4. f_i^k   = tab_i^k - ln s_i^k  on the active pairs
+ *   5. f      -= its minimum over the active pairs;  err = max |f_new - f_old| over them;  g = ln v + f_new.
+ *   Inactive pairs: v = R = 0, tab = g = -inf, f untouched; they add nothing to a frame's sum.
+ * msm_tram_rows: steps 1 and 2 are one kernel.  mode MSM_TRAM_ROWS_MULTIPLIERS: d_out = v, d_lnout = ln v + f;
+ *   mode MSM_TRAM_ROWS_COUNTS: d_out = R, d_lnout = tab.  d_g f64 [K, m] is read (never an output of the same call).
+ *   One wave per row (k, i): lane l adds the columns l, l + 64, .. in ascending order, then a fixed shuffle tree;
+ *   the S row is read coalesced; where S_ij = 0 there is no exp and no division.
+ * msm_tram_pass: step 3.  The work unit is (state, segment of MSM_TRAM_SEGMENT frames of its range), one lane per
+ *   frame, fp64 throughout; the tables that name the units are on the device and built once per problem:
+ *   d_offsets int64 [m + 1]; d_unit_ptr int64 [m + 1], state i owns the units [unit_ptr[i], unit_ptr[i+1]), one per
+ *   started segment; d_unit_state int32 [units].  A unit's K sums go to the context scratch, a second launch adds a
+ *   state's units in ascending order into d_s f64 [K, m]: no floating-point atomics, and the same bits on every run
+ *   and for every max_workgroups (0: as many workgroups as are resident at once).  d_logden f64 [N] (may be NULL)
+ *   receives d_n.  d_status int32 [1] is OR-ed into as in MBAR: MSM_MBAR_BAD_INPUT for a NaN or -inf in u,
+ *   MSM_MBAR_BAD_FRAME for a frame without a finite a_l (it adds nothing to s).  A unit whose table entries do not
+ *   describe frames of [0, N) is empty.
+ * msm_tram_update: steps 4 and 5 by one workgroup; d_f is updated in place, d_g and d_err f64 [1] are written.
+ * msm_tram_iterations: n_iterations iterations enqueued back to back, nothing read back in between; every launch is
+ *   bounded.  d_work f64 [5 K m] holds g, the g of step 2, R, tab and s (in that order) and is scratch otherwise;
+ *   g is rebuilt from (f, v) at the start, with the bits step 5 leaves.  d_logden (may be NULL) receives the d_n of
+ *   the last iteration's pass, d_err the err of the last iteration.
+ * msm_tram_transition_matrices: for ensemble k (k = -1: all K, d_P f64 [K, m, m]; else d_P f64 [m, m]):
+ *   p_ij = S_ij / (v_i + v_j exp(f_j - f_i)) for i != j among the active states; when the largest off-diagonal row
+ *   sum exceeds 1 (short of convergence only) every off-diagonal entry is divided by it, which keeps detailed
+ *   balance; p_ii = 1 - sum_{j != i} p_ij.  Rows and columns of inactive states are zero.  d_rowsum f64 [K, m] is
+ *   scratch.  One workgroup per ensemble, one wave per row, sums in a fixed order.
+ * msm_tram_plan: read-only; what msm_tram_pass would launch for state ranges h_offsets int64 [m + 1] (host):
+ *   out[0] = segment length, out[1] = units, out[2] = grid size, out[3] = LDS bytes, out[4] = workgroups of a
+ *   msm_tram_rows launch. */
+#define MSM_TRAM_MAX_STATES 2048
+#define MSM_TRAM_SEGMENT 256
+#define MSM_TRAM_ROWS_MULTIPLIERS 0
+#define MSM_TRAM_ROWS_COUNTS 1
+msm_status msm_tram_plan(msm_ctx* ctx, int K, int m, const int64_t* h_offsets, int max_workgroups, int64_t out[5]);
+msm_status msm_tram_rows(msm_ctx* ctx, int K, int m, const double* d_S, const double* d_g, const double* d_f,
+                         const double* d_N, const double* d_col, int mode, double* d_out, double* d_lnout);
+msm_status msm_tram_pass(msm_ctx* ctx, const void* d_u, msm_dtype dtype, int K, int m, int64_t N, int64_t ld,
+                         const int64_t* d_offsets, const int64_t* d_unit_ptr, const int32_t* d_unit_state,
+                         int64_t units, const double* d_tab, int max_workgroups, double* d_logden, double* d_s,
+                         int32_t* d_status);
+msm_status msm_tram_update(msm_ctx* ctx, int K, int m, const double* d_N, const double* d_tab, const double* d_s,
+                           const double* d_v, double* d_f, double* d_g, double* d_err);
+msm_status msm_tram_iterations(msm_ctx* ctx, const void* d_u, msm_dtype dtype, int K, int m, int64_t N, int64_t ld,
+                               const int64_t* d_offsets, const int64_t* d_unit_ptr, const int32_t* d_unit_state,
+                               int64_t units, const double* d_S, const double* d_N, const double* d_col, double* d_f,
+                               double* d_v, double* d_work, int n_iterations, int max_workgroups, double* d_logden,
+                               double* d_err, int32_t* d_status);
+msm_status msm_tram_transition_matrices(msm_ctx* ctx, int K, int m, const double* d_S, const double* d_N,
+                                        const double* d_f, const double* d_v, int k, double* d_rowsum, double* d_P);
+
 /* ------------------------------------------------------------------ */
 /* exchange steps of the sharded path (RCCL over xGMI)                  */
 /* ------------------------------------------------------------------ */

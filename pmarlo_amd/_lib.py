@@ -52,6 +52,9 @@ MLP_CHUNK = 256
 # MBAR (MSM_MBAR_* in include/msmhip.h): most sampled states, frames of a workgroup trip, the status bits
 MBAR_MAX_K, MBAR_THREADS = 64, 256
 MBAR_BAD_INPUT, MBAR_BAD_FRAME = 1, 2
+# TRAM (MSM_TRAM_* in include/msmhip.h): most Markov states, frames of a pass segment, the modes of msm_tram_rows
+TRAM_MAX_STATES, TRAM_SEGMENT = 2048, 256
+TRAM_ROWS_MULTIPLIERS, TRAM_ROWS_COUNTS = 0, 1
 
 
 class MsmError(RuntimeError):
@@ -250,6 +253,13 @@ _PROTOTYPES: dict[str, tuple] = {
     "msm_mbar_newton_system": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "msm_mbar_weights": (_i32, [_vp, _vp, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "msm_mbar_reduced_potentials": (_i32, [_vp, _vp, _vp, _i64, _vp, _i32, _i64, _i64, _vp]),
+    "msm_tram_plan": (_i32, [_vp, _i32, _i32, _vp, _i32, _vp]),
+    "msm_tram_rows": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "msm_tram_pass": (_i32, [_vp, _vp, _i32, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp]),
+    "msm_tram_update": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "msm_tram_iterations": (_i32, [_vp, _vp, _i32, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp,
+                                   _vp, _i32, _i32, _vp, _vp, _vp]),
+    "msm_tram_transition_matrices": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
 }
 
 DECLARED_SYMBOLS = tuple(_PROTOTYPES)

@@ -976,6 +976,132 @@ class Engine:
         self.sync()  # beta's device copy is freed on return
         return u
 
+    # -- TRAM (csrc/tram.hip) -------------------------------------------------------------------
+    @staticmethod
+    def _tram_units(offsets) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        off = np.ascontiguousarray(offsets, np.int64).reshape(-1)
+        if off.size < 2 or off[0] != 0 or (np.diff(off) <= 0).any():
+            raise ValueError("offsets must start at 0 and give every Markov state at least one frame")
+        per_state = -(-np.diff(off) // _lib.TRAM_SEGMENT)
+        unit_ptr = np.concatenate([[0], np.cumsum(per_state)]).astype(np.int64)
+        return off, unit_ptr, np.repeat(np.arange(off.size - 1, dtype=np.int32), per_state)
+
+    def tram_tables(self, offsets) -> dict:
+        """The device tables that name the work units of tram_pass for frames grouped by Markov state, state i
+        owning [offsets[i], offsets[i+1]): built once per problem (msm_tram_pass, include/msmhip.h)."""
+        off, unit_ptr, unit_state = self._tram_units(offsets)
+        return {"m": off.size - 1, "n": int(off[-1]), "units": int(unit_ptr[-1]), "host_offsets": off,
+                "offsets": self.to_device(off), "unit_ptr": self.to_device(unit_ptr),
+                "unit_state": self.to_device(unit_state)}
+
+    def tram_plan(self, K: int, offsets, max_workgroups: int = 0) -> dict:
+        """What tram_pass would launch (msm_tram_plan, include/msmhip.h).  Launches nothing."""
+        off = np.ascontiguousarray(offsets, np.int64).reshape(-1)
+        out = (C.c_int64 * 5)()
+        check(lib.msm_tram_plan(self.handle, int(K), off.size - 1, off.ctypes.data, int(max_workgroups), out), self.handle)
+        return {"segment": int(out[0]), "units": int(out[1]), "grid": int(out[2]), "lds_bytes": int(out[3]),
+                "rows_grid": int(out[4])}
+
+    @staticmethod
+    def _tram_km(S: DeviceArray, *tables: DeviceArray) -> tuple[int, int]:
+        if S.dtype != np.float64 or len(S.shape) != 3 or S.shape[1] != S.shape[2]:
+            raise ValueError(f"S must be float64 [K, m, m], got {S.dtype} {S.shape}")
+        K, m = S.shape[0], S.shape[1]
+        for t in tables:
+            if t.dtype != np.float64 or t.shape != (K, m):
+                raise ValueError(f"the per-pair tables must be float64 [{K}, {m}], got {t.dtype} {t.shape}")
+        return K, m
+
+    def tram_rows(self, S: DeviceArray, g: DeviceArray, f: DeviceArray, N: DeviceArray, col: DeviceArray,
+                  mode: str) -> tuple[DeviceArray, DeviceArray]:
+        """Step 1 (mode "multipliers" -> v, ln v + f) or step 2 (mode "counts" -> R, ln R + f) of a TRAM iteration
+        (msm_tram_rows, include/msmhip.h), f64 [K, m] device arrays."""
+        modes = {"multipliers": _lib.TRAM_ROWS_MULTIPLIERS, "counts": _lib.TRAM_ROWS_COUNTS}
+        if mode not in modes:
+            raise ValueError(f"mode must be one of {sorted(modes)}, got {mode!r}")
+        K, m = self._tram_km(S, g, f, N, col)
+        out, lnout = self.empty((K, m), np.float64), self.empty((K, m), np.float64)
+        check(lib.msm_tram_rows(self.handle, K, m, S.ptr, g.ptr, f.ptr, N.ptr, col.ptr, modes[mode], out.ptr, lnout.ptr),
+              self.handle)
+        return out, lnout
+
+    def tram_pass(self, u: DeviceArray, tables: dict, tab: DeviceArray, *, want_logden: bool = True,
+                  max_workgroups: int = 0, check_status: bool = True) -> dict:
+        """Step 3 over u [K, ld] f32 / f64, frames grouped by Markov state as `tables` (tram_tables) says, at the
+        table tab = ln R + f, f64 [K, m] (msm_tram_pass, include/msmhip.h).  Returns {"s": f64 [K, m], "logden": f64
+        [N] or None, "status": int}.  NaN / -inf in u and a frame without a finite term raise ValueError
+        (check_status=False: only reported in "status")."""
+        K, n, ld = self._mbar_matrix(u, tables["n"], "u")
+        m = tables["m"]
+        if tab.dtype != np.float64 or tab.shape != (K, m):
+            raise ValueError(f"tab must be float64 [{K}, {m}]")
+        s = self.empty((K, m), np.float64)
+        logden = self.empty((n,), np.float64) if want_logden else None
+        status = self.zeros((1,), np.int32)
+        check(lib.msm_tram_pass(self.handle, u.ptr, _dtype_code(u.dtype), K, m, n, ld, tables["offsets"].ptr,
+                                tables["unit_ptr"].ptr, tables["unit_state"].ptr, tables["units"], tab.ptr,
+                                int(max_workgroups), logden.ptr if logden is not None else None, s.ptr, status.ptr),
+              self.handle)
+        st = int(status.to_host()[0])
+        if check_status:
+            self._mbar_raise(st, "tram_pass")
+        return {"s": s, "logden": logden, "status": st}
+
+    def tram_update(self, N: DeviceArray, tab: DeviceArray, s: DeviceArray, v: DeviceArray,
+                    f: DeviceArray) -> tuple[DeviceArray, DeviceArray]:
+        """Steps 4 and 5: f is updated in place -> (g = ln v + f f64 [K, m], err f64 [1]) (msm_tram_update)."""
+        K, m = f.shape
+        g, err = self.empty((K, m), np.float64), self.empty((1,), np.float64)
+        check(lib.msm_tram_update(self.handle, K, m, N.ptr, tab.ptr, s.ptr, v.ptr, f.ptr, g.ptr, err.ptr), self.handle)
+        return g, err
+
+    def tram_solve(self, u: DeviceArray, tables: dict, S: DeviceArray, N: DeviceArray, col: DeviceArray,
+                   f: DeviceArray, v: DeviceArray, *, tol: float = 1e-10, maxiter: int = 100_000,
+                   check_every: int = 16, max_workgroups: int = 0) -> dict:
+        """Iterates the TRAM equations from (f, v), updated in place, until err <= tol (msm_tram_iterations,
+        include/msmhip.h).  `check_every` iterations are enqueued back to back with no host synchronisation; then
+        the one err word and the status word are read.  Stops at the first checked iteration with err <= tol;
+        MsmError (NOCONV) at `maxiter`.  Returns {"n_iterations", "err", "logden": d_n of the last pass, f64 [N]}."""
+        K, m = self._tram_km(S, N, col, f, v)
+        Ku, n, ld = self._mbar_matrix(u, tables["n"], "u")
+        if Ku != K or tables["m"] != m:
+            raise ValueError(f"u has {Ku} rows and the tables {tables['m']} Markov states; S is [{K}, {m}, {m}]")
+        check_every, maxiter = int(check_every), int(maxiter)
+        if check_every < 1 or maxiter < 1:
+            raise ValueError("check_every and maxiter must be >= 1")
+        work = self.empty((5, K, m), np.float64)
+        logden, err_d = self.empty((n,), np.float64), self.empty((1,), np.float64)
+        status = self.zeros((1,), np.int32)
+        it, err = 0, float("inf")
+        while it < maxiter:
+            block = min(check_every, maxiter - it)
+            check(lib.msm_tram_iterations(self.handle, u.ptr, _dtype_code(u.dtype), K, m, n, ld, tables["offsets"].ptr,
+                                          tables["unit_ptr"].ptr, tables["unit_state"].ptr, tables["units"], S.ptr,
+                                          N.ptr, col.ptr, f.ptr, v.ptr, work.ptr, block, int(max_workgroups),
+                                          logden.ptr, err_d.ptr, status.ptr), self.handle)
+            it += block
+            err = float(err_d.to_host()[0])
+            self._mbar_raise(int(status.to_host()[0]), "tram_solve")
+            if err <= tol:
+                return {"n_iterations": it, "err": err, "logden": logden}
+            if not np.isfinite(err):
+                raise _lib.MsmError(f"tram: the iteration left the finite numbers after {it} iterations (err = {err})")
+        raise _lib.MsmError(f"tram: err {err:.3e} > tol {tol:.1e} after {it} iterations (MSM_ERR_NOCONV)")
+
+    def tram_transition_matrices(self, S: DeviceArray, N: DeviceArray, f: DeviceArray, v: DeviceArray,
+                                 k: int | None = None) -> DeviceArray:
+        """The reversible transition matrix of ensemble k, f64 [m, m], or of all of them, f64 [K, m, m], at (f, v)
+        (msm_tram_transition_matrices, include/msmhip.h); rows and columns of inactive states are zero."""
+        K, m = self._tram_km(S, N, f, v)
+        if k is not None and not 0 <= int(k) < K:
+            raise ValueError(f"k must be in [0, {K})")
+        P = self.empty((K, m, m) if k is None else (m, m), np.float64)
+        rowsum = self.empty((K, m), np.float64)
+        check(lib.msm_tram_transition_matrices(self.handle, K, m, S.ptr, N.ptr, f.ptr, v.ptr, -1 if k is None else int(k),
+                                               rowsum.ptr, P.ptr), self.handle)
+        self.sync()  # the row sums are freed on return
+        return P
+
     def state_counts(self, labels: DeviceArray, k: int, out: DeviceArray | None = None) -> DeviceArray:
         out = out if out is not None else self.empty((k,), np.int64)
         check(lib.msm_state_counts(self.handle, labels.ptr, labels.size, int(k), out.ptr), self.handle)

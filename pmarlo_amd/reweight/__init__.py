@@ -1,12 +1,14 @@
-"""Frame weights for multi-ensemble runs: MBAR on the device (csrc/mbar.hip).
+"""Frame weights for multi-ensemble runs: MBAR (csrc/mbar.hip) and TRAM (csrc/tram.hip) on the device.
 
 ``mbar`` solves the MBAR equations for K sampled states and evaluates unsampled target states,
-``temperature_weights`` is the replica-ladder case built from one energy per frame, and ``Reweighter`` writes
-``dataset["frame_weights"]``, where discretize_dataset, prepare_msm_discretization and the free-energy entry points
-pick them up.
+``temperature_weights`` is the replica-ladder case built from one energy per frame, ``tram`` and ``tram_from_counts``
+couple the ensembles through one reversible Markov model each and return that model beside the weights, and
+``Reweighter`` writes ``dataset["frame_weights"]``, where discretize_dataset, prepare_msm_discretization and the
+free-energy entry points pick them up.
 """
 
 from .mbar import MBARResult, mbar, temperature_weights
 from .reweighter import Reweighter
+from .tram import TRAMResult, tram, tram_from_counts
 
-__all__ = ["MBARResult", "Reweighter", "mbar", "temperature_weights"]
+__all__ = ["MBARResult", "Reweighter", "TRAMResult", "mbar", "temperature_weights", "tram", "tram_from_counts"]
