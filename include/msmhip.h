@@ -1547,6 +1547,91 @@ msm_status msm_tram_iterations(msm_ctx* ctx, const void* d_u, msm_dtype dtype, i
 msm_status msm_tram_transition_matrices(msm_ctx* ctx, int K, int m, const double* d_S, const double* d_N,
                                         const double* d_f, const double* d_v, int k, double* d_rowsum, double* d_P);
 
+/* ---- HMM: discrete-output hidden Markov models, Baum-Welch on the device (csrc/hmm.hip) ---------------
+ * Written from the published method (Rabiner 1989; the lagged sequences of deeptime's lag_observations).  Parity
+ * with deeptime or PyEMMA is NOT pinned; the tests hold the kernels to tests/_hmm_ref.py run in 80-bit floats.
+ *
+ * n hidden states (1 <= n <= MSM_HMM_MAX_HIDDEN, MSM_ERR_UNSUPPORTED above), k >= 1 symbols, d_A f64 [n, n],
+ * d_B f64 [n, k], d_p0 f64 [n].  d_labels int32 [N].  d_seq int64 [Q, 3] holds (start, stride, length): observation
+ * t of sequence q is labels[start_q + t stride_q].  Chunk c of a sequence of length T covers the steps
+ * t = 1 + cL .. min((c+1)L, T-1), L = MSM_HMM_CHUNK; a sequence of length 1 has none.  d_chunk_ptr int64 [Q + 1] is
+ * the prefix sum of the chunk counts and d_chunk_seq int32 [n_chunks] names every chunk's sequence.  A triple or a
+ * chunk range that does not describe frames of [0, N) sets MSM_HMM_BAD_TABLE and is not walked.
+ *
+ * msm_hmm_estep: scaled forward-backward,
+ *   alpha^_0 = p0 o b_0 / c_0, alpha^_t = (alpha^_{t-1} A) o b_t / c_t, beta^_{T-1} = 1,
+ *   beta^_t = A (b_{t+1} o beta^_{t+1}) / c_{t+1}, gamma_t = alpha^_t o beta^_t.
+ *   d_gamma  f64 [N, n] in frame order; only rows of frames in a sequence are written (the caller zeroes it once)
+ *   d_C      f64 [n, n] = sum_q sum_t alpha^_t(i) A_ij b_{t+1}(j) beta^_{t+1}(j) / c_{t+1}
+ *   d_gamma0 f64 [n] = sum_q gamma_0;  d_logL f64 [Q] = sum_t ln c_t;  d_total f64 [1] = sum_q logL (may be NULL)
+ * in three phases: every chunk's product P_c = prod_t A diag(b_t), rescaled by exact powers of two; per sequence
+ * the entry vectors a_{c+1} = a_c P_c / sum and exit vectors w_c = P_c w_{c+1} / sum of its chunks; every chunk's
+ * replay of alpha^ from a_c (kept in LDS) and walk of beta^ back from w_{c+1}, scaled so that alpha^ . beta^ = 1.
+ * The partial C and sum of ln c_t of a sequence's chunks, then the sequences, are added in ascending order: every
+ * output has the same bits on every run and for every max_workgroups (0: the default grid).  No fp atomics.
+ * A symbol outside [0, k) sets MSM_HMM_BAD_SYMBOL, a sequence of probability 0 sets MSM_HMM_ZERO_PROB; either
+ * sequence reports logL = -inf, has zero rows in d_gamma and adds nothing to d_C and d_gamma0.
+ * d_work: msm_hmm_workspace_bytes(n, n_chunks, Q, units) bytes (units = 0 where no emission sums are taken).
+ *
+ * msm_hmm_emissions: E[i, y] = sum of gamma_t(i) over the frames with label y, from msm_group_by_label's
+ * d_offsets / d_members.  Unit tables as msm_tram_pass takes them (symbol, segment of 256 member frames):
+ * d_unit_ptr int64 [k + 1], d_unit_state int32 [units]; d_part f64 [units, n]; a fold adds the units of a symbol in
+ * ascending order.
+ *
+ * msm_hmm_mstep, one workgroup: B_iy = E_iy / sum_y E_iy; A = the rows of C over their sums, or (reversible) the
+ * fixed point msm_reversible_mle documents run on C, checked every iteration, until maxerr or maxiter
+ * (<= MSM_HMM_MAX_FIXED_POINT; MSM_HMM_NOT_CONVERGED at maxiter); d_pi f64 [n] = the stationary vector of the new A
+ * (the fixed point's x, or the GTH elimination); p0 = gamma0 / Q, or (stationary) pi.  A hidden state without mass
+ * keeps its row and sets MSM_HMM_EMPTY_STATE.
+ *
+ * msm_hmm_iterations: n_iterations of (estep, emissions, mstep) enqueued back to back, nothing read back in between;
+ * d_history f64 [n_iterations] receives sum_q logL of every iteration (the likelihood of the parameters the
+ * iteration started from).  d_A, d_B, d_p0 are updated in place.
+ *
+ * msm_hmm_viterbi: the most probable hidden path of every sequence, by the same chunking in the (max, +) semiring on
+ * ln A, ln B, ln p0 (taken on the device; ln 0 = -inf).  The chunk products are the kernel of the E-step's products
+ * instantiated for (max, +); per sequence delta at every chunk entry, then the boundary states backwards,
+ * s_c = argmax_i delta_c(i) + P_c(i, s_{c+1}); every chunk replays from its one-hot entry state with back-pointers
+ * in LDS and backtracks from its exit state.  Ties go to the lowest index.  d_path int32 [N] in frame order, -1 for
+ * frames in no sequence and for sequences of probability 0 (MSM_HMM_ZERO_PROB) or with a bad symbol; d_logp f64 [Q]
+ * (may be NULL) = the path's log-probability as the device added it, -inf for such sequences.
+ * d_work: msm_hmm_viterbi_workspace_bytes(n, k, n_chunks, Q) bytes.
+ *
+ * msm_hmm_plan: read-only; out = {MSM_HMM_CHUNK, padded n, n_chunks, grid of the products and the pass, grid of the
+ * boundaries, LDS bytes of the products, of the pass, of an emission unit}. */
+#define MSM_HMM_MAX_HIDDEN 16
+#define MSM_HMM_CHUNK 64
+#define MSM_HMM_MAX_FIXED_POINT 1000000
+#define MSM_HMM_BAD_SYMBOL 1
+#define MSM_HMM_ZERO_PROB 2
+#define MSM_HMM_EMPTY_STATE 4
+#define MSM_HMM_BAD_TABLE 8
+#define MSM_HMM_NOT_CONVERGED 16
+size_t msm_hmm_workspace_bytes(int n, int64_t n_chunks, int Q, int64_t units);
+msm_status msm_hmm_plan(msm_ctx* ctx, int n, int64_t n_chunks, int Q, int max_workgroups, int64_t out[8]);
+msm_status msm_hmm_estep(msm_ctx* ctx, const int32_t* d_labels, int64_t N, int k, int n, const int64_t* d_seq, int Q,
+                         const int64_t* d_chunk_ptr, const int32_t* d_chunk_seq, int64_t n_chunks, const double* d_A,
+                         const double* d_B, const double* d_p0, int max_workgroups, void* d_work, double* d_gamma,
+                         double* d_C, double* d_gamma0, double* d_logL, double* d_total, int32_t* d_status);
+msm_status msm_hmm_emissions(msm_ctx* ctx, const double* d_gamma, int64_t N, int n, int k, const int64_t* d_offsets,
+                             const int32_t* d_members, const int64_t* d_unit_ptr, const int32_t* d_unit_state,
+                             int64_t units, int max_workgroups, double* d_part, double* d_E);
+msm_status msm_hmm_mstep(msm_ctx* ctx, int n, int k, int Q, const double* d_C, const double* d_E,
+                         const double* d_gamma0, int reversible, int stationary, int maxiter, double maxerr,
+                         double* d_A, double* d_B, double* d_p0, double* d_pi, int32_t* d_status);
+size_t msm_hmm_viterbi_workspace_bytes(int n, int k, int64_t n_chunks, int Q);
+msm_status msm_hmm_viterbi(msm_ctx* ctx, const int32_t* d_labels, int64_t N, int k, int n, const int64_t* d_seq, int Q,
+                           const int64_t* d_chunk_ptr, const int32_t* d_chunk_seq, int64_t n_chunks, const double* d_A,
+                           const double* d_B, const double* d_p0, int max_workgroups, void* d_work, int32_t* d_path,
+                           double* d_logp, int32_t* d_status);
+msm_status msm_hmm_iterations(msm_ctx* ctx, const int32_t* d_labels, int64_t N, int k, int n, const int64_t* d_seq,
+                              int Q, const int64_t* d_chunk_ptr, const int32_t* d_chunk_seq, int64_t n_chunks,
+                              const int64_t* d_offsets, const int32_t* d_members, const int64_t* d_unit_ptr,
+                              const int32_t* d_unit_state, int64_t units, int reversible, int stationary, int maxiter,
+                              double maxerr, int n_iterations, int max_workgroups, void* d_work, double* d_A,
+                              double* d_B, double* d_p0, double* d_pi, double* d_gamma, double* d_C, double* d_E,
+                              double* d_gamma0, double* d_logL, double* d_history, int32_t* d_status);
+
 /* ------------------------------------------------------------------ */
 /* exchange steps of the sharded path (RCCL over xGMI)                  */
 /* ------------------------------------------------------------------ */

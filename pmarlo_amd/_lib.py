@@ -55,6 +55,9 @@ MBAR_BAD_INPUT, MBAR_BAD_FRAME = 1, 2
 # TRAM (MSM_TRAM_* in include/msmhip.h): most Markov states, frames of a pass segment, the modes of msm_tram_rows
 TRAM_MAX_STATES, TRAM_SEGMENT = 2048, 256
 TRAM_ROWS_MULTIPLIERS, TRAM_ROWS_COUNTS = 0, 1
+# HMM (MSM_HMM_* in include/msmhip.h): most hidden states, steps of a chunk, the fixed point's iteration cap, status bits
+HMM_MAX_HIDDEN, HMM_CHUNK, HMM_MAX_FIXED_POINT = 16, 64, 1_000_000
+HMM_BAD_SYMBOL, HMM_ZERO_PROB, HMM_EMPTY_STATE, HMM_BAD_TABLE, HMM_NOT_CONVERGED = 1, 2, 4, 8, 16
 
 
 class MsmError(RuntimeError):
@@ -260,6 +263,18 @@ _PROTOTYPES: dict[str, tuple] = {
     "msm_tram_iterations": (_i32, [_vp, _vp, _i32, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp,
                                    _vp, _i32, _i32, _vp, _vp, _vp]),
     "msm_tram_transition_matrices": (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "msm_hmm_workspace_bytes": (_sz, [_i32, _i64, _i32, _i64]),
+    "msm_hmm_plan": (_i32, [_vp, _i32, _i64, _i32, _i32, _vp]),
+    "msm_hmm_estep": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
+                             _vp, _vp, _vp, _vp]),
+    "msm_hmm_emissions": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp]),
+    "msm_hmm_mstep": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _f64, _vp, _vp, _vp, _vp, _vp]),
+    "msm_hmm_viterbi_workspace_bytes": (_sz, [_i32, _i32, _i64, _i32]),
+    "msm_hmm_viterbi": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
+                               _vp]),
+    "msm_hmm_iterations": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32,
+                                  _i32, _i32, _f64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                  _vp]),
 }
 
 DECLARED_SYMBOLS = tuple(_PROTOTYPES)

@@ -1102,6 +1102,173 @@ class Engine:
         self.sync()  # the row sums are freed on return
         return P
 
+    # -- hidden Markov models (csrc/hmm.hip) ------------------------------------------------------
+    def hmm_plan(self, n: int, n_chunks: int, n_sequences: int, max_workgroups: int = 0) -> dict:
+        """What an E-step would launch (msm_hmm_plan, include/msmhip.h).  Launches nothing."""
+        out = (C.c_int64 * 8)()
+        check(lib.msm_hmm_plan(self.handle, int(n), int(n_chunks), int(n_sequences), int(max_workgroups), out),
+              self.handle)
+        return {"chunk": int(out[0]), "padded_n": int(out[1]), "n_chunks": int(out[2]), "grid": int(out[3]),
+                "boundary_grid": int(out[4]), "product_lds_bytes": int(out[5]), "pass_lds_bytes": int(out[6]),
+                "emission_lds_bytes": int(out[7])}
+
+    def hmm_tables(self, labels: DeviceArray, k: int, sequences, *, n: int | None = None) -> dict:
+        """The device tables of an HMM fit over the first `n` entries of labels int32: `sequences` int64 [Q, 3] of
+        (start, stride, length) (hmm.lag_observations builds them), the chunk tables of msm_hmm_estep, and the
+        frames grouped by symbol with the (symbol, 256 member frames) units of msm_hmm_emissions.  Built once per
+        fit; one read-back of the k + 1 group offsets."""
+        if labels.dtype != np.int32:
+            raise TypeError("labels must be int32")
+        N = labels.size if n is None else int(n)
+        if not 1 <= N <= labels.size:
+            raise ValueError(f"n must be in [1, {labels.size}]")
+        seq = np.ascontiguousarray(sequences, np.int64).reshape(-1, 3)
+        if seq.shape[0] < 1 or (seq[:, 2] < 1).any():
+            raise ValueError("need at least one sequence, every one with at least one observation")
+        per_seq = -(-(seq[:, 2] - 1) // _lib.HMM_CHUNK)
+        chunk_ptr = np.concatenate([[0], np.cumsum(per_seq)]).astype(np.int64)
+        chunk_seq = np.repeat(np.arange(seq.shape[0], dtype=np.int32), per_seq)
+        offsets, members = self.empty((int(k) + 1,), np.int64), self.empty((N,), np.int32)
+        check(lib.msm_group_by_label(self.handle, labels.ptr, N, int(k), offsets.ptr, members.ptr), self.handle)
+        per_symbol = -(-np.diff(offsets.to_host()) // 256)
+        unit_ptr = np.concatenate([[0], np.cumsum(per_symbol)]).astype(np.int64)
+        unit_state = np.repeat(np.arange(int(k), dtype=np.int32), per_symbol)
+        return {"labels": labels, "N": N, "k": int(k), "Q": seq.shape[0], "n_chunks": int(chunk_ptr[-1]),
+                "units": int(unit_ptr[-1]), "host_sequences": seq, "sequences": self.to_device(seq),
+                "chunk_ptr": self.to_device(chunk_ptr), "chunk_seq": self.to_device(chunk_seq) if chunk_seq.size else None,
+                "offsets": offsets, "members": members, "unit_ptr": self.to_device(unit_ptr),
+                "unit_state": self.to_device(unit_state) if unit_state.size else None}
+
+    @staticmethod
+    def _hmm_model(t: dict, A: DeviceArray, B: DeviceArray, p0: DeviceArray) -> int:
+        n = A.shape[0]
+        for name, arr, shape in (("A", A, (n, n)), ("B", B, (n, t["k"])), ("p0", p0, (n,))):
+            if arr.dtype != np.float64 or arr.shape != shape:
+                raise ValueError(f"{name} must be float64 {list(shape)}, got {arr.dtype} {arr.shape}")
+        return n
+
+    def _hmm_work(self, t: dict, n: int) -> DeviceArray:
+        nbytes = int(lib.msm_hmm_workspace_bytes(int(n), t["n_chunks"], t["Q"], t["units"]))
+        if nbytes == 0:
+            check(lib.msm_hmm_plan(self.handle, int(n), t["n_chunks"], t["Q"], 0, (C.c_int64 * 8)()), self.handle)
+        return self.empty((nbytes,), np.uint8)
+
+    @staticmethod
+    def _opt(arr: DeviceArray | None):
+        return arr.ptr if arr is not None else None
+
+    def hmm_estep(self, tables: dict, A: DeviceArray, B: DeviceArray, p0: DeviceArray, *, max_workgroups: int = 0,
+                  want_emissions: bool = True) -> dict:
+        """One scaled forward-backward pass over every sequence (msm_hmm_estep, include/msmhip.h) and the emission
+        sums (msm_hmm_emissions).  Returns device arrays "gamma" f64 [N, n], "C" f64 [n, n], "gamma0" f64 [n], "logL"
+        f64 [Q], "E" f64 [n, k] (or None), and the host values "total" = sum of logL and "status" (HMM_* bits)."""
+        t = tables
+        n = self._hmm_model(t, A, B, p0)
+        work = self._hmm_work(t, n)
+        gamma = self.zeros((t["N"], n), np.float64)
+        Cm, g0, logL = self.empty((n, n), np.float64), self.empty((n,), np.float64), self.empty((t["Q"],), np.float64)
+        total, status = self.empty((1,), np.float64), self.zeros((1,), np.int32)
+        check(lib.msm_hmm_estep(self.handle, t["labels"].ptr, t["N"], t["k"], n, t["sequences"].ptr, t["Q"],
+                                t["chunk_ptr"].ptr, self._opt(t["chunk_seq"]), t["n_chunks"], A.ptr, B.ptr, p0.ptr,
+                                int(max_workgroups), work.ptr, gamma.ptr, Cm.ptr, g0.ptr, logL.ptr, total.ptr,
+                                status.ptr), self.handle)
+        E = None
+        if want_emissions:
+            E = self.empty((n, t["k"]), np.float64)
+            part = self.empty((max(t["units"], 1), n), np.float64)
+            check(lib.msm_hmm_emissions(self.handle, gamma.ptr, t["N"], n, t["k"], t["offsets"].ptr, t["members"].ptr,
+                                        t["unit_ptr"].ptr, self._opt(t["unit_state"]), t["units"], int(max_workgroups),
+                                        part.ptr, E.ptr), self.handle)
+        out = {"gamma": gamma, "C": Cm, "gamma0": g0, "logL": logL, "E": E, "total": float(total.to_host()[0]),
+               "status": int(status.to_host()[0])}
+        self.sync()  # the workspace is freed on return
+        return out
+
+    def hmm_viterbi(self, tables: dict, A: DeviceArray, B: DeviceArray, p0: DeviceArray, *,
+                    max_workgroups: int = 0) -> dict:
+        """The most probable hidden path of every sequence (msm_hmm_viterbi, include/msmhip.h).  Returns "path" int32
+        [N] on the device, in frame order (-1: a frame in no sequence, or in one of probability 0), "logp" f64 [Q] on
+        the device, and the host value "status" (HMM_* bits)."""
+        t = tables
+        n = self._hmm_model(t, A, B, p0)
+        work = self.empty((int(lib.msm_hmm_viterbi_workspace_bytes(n, t["k"], t["n_chunks"], t["Q"])) or 1,), np.uint8)
+        path, logp = self.empty((t["N"],), np.int32), self.empty((t["Q"],), np.float64)
+        status = self.zeros((1,), np.int32)
+        check(lib.msm_hmm_viterbi(self.handle, t["labels"].ptr, t["N"], t["k"], n, t["sequences"].ptr, t["Q"],
+                                  t["chunk_ptr"].ptr, self._opt(t["chunk_seq"]), t["n_chunks"], A.ptr, B.ptr, p0.ptr,
+                                  int(max_workgroups), work.ptr, path.ptr, logp.ptr, status.ptr), self.handle)
+        return {"path": path, "logp": logp, "status": int(status.to_host()[0])}   # synchronises: the workspace is free
+
+    def hmm_mstep(self, C_: DeviceArray, E: DeviceArray, gamma0: DeviceArray, n_sequences: int, A: DeviceArray,
+                  B: DeviceArray, p0: DeviceArray, *, reversible: bool = True, stationary: bool = False,
+                  maxerr: float = 1e-8, maxiter: int = 100_000) -> dict:
+        """The M-step (msm_hmm_mstep, include/msmhip.h): A, B and p0 are updated in place.  Returns {"pi": the
+        stationary vector of the new A, f64 [n] on the device, "status": HMM_* bits}."""
+        n, k = E.shape
+        pi, status = self.empty((n,), np.float64), self.zeros((1,), np.int32)
+        check(lib.msm_hmm_mstep(self.handle, n, k, int(n_sequences), C_.ptr, E.ptr, gamma0.ptr, int(bool(reversible)),
+                                int(bool(stationary)), int(maxiter), float(maxerr), A.ptr, B.ptr, p0.ptr, pi.ptr,
+                                status.ptr), self.handle)
+        return {"pi": pi, "status": int(status.to_host()[0])}
+
+    def hmm_iterations(self, tables: dict, A: DeviceArray, B: DeviceArray, p0: DeviceArray, n_iterations: int, *,
+                       state: dict | None = None, reversible: bool = True, stationary: bool = False,
+                       maxerr: float = 1e-8, maxiter: int = 100_000, max_workgroups: int = 0) -> dict:
+        """`n_iterations` EM iterations enqueued back to back (msm_hmm_iterations, include/msmhip.h); A, B and p0 are
+        updated in place.  Returns the state dict (pass it back in to reuse its buffers): device arrays "pi", "gamma",
+        "C", "E", "gamma0", "logL", and the host values "history" (sum of logL at the start of every iteration)
+        and "status"."""
+        t = tables
+        n = self._hmm_model(t, A, B, p0)
+        n_iterations = int(n_iterations)
+        if n_iterations < 1:
+            raise ValueError("n_iterations must be >= 1")
+        s = state
+        if s is None or s.get("n") != n or s["hist_d"].size < n_iterations:
+            s = {"n": n, "work": self._hmm_work(t, n), "gamma": self.zeros((t["N"], n), np.float64),
+                 "pi": self.empty((n,), np.float64), "C": self.empty((n, n), np.float64),
+                 "E": self.empty((n, t["k"]), np.float64), "gamma0": self.empty((n,), np.float64),
+                 "logL": self.empty((t["Q"],), np.float64), "hist_d": self.empty((n_iterations,), np.float64),
+                 "status_d": self.zeros((1,), np.int32)}
+        check(lib.msm_hmm_iterations(self.handle, t["labels"].ptr, t["N"], t["k"], n, t["sequences"].ptr, t["Q"],
+                                     t["chunk_ptr"].ptr, self._opt(t["chunk_seq"]), t["n_chunks"], t["offsets"].ptr,
+                                     t["members"].ptr, t["unit_ptr"].ptr, self._opt(t["unit_state"]), t["units"],
+                                     int(bool(reversible)), int(bool(stationary)), int(maxiter), float(maxerr),
+                                     n_iterations, int(max_workgroups), s["work"].ptr, A.ptr, B.ptr, p0.ptr,
+                                     s["pi"].ptr, s["gamma"].ptr, s["C"].ptr, s["E"].ptr, s["gamma0"].ptr,
+                                     s["logL"].ptr, s["hist_d"].ptr, s["status_d"].ptr), self.handle)
+        s["history"] = s["hist_d"].to_host()[:n_iterations].copy()
+        s["status"] = int(s["status_d"].to_host()[0])
+        return s
+
+    def hmm_fit(self, tables: dict, A: DeviceArray, B: DeviceArray, p0: DeviceArray, *, reversible: bool = True,
+                stationary: bool = False, accuracy: float = 1e-3, maxit: int = 1000, check_every: int = 8,
+                max_workgroups: int = 0) -> dict:
+        """Baum-Welch from (A, B, p0), updated in place: `check_every` iterations are enqueued with no host
+        synchronisation, then the likelihood history is read; stops after the first interval that holds an iteration
+        whose likelihood moved by less than `accuracy`, or at `maxit`.  Returns the state of hmm_iterations with "likelihoods" (one per
+        iteration run), "n_iterations" and "converged"; the parameters are those after the last iteration run, the
+        arrays "gamma", "C", "E" those of its E-step."""
+        check_every, maxit = max(1, int(check_every)), max(1, int(maxit))
+        hist: list[float] = []
+        state, converged = None, False
+        while len(hist) < maxit and not converged:
+            block = min(check_every, maxit - len(hist))
+            state = self.hmm_iterations(tables, A, B, p0, block, state=state, reversible=reversible,
+                                        stationary=stationary, max_workgroups=max_workgroups)
+            for v in state["history"]:
+                hist.append(float(v))
+            if state["status"] & (_lib.HMM_BAD_SYMBOL | _lib.HMM_BAD_TABLE):
+                raise ValueError(f"hmm_fit: the labels or the sequence tables are invalid (status {state['status']})")
+            if not np.isfinite(hist[-1]):
+                raise _lib.MsmError("hmm_fit: a sequence has probability 0 under the model (logL = -inf)")
+            d = np.abs(np.diff(hist))
+            converged = bool(d.size and (d < accuracy).any())
+        state["likelihoods"] = np.asarray(hist)
+        state["n_iterations"] = len(hist)
+        state["converged"] = converged
+        return state
+
     def state_counts(self, labels: DeviceArray, k: int, out: DeviceArray | None = None) -> DeviceArray:
         out = out if out is not None else self.empty((k,), np.int64)
         check(lib.msm_state_counts(self.handle, labels.ptr, labels.size, int(k), out.ptr), self.handle)

@@ -4,6 +4,7 @@ from .clustering import ClusteringResult, cluster_microstates  # noqa: F401
 from .estimation import (build_msm, build_simple_msm, check_transition_matrix, compute_free_energies, count_transitions,  # noqa: F401
                          effective_count_matrix, ensure_connected_counts, finalize_transition_and_stationary,
                          fit_reversible_msm, statistical_inefficiencies)
+from .hmm import HMMResult, coarse_grain_hmm, estimate_hmm, init_hmm_from_msm, lag_observations  # noqa: F401
 from .features import MSMFeatures, ca_distance_pairs, compute_msm_features  # noqa: F401
 from .its import (  # noqa: F401
     DEFAULT_ITS_LAGS,
