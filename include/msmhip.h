@@ -1632,6 +1632,61 @@ msm_status msm_hmm_iterations(msm_ctx* ctx, const int32_t* d_labels, int64_t N, 
                               double* d_B, double* d_p0, double* d_pi, double* d_gamma, double* d_C, double* d_E,
                               double* d_gamma0, double* d_logL, double* d_history, int32_t* d_status);
 
+/* ---- Metadynamics: hills bias, its gradient, the c(t) scan, a device ledger (csrc/metad.hip) ---------
+ * Written from Laio & Parrinello, PNAS 99, 12562 (2002), Barducci, Bussi & Parrinello, PRL 100, 020603 (2008) and
+ * Tiwary & Parrinello, J. Phys. Chem. B 119, 736 (2015), with the cutoff and the stretched kernel as PLUMED's METAD
+ * documents them.  The tests hold the kernels to a numpy restatement of the rule below (tests/_metad_ref.py), run in
+ * 80-bit floats.  Everything is fp64.
+ *
+ * d_hills f64 [H, 2 d + 1]: hill k is the record (centre [d], 1 / sigma [d], height); sigma is per hill, diagonal.
+ * h_period f64 [d] or NULL: the period of a periodic CV, 0 for one that is not.  The term of hill k at the point s:
+ *     dp_i = s_i - c_i;   periodic:  dp_i -= P_i * rint(dp_i / P_i);   z_i = dp_i * (1 / sigma_i)
+ *     dp2  = 0.5 * sum_i z_i^2   (ascending i);   the term and its gradient are 0 where dp2 >= cut  (cut > 0)
+ *     term = h * (A * exp(-dp2) + B),   d term / d s_i = -(h * (A * exp(-dp2))) * (z_i * (1 / sigma_i))
+ *   MSM_METAD_GAUSSIAN: A = 1, B = 0.  MSM_METAD_STRETCHED: A = 1 / (1 - exp(-cut)), B = -exp(-cut) * A, which
+ *   brings the term to 0 at the cutoff (PLUMED's default kernel).
+ * msm_metad_bias: d_cv f64 [n, ld], the first d columns of a row are a frame's CVs.  Frame f adds the hills
+ *   0 .. count[f] - 1 (d_count int32 [n], clamped to [0, H]; NULL: all H), in ascending hill index, into
+ *   d_bias f64 [n] and, where d_grad is not NULL, d_grad f64 [n, ldg] (columns 0 .. d - 1).  H = 0 gives zeros.
+ *   A frame with a non-finite CV is NaN in its own outputs and nowhere else.
+ *   Launch shape (msm_metad_plan: out = frames per workgroup, hills per tile, grid, LDS bytes): one frame per lane,
+ *   MSM_METAD_THREADS frames per workgroup trip in a grid-stride loop (max_workgroups > 0 caps the grid), the hills
+ *   staged through LDS in tiles of MSM_METAD_TILE.  A workgroup walks the hills up to the largest count of its
+ *   frames.  No lane shares a sum with another: a frame's bits depend on its CVs, its count and the hills alone, not
+ *   on the grid, the tile or its neighbours.  No scratch memory.
+ * msm_metad_grid_scan: a regular grid of d <= MSM_METAD_GRID_MAX_D CVs, point (i_0, .., i_{d-1}) at
+ *   lo_a + i_a * step_a, the last axis fastest, G = prod bins (a periodic axis carries no duplicate end point).
+ *   h_checkpoints int32 [M], ascending in [0, H]; a1 >= a2 >= 0.  Every lane keeps V of one grid point in a register
+ *   and walks all hills once in order; at checkpoint k_j (V_{k_j}: the first k_j hills) a workgroup forms
+ *   (max, sum exp(a V - max)) of its MSM_METAD_SCAN_TILE points for both exponents in a fixed order, and a second
+ *   launch merges the tiles in a fixed order (lane l of a wave adds the tiles l, l + 64, .. ascending, then a shuffle
+ *   tree):  d_lse f64 [M, 2],  lse[j, e] = log sum_g exp(a_e V_{k_j}(g)).
+ *   The maximum is subtracted before every exp, so a V may be of any size.  d_vgrid f64 [G] (may be NULL) receives
+ *   V_H.  The tile is fixed, so the bits do not depend on max_workgroups.  A negative, NaN or infinite height is
+ *   MSM_ERR_INVALID (the heights are read back before the scan is launched: the call waits for the stream, and is
+ *   not for graph capture).
+ * msm_metad_append: writes record `index` of a ledger of `capacity` records from h_record f64 [2 d + 1], passed to
+ *   the kernel by value: nothing is staged and nothing waits.  d_center (f64 [d], may be NULL) replaces the centre by
+ *   CVs that are still on the device; d_v (f64 [1], may be NULL) scales the height by exp(v_scale * d_v[0]): the
+ *   well-tempered rule h0 exp(-V(centre) / ((gamma - 1) kT)) with V evaluated by msm_metad_bias just before. */
+#define MSM_METAD_MAX_D 8
+#define MSM_METAD_GRID_MAX_D 3
+#define MSM_METAD_THREADS 256
+#define MSM_METAD_TILE 128
+#define MSM_METAD_SCAN_TILE 256
+#define MSM_METAD_GAUSSIAN 0
+#define MSM_METAD_STRETCHED 1
+msm_status msm_metad_plan(msm_ctx* ctx, int64_t n, int H, int d, int max_workgroups, int64_t out[4]);
+msm_status msm_metad_bias(msm_ctx* ctx, const double* d_cv, int64_t n, int64_t ld, int d, const double* d_hills, int H,
+                          const double* h_period, int kernel, double cut, const int32_t* d_count, int max_workgroups,
+                          double* d_bias, double* d_grad, int64_t ldg);
+msm_status msm_metad_grid_scan(msm_ctx* ctx, const double* d_hills, int H, int d, const double* h_lo,
+                               const double* h_step, const int32_t* h_bins, const double* h_period, int kernel,
+                               double cut, const int32_t* h_checkpoints, int M, double a1, double a2,
+                               int max_workgroups, double* d_lse, double* d_vgrid);
+msm_status msm_metad_append(msm_ctx* ctx, double* d_hills, int capacity, int index, int d, const double* h_record,
+                            const double* d_center, const double* d_v, double v_scale);
+
 /* ------------------------------------------------------------------ */
 /* exchange steps of the sharded path (RCCL over xGMI)                  */
 /* ------------------------------------------------------------------ */

@@ -58,6 +58,10 @@ TRAM_ROWS_MULTIPLIERS, TRAM_ROWS_COUNTS = 0, 1
 # HMM (MSM_HMM_* in include/msmhip.h): most hidden states, steps of a chunk, the fixed point's iteration cap, status bits
 HMM_MAX_HIDDEN, HMM_CHUNK, HMM_MAX_FIXED_POINT = 16, 64, 1_000_000
 HMM_BAD_SYMBOL, HMM_ZERO_PROB, HMM_EMPTY_STATE, HMM_BAD_TABLE, HMM_NOT_CONVERGED = 1, 2, 4, 8, 16
+# metadynamics (MSM_METAD_* in include/msmhip.h): most CVs of a hill and of a grid, frames of a workgroup trip, hills of
+# an LDS tile, grid points of a scan tile, the hill kernels
+METAD_MAX_D, METAD_GRID_MAX_D, METAD_THREADS, METAD_TILE, METAD_SCAN_TILE = 8, 3, 256, 128, 256
+METAD_KERNELS = {"gaussian": 0, "stretched-gaussian": 1}
 
 
 class MsmError(RuntimeError):
@@ -275,6 +279,11 @@ _PROTOTYPES: dict[str, tuple] = {
     "msm_hmm_iterations": (_i32, [_vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32,
                                   _i32, _i32, _f64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                   _vp]),
+    "msm_metad_plan": (_i32, [_vp, _i64, _i32, _i32, _i32, _vp]),
+    "msm_metad_bias": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _i32, _vp, _i32, _f64, _vp, _i32, _vp, _vp, _i64]),
+    "msm_metad_grid_scan": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _f64, _vp, _i32, _f64, _f64, _i32,
+                                   _vp, _vp]),
+    "msm_metad_append": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _f64]),
 }
 
 DECLARED_SYMBOLS = tuple(_PROTOTYPES)

@@ -1269,6 +1269,102 @@ class Engine:
         state["converged"] = converged
         return state
 
+    # -- metadynamics (csrc/metad.hip) -----------------------------------------------------------
+    @staticmethod
+    def _metad_shape(hills: DeviceArray, n_hills: int | None, periods, kernel: str, max_d: int):
+        """(H, d, periods array or None, kernel code) of a packed ledger hills f64 [capacity, 2 d + 1]."""
+        if hills.dtype != np.float64 or len(hills.shape) != 2 or hills.shape[1] < 3 or hills.shape[1] % 2 == 0:
+            raise ValueError(f"hills must be float64 with shape (capacity, 2 d + 1), got {hills.shape} {hills.dtype}")
+        d = (hills.shape[1] - 1) // 2
+        if d > max_d:
+            raise ValueError(f"{d} collective variables, at most {max_d} are supported here")
+        H = hills.shape[0] if n_hills is None else int(n_hills)
+        if not 0 <= H <= hills.shape[0]:
+            raise ValueError(f"n_hills = {H} outside [0, {hills.shape[0]}]")
+        if kernel not in _lib.METAD_KERNELS:
+            raise ValueError(f"kernel must be one of {sorted(_lib.METAD_KERNELS)}, got {kernel!r}")
+        per = None
+        if periods is not None:
+            per = np.ascontiguousarray(periods, np.float64).reshape(-1)
+            if per.size != d or not (np.isfinite(per).all() and (per >= 0).all()):
+                raise ValueError(f"periods must be {d} finite numbers >= 0 (0: not periodic)")
+        return H, d, per, _lib.METAD_KERNELS[kernel]
+
+    def metad_plan(self, n: int, n_hills: int, d: int, max_workgroups: int = 0) -> dict:
+        """What metad_bias would launch (msm_metad_plan, include/msmhip.h).  Launches nothing."""
+        out = (C.c_int64 * 4)()
+        check(lib.msm_metad_plan(self.handle, int(n), int(n_hills), int(d), int(max_workgroups), out), self.handle)
+        return {"frames_per_workgroup": int(out[0]), "hills_per_tile": int(out[1]), "grid": int(out[2]),
+                "lds_bytes": int(out[3])}
+
+    def metad_bias(self, cv: DeviceArray, hills: DeviceArray, n_hills: int | None = None, *, periods=None,
+                   kernel: str = "gaussian", cut: float = 6.25, counts: DeviceArray | None = None, grad: bool = False,
+                   max_workgroups: int = 0, bias: DeviceArray | None = None, grad_out: DeviceArray | None = None):
+        """The hills sum at the frames cv f64 [n, ld >= d] (msm_metad_bias): `bias` f64 [n] and, with grad, its
+        gradient f64 [n, d] in the CVs, device arrays.  hills f64 [capacity, 2 d + 1] (centre, 1 / sigma, height), of
+        which the first `n_hills` count; frame f sums the hills 0 .. counts[f] - 1 (int32 [n]; None: all).  With
+        preallocated `bias` / `grad_out` nothing is allocated, uploaded or waited for."""
+        H, d, per, code = self._metad_shape(hills, n_hills, periods, kernel, _lib.METAD_MAX_D)
+        if cv.dtype != np.float64 or len(cv.shape) != 2 or cv.shape[1] < d or cv.shape[0] < 1:
+            raise ValueError(f"cv must be float64 with shape (n >= 1, >= {d}), got {cv.shape} {cv.dtype}")
+        n, ld = cv.shape
+        if counts is not None and (counts.dtype != np.int32 or counts.size != n):
+            raise ValueError(f"counts must be int32 of {n} entries")
+        bias = bias if bias is not None else self.empty((n,), np.float64)
+        if grad and grad_out is None:
+            grad_out = self.empty((n, d), np.float64)
+        if bias.dtype != np.float64 or bias.size != n:
+            raise ValueError(f"bias must be float64 of {n} entries")
+        if grad_out is not None and (grad_out.dtype != np.float64 or len(grad_out.shape) != 2
+                                     or grad_out.shape[0] != n or grad_out.shape[1] < d):
+            raise ValueError(f"grad_out must be float64 with shape ({n}, >= {d})")
+        check(lib.msm_metad_bias(self.handle, cv.ptr, n, ld, d, hills.ptr, H, per.ctypes.data if per is not None else None,
+                                 code, float(cut), counts.ptr if counts is not None else None, int(max_workgroups),
+                                 bias.ptr, grad_out.ptr if grad_out is not None else None,
+                                 grad_out.shape[1] if grad_out is not None else 0), self.handle)
+        return (bias, grad_out) if grad_out is not None else bias
+
+    def metad_grid_scan(self, hills: DeviceArray, n_hills: int | None, lo, step, bins, checkpoints, a1: float,
+                        a2: float, *, periods=None, kernel: str = "gaussian", cut: float = 6.25,
+                        want_grid: bool = False, max_workgroups: int = 0):
+        """lse f64 [M, 2] with lse[j, e] = log sum_g exp(a_e V_{k_j}(g)) over the regular grid lo + i * step of
+        `bins` points per axis (msm_metad_grid_scan), V_k the sum of the first k hills; checkpoints ascending in
+        [0, n_hills].  -> (lse, V_H on the grid f64 [bins] or None), device arrays.  A negative height raises
+        ValueError; the call waits for the stream."""
+        H, d, per, code = self._metad_shape(hills, n_hills, periods, kernel, _lib.METAD_GRID_MAX_D)
+        lo, step = (np.ascontiguousarray(a, np.float64).reshape(-1) for a in (lo, step))
+        bins = np.ascontiguousarray(bins, np.int32).reshape(-1)
+        if lo.size != d or step.size != d or bins.size != d:
+            raise ValueError(f"lo, step and bins must have {d} entries")
+        ck = np.ascontiguousarray(checkpoints, np.int32).reshape(-1)
+        if ck.size < 1:
+            raise ValueError("metad_grid_scan needs at least one checkpoint")
+        lse = self.empty((ck.size, 2), np.float64)
+        vgrid = self.empty(tuple(int(b) for b in bins), np.float64) if want_grid else None
+        check(lib.msm_metad_grid_scan(self.handle, hills.ptr, H, d, lo.ctypes.data, step.ctypes.data, bins.ctypes.data,
+                                      per.ctypes.data if per is not None else None, code, float(cut), ck.ctypes.data,
+                                      ck.size, float(a1), float(a2), int(max_workgroups), lse.ptr,
+                                      vgrid.ptr if vgrid is not None else None), self.handle)
+        self.sync()  # the uploaded checkpoint table is shared: the scan has read it before the next upload
+        return lse, vgrid
+
+    def metad_append(self, hills: DeviceArray, index: int, record, *, center: DeviceArray | None = None,
+                     v: DeviceArray | None = None, v_scale: float = 0.0) -> None:
+        """Writes hill `index` of the ledger hills f64 [capacity, 2 d + 1] (msm_metad_append): `record` = centre,
+        1 / sigma, height, passed by value; `center` f64 [>= d] on the device replaces the centre, `v` f64 [1] scales
+        the height by exp(v_scale * v[0]).  Nothing is staged and nothing waits."""
+        _H, d, _per, _code = self._metad_shape(hills, None, None, "gaussian", _lib.METAD_MAX_D)
+        rec = np.ascontiguousarray(record, np.float64).reshape(-1)
+        if rec.size != 2 * d + 1:
+            raise ValueError(f"a hill record has {2 * d + 1} entries, got {rec.size}")
+        if center is not None and (center.dtype != np.float64 or center.size < d):
+            raise ValueError(f"center must be float64 with at least {d} entries")
+        if v is not None and (v.dtype != np.float64 or v.size < 1):
+            raise ValueError("v must be float64 with one entry")
+        check(lib.msm_metad_append(self.handle, hills.ptr, hills.shape[0], int(index), d, rec.ctypes.data,
+                                   center.ptr if center is not None else None, v.ptr if v is not None else None,
+                                   float(v_scale)), self.handle)
+
     def state_counts(self, labels: DeviceArray, k: int, out: DeviceArray | None = None) -> DeviceArray:
         out = out if out is not None else self.empty((k,), np.int64)
         check(lib.msm_state_counts(self.handle, labels.ptr, labels.size, int(k), out.ptr), self.handle)

@@ -4,11 +4,16 @@
 ``temperature_weights`` is the replica-ladder case built from one energy per frame, ``tram`` and ``tram_from_counts``
 couple the ensembles through one reversible Markov model each and return that model beside the weights, and
 ``Reweighter`` writes ``dataset["frame_weights"]``, where discretize_dataset, prepare_msm_discretization and the
-free-energy entry points pick them up.
+free-energy entry points pick them up.  Metadynamics (csrc/metad.hip) is the bias that changes with time:
+``HillsLedger`` holds the hills on the device, ``metadynamics_weights`` and ``MetadynamicsReweighter`` undo them, and
+``read_hills`` / ``read_colvar`` read PLUMED's files.
 """
 
 from .mbar import MBARResult, mbar, temperature_weights
+from .metadynamics import (HillsLedger, MetadWeights, MetadynamicsReweighter, metadynamics_weights, read_colvar,
+                           read_hills)
 from .reweighter import Reweighter
 from .tram import TRAMResult, tram, tram_from_counts
 
-__all__ = ["MBARResult", "Reweighter", "TRAMResult", "mbar", "temperature_weights", "tram", "tram_from_counts"]
+__all__ = ["HillsLedger", "MBARResult", "MetadWeights", "MetadynamicsReweighter", "Reweighter", "TRAMResult", "mbar",
+           "metadynamics_weights", "read_colvar", "read_hills", "temperature_weights", "tram", "tram_from_counts"]
