@@ -900,6 +900,37 @@ msm_status msm_kmeans_lloyd_pass_from(msm_ctx* ctx, const void* d_x, msm_dtype d
                                       double* d_centers, int k, const double* d_mean, const double* d_std,
                                       const void* d_image, double* d_state, int32_t* d_prev_labels, int64_t* d_sums,
                                       int64_t* d_counts, int first_pass);
+/* The deferred chain: a second way of chaining the Lloyd passes of a single-shard fit, with the bits of
+ * msm_kmeans_lloyd_pass_from + msm_kmeans_assign_packed after every launch.  A pass ends with the flush of its member
+ * sums; the NEXT launch (a pass, or the closing assign) closes the iteration in its prologue: every workgroup computes
+ * centres <- sums / counts for itself from what the kernel boundary has ordered, keeps them in its LDS, and one of them
+ * writes d_centers_out and the fit state.  No workgroup waits for another inside a launch.
+ *   d_centers_in   the centres before the pending close (read only); d_centers_out receives the centres the launch
+ *                  works with (close_pending != 0: a different buffer; the caller alternates two)
+ *   close_pending  0 on the first pass of a fit (nothing to close: d_centers_in are the centres, d_sums_in is not read)
+ *   member sums    rotate through THREE buffers, so that no workgroup reads what another adds to in the same launch:
+ *                  d_sums_in / d_counts_in hold the complete sums of the previous pass; d_sums_out / d_counts_out must be
+ *                  ZERO when the launch begins and receive in + the moves of this pass; d_sums_next / d_counts_next are
+ *                  cleared for the launch after this one.  (First pass: `out` cleared by msm_kmeans_fit_begin_clear.)
+ *   a fit that has converged (state.done): later passes compute nothing and keep both rotations going.
+ * Incremental only: d_prev_labels is required (first_pass as in msm_kmeans_lloyd_pass_from).
+ * *h_applied (HOST int) = 1 when the launch was made, 0 (and MSM_OK, nothing launched or written) where this flavour
+ * does not run -- fp32 frames, whitening, d <= 4 or d > 10, k d > 5120, no image, or the fp64 centre table does not fit
+ * the LDS next to the rest: the caller then runs the entry points above.  msm_kmeans_assign_closing: the assignment
+ * under the centres of the pending close (labels, d_mindist as msm_kmeans_assign); close_pending == 0: d_centers_in as
+ * they are, d_state / sums may be NULL. */
+msm_status msm_kmeans_lloyd_pass_deferred(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n, int d, int64_t ld,
+                                          const double* d_centers_in, double* d_centers_out, int k,
+                                          const double* d_mean, const double* d_std, const void* d_image,
+                                          double* d_state, int32_t* d_prev_labels, const int64_t* d_sums_in,
+                                          const int64_t* d_counts_in, int64_t* d_sums_out, int64_t* d_counts_out,
+                                          int64_t* d_sums_next, int64_t* d_counts_next, int close_pending,
+                                          int first_pass, int* h_applied);
+msm_status msm_kmeans_assign_closing(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n, int d, int64_t ld,
+                                     const double* d_centers_in, double* d_centers_out, int k, const double* d_mean,
+                                     const double* d_std, const void* d_image, double* d_state,
+                                     const int64_t* d_sums_in, const int64_t* d_counts_in, int close_pending,
+                                     int32_t* d_labels, double* d_mindist, int* h_applied);
 msm_status msm_kmeans_filter_scanned(msm_ctx* ctx, uint64_t* h_out, int reset);
 /* Hardware rule the filter's certificate rests on (kmeans_filter.h, step 1): n_tiles independent
  * v_mfma_f32_16x16x32_bf16 instructions, D = A B + C with A [16][32], B [32][16] bf16 (row major, raw 16-bit

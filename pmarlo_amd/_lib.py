@@ -191,6 +191,10 @@ _PROTOTYPES: dict[str, tuple] = {
                                           _i32]),
     "msm_kmeans_accumulate_delta_from": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
                                                 _vp, _i32]),
+    "msm_kmeans_lloyd_pass_deferred": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp,
+                                              _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, C.POINTER(_i32)]),
+    "msm_kmeans_assign_closing": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                         _i32, _vp, _vp, C.POINTER(_i32)]),
     "msm_kmeans_filter_scanned": (_i32, [_vp, C.POINTER(C.c_uint64), _i32]),
     "msm_kmeans_init_plusplus": (_i32, [_vp, _vp, _i32, _i64, _i32, _i64, _vp, _vp, _i32, C.c_uint64, _f64, _vp, _vp, _vp]),
     "msm_mfma_bf16_probe": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32]),

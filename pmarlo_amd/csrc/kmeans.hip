@@ -934,6 +934,7 @@ bool filter_enabled() {
 // MSM_KMEANS_DEBUG (any value, read at every launch): one line on stderr per assign / accumulate launch, either
 // "msm_kmeans: filter T= n= d= k= ACCUM=" or "msm_kmeans: fp64 T= n= d= k= KS= NF= MT= ACCUM= FOLD= MULTI= tile_k=
 // lds_acc= grid= lds=": the kernel instantiation that ran.  tests/_kmeans_ref.py restates the rule; the GPU tests compare.
+// A launch of the deferred chain says "msm_kmeans: filter T=f64 n= d= k= ACCUM= close=prologue pending= lds=".
 
 // whole units of 64 rows (the filter kernel loads a unit without clamping), then one uint4: [max |x| bound | e_x | pad]
 size_t filter_image_bytes(int64_t n, int) { return (size_t)((n + 63) & ~(int64_t)63) * 16 * kFilterRowQ + 16; }
@@ -1000,7 +1001,7 @@ msm_status launch_filter_dp(msm_ctx* ctx, const T* x, int64_t n, int d, int64_t 
         MSM_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * kWaves), lds, ctx->stream, x, n, d, ld, k, mean, stdv, image, centers,
                        labels, mindist, st, sums, counts, stats, stats ? upd_centers : nullptr,
-                       stats ? (unsigned int*)(stats + 1) : nullptr, (int)first_pass);
+                       stats ? (unsigned int*)(stats + 1) : nullptr, (int)first_pass, FilterNoClose{});
     MSM_CHECK_LAUNCH(ctx);
     return MSM_OK;
 }
@@ -1018,6 +1019,38 @@ msm_status launch_filter(msm_ctx* ctx, const T* x, int64_t n, int d, int64_t ld,
 }
 
 bool filter_fits(int k, int d, bool accum) { return filter_enabled() && d <= kFilterMaxD && filter_lds_bytes(k, d, accum) != 0; }
+
+// The deferred chain's flavour runs where the bench chain's two kernels do: fp64 frames without whitening, 4 < d <= 10, a
+// table the prologue close takes in one round of loads, and room in the LDS for the fp64 centres on top of the rest
+bool filter_close_fits(msm_dtype dtype, int k, int d, bool whiten, bool accum) {
+    return filter_enabled() && dtype == MSM_F64 && !whiten && d <= kFilterMaxD && filter_dp(d) == 10 &&
+           (int64_t)k * d <= 1024 * kFilterCloseCH && filter_lds_bytes_close(k, d, accum) != 0;
+}
+
+template <bool ACCUM>
+msm_status launch_filter_close(msm_ctx* ctx, const double* x, int64_t n, int d, int64_t ld, const double* centers, int k,
+                               const uint4* image, int32_t* labels, double* mindist, const FitState* st,
+                               unsigned long long* sums, unsigned long long* counts, bool first_pass,
+                               const FilterCloseArgs& cl) {
+    constexpr int NF = 4, kWaves = 16;
+    const size_t lds = filter_lds_bytes_close(k, d, ACCUM);
+    const int64_t n_units = (n + 16 * NF - 1) / (16 * NF);
+    const int grid = (int)std::min<int64_t>((n_units + kWaves - 1) / kWaves, (int64_t)ctx->n_cu);
+    unsigned long long* stats = nullptr;
+    msm_status rs = filter_stats_buffer(ctx, &stats);
+    if (rs != MSM_OK) return rs;
+    if (getenv("MSM_KMEANS_DEBUG"))
+        fprintf(stderr, "msm_kmeans: filter T=f64 n=%lld d=%d k=%d ACCUM=%d close=prologue pending=%d lds=%zu\n", (long long)n, d,
+                k, (int)ACCUM, cl.close_pending, lds);
+    auto kern = kmeans_filter_kernel<double, 10, NF, ACCUM, false, FilterCloseArgs>;
+    if (lds > 48 * 1024)
+        MSM_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * kWaves), lds, ctx->stream, x, n, d, ld, k, (const double*)nullptr,
+                       (const double*)nullptr, image, centers, labels, mindist, st, sums, counts, stats, (double*)nullptr,
+                       (unsigned int*)nullptr, (int)first_pass, cl);
+    MSM_CHECK_LAUNCH(ctx);
+    return MSM_OK;
+}
 
 // image: the frames' bf16 images (msm_kmeans_pack) or NULL (built here into the context's buffer)
 template <typename T, bool ACCUM>
@@ -1281,6 +1314,60 @@ msm_status msm_kmeans_lloyd_pass(msm_ctx* ctx, const void* d_x, msm_dtype dtype,
                                  double* d_state, int32_t* d_prev_labels, int64_t* d_sums, int64_t* d_counts) {
     return msm_kmeans_lloyd_pass_from(ctx, d_x, dtype, n, d, ld, d_centers, k, d_mean, d_std, d_image, d_state,
                                       d_prev_labels, d_sums, d_counts, 0);
+}
+
+// The deferred chain (header: msm_kmeans_lloyd_pass_deferred).  *h_applied = 0 and nothing launched where the flavour does
+// not run; the caller then takes msm_kmeans_lloyd_pass_from / msm_kmeans_assign_packed.
+msm_status msm_kmeans_lloyd_pass_deferred(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n, int d, int64_t ld,
+                                          const double* d_centers_in, double* d_centers_out, int k, const double* d_mean,
+                                          const double* d_std, const void* d_image, double* d_state, int32_t* d_prev_labels,
+                                          const int64_t* d_sums_in, const int64_t* d_counts_in, int64_t* d_sums_out,
+                                          int64_t* d_counts_out, int64_t* d_sums_next, int64_t* d_counts_next,
+                                          int close_pending, int first_pass, int* h_applied) {
+    if (!ctx || !h_applied) return MSM_ERR_INVALID;
+    *h_applied = 0;
+    MSM_REQUIRE(ctx, n >= 1 && d >= 1 && k >= 1 && ld >= d, "msm_kmeans_lloyd_pass_deferred: bad shape");
+    MSM_REQUIRE(ctx, (d_mean == nullptr) == (d_std == nullptr), "msm_kmeans_lloyd_pass_deferred: mean/std must come together");
+    MSM_REQUIRE(ctx, dtype == MSM_F32 || dtype == MSM_F64, "msm_kmeans_lloyd_pass_deferred: bad dtype");
+    MSM_REQUIRE(ctx, d_x && d_centers_in && d_centers_out && d_state && d_sums_out && d_counts_out && d_sums_next && d_counts_next,
+                "msm_kmeans_lloyd_pass_deferred: NULL pointer");
+    MSM_REQUIRE(ctx, d_prev_labels, "msm_kmeans_lloyd_pass_deferred: the sums are carried from pass to pass (delta mode): "
+                "d_prev_labels is required");
+    MSM_REQUIRE(ctx, !close_pending || (d_sums_in && d_counts_in && d_centers_in != d_centers_out),
+                "msm_kmeans_lloyd_pass_deferred: a pending close needs the previous pass's sums and two centre buffers");
+    MSM_REQUIRE(ctx, d_sums_out != d_sums_next && d_sums_in != d_sums_out && d_sums_in != d_sums_next,
+                "msm_kmeans_lloyd_pass_deferred: the three member-sum buffers must differ");
+    if (!d_image || !filter_close_fits(dtype, k, d, d_mean != nullptr, true)) return MSM_OK;
+    FilterCloseArgs cl{d_centers_out, (const unsigned long long*)d_sums_in, (const unsigned long long*)d_counts_in,
+                       (unsigned long long*)d_sums_next, (unsigned long long*)d_counts_next, close_pending != 0};
+    msm_status rs = launch_filter_close<true>(ctx, (const double*)d_x, n, d, ld, d_centers_in, k, (const uint4*)d_image,
+                                              d_prev_labels, nullptr, (const FitState*)d_state,
+                                              (unsigned long long*)d_sums_out, (unsigned long long*)d_counts_out,
+                                              first_pass != 0, cl);
+    if (rs == MSM_OK) *h_applied = 1;
+    return rs;
+}
+
+msm_status msm_kmeans_assign_closing(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n, int d, int64_t ld,
+                                     const double* d_centers_in, double* d_centers_out, int k, const double* d_mean,
+                                     const double* d_std, const void* d_image, double* d_state, const int64_t* d_sums_in,
+                                     const int64_t* d_counts_in, int close_pending, int32_t* d_labels, double* d_mindist,
+                                     int* h_applied) {
+    if (!ctx || !h_applied) return MSM_ERR_INVALID;
+    *h_applied = 0;
+    MSM_REQUIRE(ctx, n >= 1 && d >= 1 && k >= 1 && ld >= d, "msm_kmeans_assign_closing: bad shape");
+    MSM_REQUIRE(ctx, (d_mean == nullptr) == (d_std == nullptr), "msm_kmeans_assign_closing: mean/std must come together");
+    MSM_REQUIRE(ctx, dtype == MSM_F32 || dtype == MSM_F64, "msm_kmeans_assign_closing: bad dtype");
+    MSM_REQUIRE(ctx, d_x && d_centers_in && d_centers_out && d_labels, "msm_kmeans_assign_closing: NULL pointer");
+    MSM_REQUIRE(ctx, !close_pending || (d_state && d_sums_in && d_counts_in && d_centers_in != d_centers_out),
+                "msm_kmeans_assign_closing: a pending close needs the fit state, the last pass's sums and two centre buffers");
+    if (!d_image || !filter_close_fits(dtype, k, d, d_mean != nullptr, false)) return MSM_OK;
+    FilterCloseArgs cl{d_centers_out, (const unsigned long long*)d_sums_in, (const unsigned long long*)d_counts_in, nullptr,
+                       nullptr, close_pending != 0};
+    msm_status rs = launch_filter_close<false>(ctx, (const double*)d_x, n, d, ld, d_centers_in, k, (const uint4*)d_image,
+                                               d_labels, d_mindist, (const FitState*)d_state, nullptr, nullptr, false, cl);
+    if (rs == MSM_OK) *h_applied = 1;
+    return rs;
 }
 
 msm_status msm_kmeans_accumulate_delta_from(msm_ctx* ctx, const void* d_x, msm_dtype dtype, int64_t n, int d, int64_t ld,

@@ -86,6 +86,7 @@ __host__ __device__ constexpr int filter_waves(int, bool, bool) { return MSM_KMF
 __host__ __device__ constexpr int filter_waves(int dp, bool heavy, bool plain) { return dp == 10 && heavy && !plain ? 12 : 16; }
 #endif
 constexpr int kFilterMaxD = 10;
+constexpr int kFilterCloseCH = 5;                                // prologue close: k d <= 5 x 1024 elements in one round of loads
 constexpr int kFilterRowQ = 3;                                   // uint4 per frame image (48 bytes)
 constexpr double kFilterHi = 1e18;                               // unscaled range guard (the fp32 pick)
 constexpr double kFilterScaledHi = 16384.0;                      // 2^14: scaled range guard (fp16 operands)
@@ -424,7 +425,7 @@ __device__ __forceinline__ void filter_load_frame(const T* __restrict__ x, int64
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// LDS of the main kernel: img | tab | hs | lsum [k][d], lcnt [k] u64 (ACCUM)
+// LDS of the main kernel: img | tab | hs | lsum [k][d], lcnt [k] u64 (ACCUM) | cen [k][d] f64 (CLOSE)
 // centres <- sums / counts, shift2, n_iter, done: what kmeans_update_kernel (kmeans.hip) does, by one workgroup of MT
 // threads, with the additions of shift2 in the order of that kernel's 1024 threads (virtual thread v takes the
 // elements v, v + 1024, ...; 64 consecutive virtual threads add up by the same shuffles; the sixteen partial sums in
@@ -479,14 +480,36 @@ __device__ __forceinline__ void filter_close_iteration(const unsigned long long*
 }
 
 // ---------------------------------------------------------------------------------------------------------
-template <typename T, int DP, int NF, bool ACCUM, bool WHITEN>
+// CL = FilterCloseArgs (CLOSE; msm_kmeans_lloyd_pass_deferred / msm_kmeans_assign_closing, fp64 frames without whitening): the
+// launch closes the Lloyd iteration of its PREDECESSOR in its own prologue (every workgroup for itself, from the member sums
+// the kernel boundary has ordered), keeps the fp64 centre table in the LDS, and ends with its flush: no workgroup
+// waits for another.  The member sums rotate through three buffers so that no workgroup reads what another one of
+// the same launch adds to: `sums_in` / `counts_in` (complete, read only), `sums` / `counts` (zero when the launch
+// begins; receive sums_in + this launch's moves), `sums_clear` / `counts_clear` (zeroed for the next launch).  The
+// LAST workgroup (the one with the fewest units) writes everything global that is not a flush: centers_out, the
+// fit state, the carry of sums_in and the clear.  `centers` are then the centres BEFORE the pending close, never written
+// in this launch.  CL = FilterNoClose: the kernel as it was, with the ticket close in its epilogue where upd_centers is given.
+struct FilterNoClose {
+    static constexpr bool kClose = false;
+};
+struct FilterCloseArgs {
+    static constexpr bool kClose = true;
+    double* centers_out;
+    const unsigned long long* sums_in;
+    const unsigned long long* counts_in;
+    unsigned long long* sums_clear;
+    unsigned long long* counts_clear;
+    int close_pending;
+};
+template <typename T, int DP, int NF, bool ACCUM, bool WHITEN, typename CL = FilterNoClose>
 __global__ __launch_bounds__(64 * filter_waves(DP, ACCUM, sizeof(T) == 8 && !WHITEN)) void kmeans_filter_kernel(
     const T* __restrict__ x, int64_t n, int d, int64_t ld, int k, const double* __restrict__ mean,
     const double* __restrict__ stdv, const uint4* __restrict__ image, const double* __restrict__ centers,
     int32_t* __restrict__ labels,
     double* __restrict__ mindist, const FitState* __restrict__ st, unsigned long long* __restrict__ sums,
     unsigned long long* __restrict__ counts, unsigned long long* __restrict__ n_scanned, double* upd_centers,
-    unsigned int* __restrict__ ticket, int first_pass) {
+    unsigned int* __restrict__ ticket, int first_pass, CL cl) {
+    constexpr bool CLOSE = CL::kClose;
     // first_pass (delta mode): no frame is booked under a centre yet -- every previous label counts as -1 and `labels`
     // is only written, so the fit needs neither a fill of the label buffer nor the pass over it (a kernel argument:
     // uniform, it stays in a scalar register)
@@ -497,9 +520,44 @@ __global__ __launch_bounds__(64 * filter_waves(DP, ACCUM, sizeof(T) == 8 && !WHI
     // frames that move their member sums read their fp64 row once more (filter_waves)
     constexpr bool kReloadZ = ACCUM && DP == 10;
     static_assert(NF == 4, "one frame group per lane quarter: a unit is 64 frames, one per lane in the candidate pick");
+    static_assert(!CLOSE || (kMT == 1024 && sizeof(T) == 8 && !WHITEN), "the prologue close is kmeans_update_kernel's 1024 threads");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    // CLOSE: the workgroup that writes the global results of the close; with the rounded-up deal of units it has the fewest
+    const bool closer = CLOSE && blockIdx.x == gridDim.x - 1;
+    // CLOSE: carry the complete member sums into this launch's buffer (atomics: other workgroups are adding their moves
+    // to it) and clear the buffer of the next launch
+    auto close_housekeeping = [&]() {
+      if constexpr (CLOSE) {
+        if (cl.close_pending && cl.sums_in) {
+            for (int i = threadIdx.x; i < k * d; i += kMT) {
+                const unsigned long long v = cl.sums_in[i];
+                if (v) atomicAdd(&sums[i], v);
+            }
+            for (int i = threadIdx.x; i < k; i += kMT) {
+                const unsigned long long v = cl.counts_in[i];
+                if (v) atomicAdd(&counts[i], v);
+            }
+        }
+        if (cl.sums_clear) {
+            for (int i = threadIdx.x; i < k * d; i += kMT) cl.sums_clear[i] = 0ull;
+            for (int i = threadIdx.x; i < k; i += kMT) cl.counts_clear[i] = 0ull;
+        }
+      }
+    };
     if constexpr (ACCUM) {
-        if (st->done != 0.0) return;
+        // (CLOSE: the closing workgroup of THIS launch may set `done` while a late workgroup arrives here; that one
+        // returns now, the others a few lines down when they find the same shift -- nothing differs)
+        if (st->done != 0.0) {
+            if constexpr (CLOSE) {
+                // converged in an earlier launch: nothing is computed, the buffers keep their rotation
+                if (closer) {
+                    if (cl.close_pending && cl.centers_out != centers)
+                        for (int i = threadIdx.x; i < k * d; i += kMT) cl.centers_out[i] = centers[i];
+                    close_housekeeping();
+                }
+            }
+            return;
+        }
     }
     const int k16 = (k + 15) & ~15;
     const int n_tiles = ((k16 / 16) + 1) & ~1;            // even: the loop takes tile pairs
@@ -509,6 +567,10 @@ __global__ __launch_bounds__(64 * filter_waves(DP, ACCUM, sizeof(T) == 8 && !WHI
     double* hs = reinterpret_cast<double*>(cz + (size_t)n_tiles * 16);
     unsigned long long* lsum = reinterpret_cast<unsigned long long*>(hs + (size_t)n_tiles * 16);
     unsigned long long* lcnt = lsum + (ACCUM ? (size_t)k * d : 0);
+    // CLOSE: cen [k][d] f64, the centres of this launch -- every fp64 centre coordinate the kernel reads comes from here
+    // (centers_out is being written during the launch)
+    double* cen = reinterpret_cast<double*>(lcnt + (ACCUM ? (size_t)k : 0));
+    const double* crows = CLOSE ? cen : centers;
     __shared__ int unit_ctr;
     __shared__ int any_bad;
     __shared__ unsigned long long cmax_bits;
@@ -526,7 +588,71 @@ __global__ __launch_bounds__(64 * filter_waves(DP, ACCUM, sizeof(T) == 8 && !WHI
     if constexpr (ACCUM) {
         for (int i = tid; i < k * (d + 1); i += kMT) lsum[i] = 0ull;
     }
-    __syncthreads();
+    if constexpr (CLOSE) {
+        // ---- the close of the previous launch's iteration: the arithmetic of filter_close_iteration<1024> (thread =
+        // virtual thread, elements tid, tid + 1024, ... in ascending order, the same shuffles, the sixteen partial sums in
+        // order), by every workgroup for itself: same inputs, same bits on every CU.  All loads go out before any
+        // arithmetic: one round trip (kFilterCloseCH x 1024 elements; the host sends larger tables elsewhere)
+        __shared__ double red[16];
+        constexpr int CH = kFilterCloseCH;
+        long long cnt[CH], sm[CH];
+        double old[CH];
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+            const int i = tid + c * 1024;
+            cnt[c] = 0;
+            sm[c] = 0;
+            old[c] = 0.0;
+            if (i < k * d) {
+                old[c] = centers[i];
+                if (cl.close_pending) {
+                    cnt[c] = (long long)cl.counts_in[i / d];
+                    sm[c] = (long long)cl.sums_in[i];
+                }
+            }
+        }
+        const double inv_scale = st ? st->inv_scale : 0.0;   // (no state: an assign launch with nothing to close)
+        double acc = 0.0;
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+            const int i = tid + c * 1024;
+            if (i < k * d) {
+                double cv = old[c];
+                if (cnt[c] > 0) {
+                    const double c_new = (double)sm[c] * inv_scale / (double)cnt[c];
+                    const double dlt = c_new - old[c];
+                    acc = fma(dlt, dlt, acc);
+                    cv = c_new;
+                }
+                cen[i] = cv;
+                if (closer && cl.centers_out != centers) cl.centers_out[i] = cv;
+            }
+        }
+        for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+        if (lane == 0) red[wave] = acc;
+        __syncthreads();
+        if (cl.close_pending) {
+            double t = 0.0;
+            for (int i = 0; i < 16; ++i) t += red[i];
+            // an assign launch behind a fit that had converged before: the close above gave the centres it was handed
+            // (same sums, same arithmetic) and the fit state stays.  Only the closing workgroup looks at `done` here:
+            // it is the one that writes it
+            FitState* stw = const_cast<FitState*>(st);
+            if (closer && tid == 0 && (ACCUM || stw->done == 0.0)) {
+                stw->shift2 = t;
+                stw->n_iter += 1.0;
+                if (t <= stw->tol2) stw->done = 1.0;
+            }
+            if constexpr (ACCUM) {
+                if (closer) close_housekeeping();
+                if (t <= st->tol2) return;   // converged: no units, no flush -- what the next launch of the ticket chain does
+            }
+        } else if constexpr (ACCUM) {
+            if (closer) close_housekeeping();
+        }
+    } else {
+        __syncthreads();
+    }
     constexpr int kUnit = 16 * NF;   // 64 frames
     const int64_t n_units = (n + kUnit - 1) / kUnit;
     const int64_t units_per_block = (n_units + gridDim.x - 1) / gridDim.x;
@@ -560,7 +686,7 @@ __global__ __launch_bounds__(64 * filter_waves(DP, ACCUM, sizeof(T) == 8 && !WHI
     // their registers alive across the barrier: scratch memory.)
     {
         double cm = 0.0;
-        for (int i = tid; i < k * d; i += kMT) cm = fmax(cm, fabs(centers[i]));
+        for (int i = tid; i < k * d; i += kMT) cm = fmax(cm, fabs(crows[i]));
         cm = wave_max_f64(cm);
         if (lane == 0 && cm > 0.0) atomicMax(&cmax_bits, (unsigned long long)__double_as_longlong(cm));
     }
@@ -571,8 +697,8 @@ __global__ __launch_bounds__(64 * filter_waves(DP, ACCUM, sizeof(T) == 8 && !WHI
     for (int t = wave; t < n_tiles; t += 2 * kFilterWaves) {
         const int t2 = t + kFilterWaves;
         double c0[kStageRegs], c1[kStageRegs], r0[DP], r1[DP];
-        filter_stage_fetch<DP>(t, lane, centers, k, d, c0, r0);
-        if (t2 < n_tiles) filter_stage_fetch<DP>(t2, lane, centers, k, d, c1, r1);
+        filter_stage_fetch<DP>(t, lane, crows, k, d, c0, r0);
+        if (t2 < n_tiles) filter_stage_fetch<DP>(t2, lane, crows, k, d, c1, r1);
         filter_stage_build<DP>(t, lane, reinterpret_cast<unsigned short*>(img + (size_t)t * 64), c0, r0, k, d, ec, exc, tab, cz,
                                hs, &any_bad);
         if (t2 < n_tiles)
@@ -638,7 +764,7 @@ __global__ __launch_bounds__(64 * filter_waves(DP, ACCUM, sizeof(T) == 8 && !WHI
         }
     };
     // ---- the plain form of step 4: the pinned fp64 scores of ALL centres, lane l takes centres l, l + 64, ..., rows from
-    // the global table (40 KB, L2-resident), one round trip per 64 centres: only for frames (or centre tables) outside
+    // the global table (40 KB, L2-resident; CLOSE: from cen[] in the LDS), one round trip per 64 centres: only for frames (or centre tables) outside
     // the range the fp32 scores are certified for, and for bands too crowded for the bookkeeping of the fp32 scan
     auto scan_frame = [&](int64_t t) {
         double zz[DP];
@@ -646,7 +772,7 @@ __global__ __launch_bounds__(64 * filter_waves(DP, ACCUM, sizeof(T) == 8 && !WHI
         double sbest = -__builtin_inf();
         int sbi = kNone;
         for (int c = lane; c < k; c += 64) {
-            const double sc = score64(centers + (size_t)c * d, c, zz);
+            const double sc = score64(crows + (size_t)c * d, c, zz);
             if (sc > sbest) { sbest = sc; sbi = c; }   // ascending c per lane: the first maximum stays
         }
         // wave_argmax_xor (wave.h) written out: as a call, every specialisation of the kernel gets a different branch layout
@@ -850,8 +976,8 @@ __global__ __launch_bounds__(64 * filter_waves(DP, ACCUM, sizeof(T) == 8 && !WHI
                     if (labels) labels[f0] = lab;
                 }
             } else {
-                // the pinned distance, when asked for: the fp64 chain of the one winning centre (row from the global table)
-                if (mindist) write_label(f0, lab, score64(centers + (size_t)lab * d, lab, z), z);
+                // the pinned distance, when asked for: the fp64 chain of the one winning centre (row from the global table; CLOSE: cen[])
+                if (mindist) write_label(f0, lab, score64(crows + (size_t)lab * d, lab, z), z);
                 else labels[f0] = lab;
             }
         }
@@ -913,8 +1039,8 @@ __global__ __launch_bounds__(64 * filter_waves(DP, ACCUM, sizeof(T) == 8 && !WHI
             // few lanes inside the band
             double rowa[DP], rowb[DP];
             {
-                const double* ca = centers + (size_t)(c1 < k ? c1 : 0) * d;
-                const double* cb = centers + (size_t)(c2 < k ? c2 : 0) * d;
+                const double* ca = crows + (size_t)(c1 < k ? c1 : 0) * d;
+                const double* cb = crows + (size_t)(c2 < k ? c2 : 0) * d;
 #pragma unroll
                 for (int f = 0; f < DP; ++f) {
                     rowa[f] = f < d ? ca[f] : 0.0;
@@ -989,6 +1115,7 @@ __global__ __launch_bounds__(64 * filter_waves(DP, ACCUM, sizeof(T) == 8 && !WHI
         // The workgroup that finishes LAST closes the Lloyd iteration (centres <- sums / counts, shift, convergence flag)
         // instead of a one-workgroup launch of its own after this one: every other workgroup has then added its member
         // sums and read the old centres for the last time.
+        if constexpr (!CLOSE)   // (CLOSE: the launch ends with its flush; the next one closes the iteration)
         if (upd_centers) {
             // Ordering without a device-wide fence (__threadfence() = buffer_wbl2: a write-back of the XCD's whole L2 by
             // every workgroup, +45 us per launch, measured): the member sums travel as atomics, which are resolved at
@@ -1019,5 +1146,13 @@ static inline size_t filter_lds_bytes(int k, int d, bool accum) {
     const size_t tile_bytes = filter_dp(d) == 4 ? FilterShape<4>::kTileBytes : FilterShape<10>::kTileBytes;
     const size_t total = (size_t)n_tiles * tile_bytes + (accum ? (size_t)k * (d + 1) * sizeof(unsigned long long) : 0);
     const size_t cap = 160 * 1024 - 64;   // static __shared__ words of the kernel (two ints, one u64)
+    return total <= cap ? total : 0;
+}
+// the same for the deferred chain's flavour: the fp64 centre table on top, and the close's sixteen partial sums
+static inline size_t filter_lds_bytes_close(int k, int d, bool accum) {
+    const size_t base = filter_lds_bytes(k, d, accum);
+    if (!base) return 0;
+    const size_t total = base + (size_t)k * d * sizeof(double);
+    const size_t cap = 160 * 1024 - 256;
     return total <= cap ? total : 0;
 }

@@ -1985,6 +1985,43 @@ class Engine:
         else:
             check(lib.msm_kmeans_lloyd_pass(*args), self.handle)
 
+    def kmeans_lloyd_pass_deferred(self, x: DeviceArray, centers_in: DeviceArray, centers_out: DeviceArray,
+                                   state: DeviceArray, acc_in, acc_out, acc_next, *, image: DeviceArray | None,
+                                   prev_labels: DeviceArray, close_pending: bool, first_pass: bool = False,
+                                   mean: DeviceArray | None = None, std: DeviceArray | None = None) -> bool:
+        """One Lloyd pass of the deferred chain (msm_kmeans_lloyd_pass_deferred): the launch closes its predecessor's
+        iteration in its prologue and ends with its own flush.  acc_* are (sums, counts) pairs: acc_in the complete sums
+        of the previous pass (None on the first), acc_out zero on entry, acc_next cleared for the following launch.
+        False: the flavour does not run at this shape and nothing was launched (take kmeans_lloyd_pass)."""
+        n, d = x.shape
+        k = centers_in.shape[0]
+        applied = C.c_int32(0)
+        check(lib.msm_kmeans_lloyd_pass_deferred(
+            self.handle, x.ptr, _dtype_code(x.dtype), n, d, d, centers_in.ptr, centers_out.ptr, k,
+            mean.ptr if mean is not None else None, std.ptr if std is not None else None,
+            image.ptr if image is not None else None, state.ptr, prev_labels.ptr,
+            acc_in[0].ptr if acc_in is not None else None, acc_in[1].ptr if acc_in is not None else None,
+            acc_out[0].ptr, acc_out[1].ptr, acc_next[0].ptr, acc_next[1].ptr, int(close_pending), int(first_pass),
+            C.byref(applied)), self.handle)
+        return bool(applied.value)
+
+    def kmeans_assign_closing(self, x: DeviceArray, centers_in: DeviceArray, centers_out: DeviceArray,
+                              state: DeviceArray | None, acc_in, *, image: DeviceArray | None, labels: DeviceArray,
+                              close_pending: bool, mindist: DeviceArray | None = None,
+                              mean: DeviceArray | None = None, std: DeviceArray | None = None) -> bool:
+        """The assignment that ends the deferred chain (msm_kmeans_assign_closing): closes the last pass's iteration in
+        its prologue, leaves the final centres in centers_out.  False: not run at this shape, nothing launched."""
+        n, d = x.shape
+        k = centers_in.shape[0]
+        applied = C.c_int32(0)
+        check(lib.msm_kmeans_assign_closing(
+            self.handle, x.ptr, _dtype_code(x.dtype), n, d, d, centers_in.ptr, centers_out.ptr, k,
+            mean.ptr if mean is not None else None, std.ptr if std is not None else None,
+            image.ptr if image is not None else None, state.ptr if state is not None else None,
+            acc_in[0].ptr if acc_in is not None else None, acc_in[1].ptr if acc_in is not None else None,
+            int(close_pending), labels.ptr, mindist.ptr if mindist is not None else None, C.byref(applied)), self.handle)
+        return bool(applied.value)
+
     def kmeans_update(self, sums: DeviceArray, counts: DeviceArray, centers: DeviceArray, state: DeviceArray,
                       clear: bool = True):
         k, d = centers.shape

@@ -405,6 +405,20 @@ class ShardedMSM:
         # separate calls, for A/B timing and tests; so does an engine without those methods (a host stand-in).
         self.folds = (not multi_shard and os.environ.get("MSM_STEP_FOLDS", "1") != "0"
                       and all(hasattr(eng, m) for m in ("moments_tail", "count_transitions_normalised")))
+        # Single shard with folds: the Lloyd passes run as the deferred chain where the kernel has that flavour -- a pass
+        # ends with the flush of its member sums and the NEXT launch closes the iteration in its prologue, so no
+        # workgroup waits for another inside a launch.  Two centre buffers alternate (in / out) and the member sums
+        # rotate through three (in / out / cleared for the next launch).  MSM_KMEANS_DEFERRED_CLOSE=0 (read here, once)
+        # keeps kmeans_lloyd_pass + kmeans_assign; so do several shards, MSM_STEP_FOLDS=0 and shapes the flavour does
+        # not take (found out by the first call, which then launches nothing).
+        self.deferred = (self.folds and self.km_image is not None
+                         and os.environ.get("MSM_KMEANS_DEFERRED_CLOSE", "1") != "0"
+                         and all(hasattr(eng, m) for m in ("kmeans_lloyd_pass_deferred", "kmeans_assign_closing")))
+        if self.deferred:
+            self.centers_alt = eng.empty((k, d), np.float64)
+            extra = [eng.empty((k * d + k,), np.int64) for _ in range(2)]
+            self.km_rot = [(self.km_sums, self.km_counts)] + [
+                (a.view((k * d,), np.int64), a.view((k,), np.int64, offset_elems=k * d)) for a in extra]
         self.accum_events: list = []
         self.stage_events: dict = {}
         self.time_accum = False
@@ -466,9 +480,14 @@ class ShardedMSM:
         # 4. k-means: fixed number of Lloyd iterations over all frames
         acc = self.km_local if self.km_local is not None else b["km_acc"]
         acc_sums, acc_counts = acc.view((k * d,), np.int64), acc.view((k,), np.int64, offset_elems=k * d)
+        # the deferred chain rotates the member sums through three buffers, one step per pass: it starts where the LAST
+        # pass ends in the caller's buffer (km_acc), so that the step leaves the same sums there as the ticket chain
+        deferred = self.deferred and folds and cfg.kmeans_iters > 0
+        rot0 = (1 - cfg.kmeans_iters) % 3 if deferred else 0
+        clear_sums, clear_counts = self.km_rot[rot0] if deferred else (acc_sums, acc_counts)
         eng.kmeans_fit_begin(self.Y, k, seed=cfg.seed, n_total=self.n_total, tol2=0.0, centers=b["centers"],
                              state=b["fit_state"], absmax_ready=cfg.tica_dim > 0,
-                             **({"sums": acc_sums, "counts": acc_counts} if folds else {}))
+                             **({"sums": clear_sums, "counts": clear_counts} if folds else {}))
         if multi:
             # identical start on every rank in ONE collective: the MIN over [centres | scale] where every rank but 0
             # offers 0x7F7F... = 1.4e306 for the centres (finite coordinates pass through bit for bit) and its own
@@ -485,13 +504,29 @@ class ShardedMSM:
         if self.km_image is not None:
             # the frames' scale from max |Y| in slot 2 of the fit state (left there by the projection or fit_begin)
             eng.kmeans_pack(self.Y, image=self.km_image, absmax=b["fit_state"].view((1,), offset_elems=2))
+        cen = (b["centers"], self.centers_alt) if deferred else None
         for it in range(cfg.kmeans_iters):
             # folds: the first pass takes every frame as booked under no centre, whatever the label buffer holds
             first = {"first_pass": True} if folds and it == 0 else {}
             if self.time_accum:
                 e0, e1 = eng.event(), eng.event()
                 e0.record()
-            if not multi:
+            if deferred:
+                # pass 1 has nothing to close (in = out = the caller's centres); pass it + 1 closes pass it
+                rot = self.km_rot
+                ran = eng.kmeans_lloyd_pass_deferred(
+                    self.Y, cen[(it - 1) & 1] if it else cen[0], cen[it & 1] if it else cen[0], b["fit_state"],
+                    rot[(rot0 + it - 1) % 3] if it else None, rot[(rot0 + it) % 3], rot[(rot0 + it + 1) % 3],
+                    image=self.km_image, prev_labels=self.labels, close_pending=it > 0, first_pass=it == 0)
+                if not ran:
+                    if it:
+                        raise RuntimeError("the deferred k-means chain stopped taking a shape it had taken")
+                    deferred = self.deferred = False      # not this shape: the ticket chain, from now on
+                    if rot0:
+                        acc.zero_()                       # (fit_begin cleared the rotation's first buffer instead)
+            if deferred:
+                pass                                      # (the launch above was this pass)
+            elif not multi:
                 # one shard: the accumulate launch closes the iteration itself (its last workgroup)
                 eng.kmeans_lloyd_pass(self.Y, b["centers"], b["fit_state"], acc_sums, acc_counts,
                                       image=self.km_image, prev_labels=self.labels, **first)
@@ -504,7 +539,17 @@ class ShardedMSM:
             if multi:
                 comm.allreduce_sum_from("km_acc", self.km_local)     # out of place: no copy in front of the collective
                 eng.kmeans_update(self.km_sums, self.km_counts, b["centers"], b["fit_state"], clear=False)
-        eng.kmeans_assign(self.Y, b["centers"], labels=self.labels, image=self.km_image)
+        iters = cfg.kmeans_iters
+        if deferred:
+            # the closing assign: the last pass's close, then the labels; the final centres end in the caller's buffer
+            if not eng.kmeans_assign_closing(self.Y, cen[(iters - 1) & 1], cen[iters & 1], b["fit_state"],
+                                             self.km_rot[0], image=self.km_image, labels=self.labels,
+                                             close_pending=True):
+                raise RuntimeError("the deferred k-means chain stopped taking a shape it had taken")
+            if iters & 1:
+                b["centers"].copy_from(self.centers_alt)
+        else:
+            eng.kmeans_assign(self.Y, b["centers"], labels=self.labels, image=self.km_image)
         self._stamp("kmeans")
         # 5. lag-tau counts (a whole lag scan in one pass and ONE collective) + row-normalised transition matrix
         if cfg.lags:
