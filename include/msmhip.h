@@ -1718,6 +1718,88 @@ msm_status msm_metad_grid_scan(msm_ctx* ctx, const double* d_hills, int H, int d
 msm_status msm_metad_append(msm_ctx* ctx, double* d_hills, int capacity, int index, int d, const double* h_record,
                             const double* d_center, const double* d_v, double v_scale);
 
+/* ---- OPES: compressed kernels, the journal of their versions, bias and gradient (csrc/opes.hip) -------
+ * Written from Invernizzi & Parrinello, J. Phys. Chem. Lett. 11, 2731 (2020) (OPES_METAD).  The definition is this
+ * library's own ("OPES"); the tests hold the kernels to tests/_opes_ref.py run in 80-bit floats.  fp64.
+ *
+ * h_par f64 [MSM_OPES_PARAMS]: kT, p = 1 - 1 / gamma, epsilon, cutoff, compression threshold, fixed_sigma (0 / 1),
+ *   period [MSM_METAD_MAX_D] (0: not periodic), sigma0 [MSM_METAD_MAX_D] (read by the on-line deposit only).
+ * A kernel is the record (centre [d], sigma [d], height) of 2 d + 1 doubles.  With dp_i the minimum image of
+ *   s_i - c_i (dp_i -= P_i * rint(dp_i / P_i)), q = sum_i (dp_i / sigma_i)^2 in ascending i and v = exp(-cutoff^2 / 2):
+ *     G(s) = h * (exp(-q / 2) - v) where q < cutoff^2, else 0.
+ *   P(s) = sum_live G(s) / W,   V(s) = kT p log(P(s) / Z + epsilon),
+ *   dV / ds_i = kT p ((sum_live dG / ds_i / W) / Z) / (P / Z + epsilon);
+ *   no deposit yet: V = kT p log(epsilon), formed on the host, and dV = 0.
+ * The ledger on the device, all of `capacity` entries: d_live f64 [capacity, 2 d + 1] (the first K slots live),
+ *   d_slot_version int32 [capacity] (the version a slot holds), d_journal f64 [capacity, 2 d + 1] (version j is what
+ *   deposit j left: the appended or the finally merged kernel), d_death int32 [capacity] (the deposit that removed the
+ *   version, INT32_MAX while it lives: after deposits 0 .. c - 1 the live set is {j < c : death_j >= c}),
+ *   d_per_deposit f64 [capacity, MSM_OPES_PER_DEPOSIT] = W, Z, neff, K after deposit j, and
+ *   d_state f64 [MSM_OPES_STATE] = deposits so far, K, W = sum w, W2 = sum w^2, S = sum_k sum_k' G_k'(c_k), Z,
+ *   status bits, cursor.  A fresh state is 0 everywhere except Z = 1.
+ * msm_opes_deposit: ONE launch of one wave that consumes up to max_steps of the n_records deposits, from the cursor
+ *   in the state on (restart != 0: from record 0); the caller repeats the launch ceil(n_records / max_steps) times
+ *   and nothing waits.  d_records f64 [n_records, 2 d + 2] = centre, sigma, height, logweight.  d_cv == NULL: the
+ *   records are given and w = exp(logweight).  d_cv f64 [n_records, ld]: deposit r is made at the CVs of row r with
+ *   logweight = V(s) / kT of the state so far, w = h = exp(logweight), then W += w, W2 += w^2,
+ *   neff = (1 + W)^2 / (1 + W2), and unless fixed_sigma sigma_i = sigma0_i (neff (d + 2) / 4)^(-1 / (d + 4)) and
+ *   h *= prod_i sigma0_i / sigma_i; the record made is written to d_records.  Then, both forms alike: the live kernel
+ *   k* with the smallest sum_i (dp_i / sigma*_i)^2 (lowest slot on a tie; lanes take slots l, l + 64, .., then a fixed
+ *   arg-min tree) takes the kernel in if that value < threshold^2:  h = h1 + h2,  c = c1 + (h2 / h) dp,
+ *   sigma^2 = (h1 sigma1^2 + h2 sigma2^2) / h + (h1 h2 / h^2) dp^2  (1: k*, 2: the incoming kernel, dp the minimum
+ *   image of c2 - c1), the merged kernel keeps slot k* and is tested against the others again, at most K times; a
+ *   chain merge keeps the lower slot and the last live slot fills the higher.  Otherwise the kernel is appended.
+ *   S loses the pairs of every kernel removed and gains those of the kernel added (each a sum over the live slots in
+ *   the lane order above), Z = S / (W K).  A full ledger (MSM_OPES_FULL), a record with a non-finite centre or
+ *   logweight or a sigma or height that is not positive and finite (MSM_OPES_BAD_RECORD) and a state that does not fit
+ *   the buffers (MSM_OPES_BAD_STATE) set their bit in the state and consume nothing more: a launch that finds the
+ *   status not 0 returns at once, so the ledger stays as the last accepted deposit left it until the caller writes
+ *   0 to the status word.
+ * msm_opes_bias, journal form (d_death != NULL): d_kernels is the journal of T versions; frame f with count c
+ *   (d_count int32 [n], clamped to [0, T]; NULL: T, the final bias) adds the versions j < c <= death_j in ascending j
+ *   with 1 / sigma formed once per tile, and reads W, Z of deposit c - 1.  One frame per lane, MSM_METAD_THREADS
+ *   frames per workgroup trip, tiles of MSM_METAD_TILE versions; a tile whose versions all died before the smallest
+ *   count of the workgroup is skipped unless MSM_OPES_NO_SKIP is set (the bits are the same).  A frame's bits depend
+ *   on its CVs, its count and the journal alone.  A frame with a non-finite CV is NaN in its own outputs.  Where
+ *   d_state is given, T is lowered to the deposits the device has made (a caller that did not wait cannot know of a
+ *   refused deposit): no row is read that was never written.
+ *   Live form (d_death == NULL, d_count == NULL): d_kernels is d_live, T its capacity, and K, W, Z are read from
+ *   d_state on the device; one wave per frame in the order of the deposit's own V(s) (n = 1 is the MD step).
+ * msm_opes_plan: out = frames per workgroup, versions per tile, grid, LDS bytes, threads of the deposit launch,
+ *   grid of the live form.  No scratch memory anywhere. */
+#define MSM_OPES_PARAMS (6 + 2 * MSM_METAD_MAX_D)
+#define MSM_OPES_PAR_KT 0
+#define MSM_OPES_PAR_PREFACTOR 1
+#define MSM_OPES_PAR_EPSILON 2
+#define MSM_OPES_PAR_CUTOFF 3
+#define MSM_OPES_PAR_THRESHOLD 4
+#define MSM_OPES_PAR_FIXED_SIGMA 5
+#define MSM_OPES_PAR_PERIOD 6
+#define MSM_OPES_PAR_SIGMA0 (6 + MSM_METAD_MAX_D)
+#define MSM_OPES_STATE 8
+#define MSM_OPES_STATE_COUNT 0
+#define MSM_OPES_STATE_LIVE 1
+#define MSM_OPES_STATE_W 2
+#define MSM_OPES_STATE_W2 3
+#define MSM_OPES_STATE_SUM 4
+#define MSM_OPES_STATE_Z 5
+#define MSM_OPES_STATE_STATUS 6
+#define MSM_OPES_STATE_CURSOR 7
+#define MSM_OPES_PER_DEPOSIT 4
+#define MSM_OPES_FULL 1
+#define MSM_OPES_BAD_RECORD 2
+#define MSM_OPES_BAD_STATE 4
+#define MSM_OPES_NO_SKIP 1
+msm_status msm_opes_plan(msm_ctx* ctx, int64_t n, int T, int d, int max_workgroups, int64_t out[6]);
+msm_status msm_opes_deposit(msm_ctx* ctx, int d, const double* h_par, double* d_state, double* d_live,
+                            int32_t* d_slot_version, double* d_journal, int32_t* d_death, double* d_per_deposit,
+                            int capacity, double* d_records, int n_records, const double* d_cv, int64_t ld,
+                            int max_steps, int restart);
+msm_status msm_opes_bias(msm_ctx* ctx, const double* d_cv, int64_t n, int64_t ld, int d, const double* h_par,
+                         const double* d_kernels, const int32_t* d_death, const double* d_per_deposit, int T,
+                         const int32_t* d_count, const double* d_state, int flags, int max_workgroups, double* d_bias,
+                         double* d_grad, int64_t ldg);
+
 /* ------------------------------------------------------------------ */
 /* exchange steps of the sharded path (RCCL over xGMI)                  */
 /* ------------------------------------------------------------------ */

@@ -62,6 +62,14 @@ HMM_BAD_SYMBOL, HMM_ZERO_PROB, HMM_EMPTY_STATE, HMM_BAD_TABLE, HMM_NOT_CONVERGED
 # an LDS tile, grid points of a scan tile, the hill kernels
 METAD_MAX_D, METAD_GRID_MAX_D, METAD_THREADS, METAD_TILE, METAD_SCAN_TILE = 8, 3, 256, 128, 256
 METAD_KERNELS = {"gaussian": 0, "stretched-gaussian": 1}
+# OPES (MSM_OPES_* in include/msmhip.h): the parameter vector, the device state, the per-deposit row, status bits, flags
+OPES_PARAMS, OPES_PAR_PERIOD, OPES_PAR_SIGMA0 = 6 + 2 * METAD_MAX_D, 6, 6 + METAD_MAX_D
+OPES_STATE, OPES_PER_DEPOSIT = 8, 4
+(OPES_STATE_COUNT, OPES_STATE_LIVE, OPES_STATE_W, OPES_STATE_W2, OPES_STATE_SUM, OPES_STATE_Z, OPES_STATE_STATUS,
+ OPES_STATE_CURSOR) = range(8)
+OPES_FULL, OPES_BAD_RECORD, OPES_BAD_STATE = 1, 2, 4
+OPES_NO_SKIP = 1
+OPES_ALIVE = 2**31 - 1      # death of a version that lives
 
 
 class MsmError(RuntimeError):
@@ -288,6 +296,10 @@ _PROTOTYPES: dict[str, tuple] = {
     "msm_metad_grid_scan": (_i32, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _f64, _vp, _i32, _f64, _f64, _i32,
                                    _vp, _vp]),
     "msm_metad_append": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _f64]),
+    "msm_opes_plan": (_i32, [_vp, _i64, _i32, _i32, _i32, _vp]),
+    "msm_opes_deposit": (_i32, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _i64, _i32, _i32]),
+    "msm_opes_bias": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp,
+                             _i64]),
 }
 
 DECLARED_SYMBOLS = tuple(_PROTOTYPES)

@@ -1365,6 +1365,139 @@ class Engine:
                                    center.ptr if center is not None else None, v.ptr if v is not None else None,
                                    float(v_scale)), self.handle)
 
+    # -- OPES (csrc/opes.hip) ------------------------------------------------------------------
+    @staticmethod
+    def opes_params(d: int, kT: float, prefactor: float, epsilon: float, cutoff: float, threshold: float = 1.0,
+                    fixed_sigma: bool = False, periods=None, sigma0=None) -> np.ndarray:
+        """The parameter vector h_par f64 [MSM_OPES_PARAMS] of msm_opes_deposit / msm_opes_bias."""
+        d = int(d)
+        if not 1 <= d <= _lib.METAD_MAX_D:
+            raise ValueError(f"{d} collective variables, 1 to {_lib.METAD_MAX_D} are supported")
+        par = np.zeros(_lib.OPES_PARAMS)
+        par[:6] = float(kT), float(prefactor), float(epsilon), float(cutoff), float(threshold), float(bool(fixed_sigma))
+        for name, at, given in (("periods", _lib.OPES_PAR_PERIOD, periods), ("sigma0", _lib.OPES_PAR_SIGMA0, sigma0)):
+            if given is not None:
+                a = np.ascontiguousarray(given, np.float64).reshape(-1)
+                if a.size != d or not np.isfinite(a).all():
+                    raise ValueError(f"{name} must be {d} finite numbers")
+                par[at:at + d] = a
+        return par
+
+    def opes_plan(self, n: int, n_versions: int, d: int, max_workgroups: int = 0) -> dict:
+        """What opes_bias and opes_deposit would launch (msm_opes_plan, include/msmhip.h).  Launches nothing."""
+        out = (C.c_int64 * 6)()
+        check(lib.msm_opes_plan(self.handle, int(n), int(n_versions), int(d), int(max_workgroups), out), self.handle)
+        return {"frames_per_workgroup": int(out[0]), "versions_per_tile": int(out[1]), "grid": int(out[2]),
+                "lds_bytes": int(out[3]), "deposit_threads": int(out[4]), "live_grid": int(out[5])}
+
+    def opes_state(self, capacity: int, d: int) -> dict:
+        """A fresh OPES ledger of `capacity` deposits on the device: the buffers msm_opes_deposit writes (state, live,
+        slot_version, journal, death, per_deposit), with "capacity" and "d".  Z = 1, everything else 0."""
+        cap, d = int(capacity), int(d)
+        if cap < 1 or not 1 <= d <= _lib.METAD_MAX_D:
+            raise ValueError(f"opes_state needs capacity >= 1 and 1 <= d <= {_lib.METAD_MAX_D}")
+        state = np.zeros(_lib.OPES_STATE)
+        state[_lib.OPES_STATE_Z] = 1.0
+        R = 2 * d + 1
+        return {"capacity": cap, "d": d, "state": self.to_device(state), "live": self.zeros((cap, R), np.float64),
+                "slot_version": self.zeros((cap,), np.int32), "journal": self.zeros((cap, R), np.float64),
+                "death": self.zeros((cap,), np.int32),
+                "per_deposit": self.zeros((cap, _lib.OPES_PER_DEPOSIT), np.float64)}
+
+    def opes_read_state(self, ledger: dict) -> dict:
+        """The scalar state of a ledger, read back (waits for the stream): count, live, W, W2, S, Z, status, cursor."""
+        s = ledger["state"].to_host()
+        return {"count": int(s[_lib.OPES_STATE_COUNT]), "live": int(s[_lib.OPES_STATE_LIVE]),
+                "W": float(s[_lib.OPES_STATE_W]), "W2": float(s[_lib.OPES_STATE_W2]),
+                "S": float(s[_lib.OPES_STATE_SUM]), "Z": float(s[_lib.OPES_STATE_Z]),
+                "status": int(s[_lib.OPES_STATE_STATUS]), "cursor": int(s[_lib.OPES_STATE_CURSOR])}
+
+    def opes_clear_status(self, ledger: dict) -> dict:
+        """Writes 0 to the status word of a ledger that refused a deposit, so that it accepts deposits again; the
+        ledger is as its last accepted deposit left it.  Returns the state read (waits for the stream)."""
+        s = ledger["state"].to_host()
+        s[_lib.OPES_STATE_STATUS] = 0.0
+        ledger["state"].copy_from_host(s)
+        return self.opes_read_state(ledger)
+
+    def opes_deposit(self, ledger: dict, params: np.ndarray, records: DeviceArray, n_records: int | None = None, *,
+                     cv: DeviceArray | None = None, max_steps: int = 0) -> int:
+        """Consumes the deposits records f64 [n_records, 2 d + 2] = centre, sigma, height, logweight
+        (msm_opes_deposit) in ceil(n_records / max_steps) bounded launches (max_steps = 0: one launch); returns the
+        number of launches.  With cv f64 [n_records, ld >= d] the deposits are made on line at those CVs and
+        `records` receives what was deposited.  Nothing is uploaded or waited for; a full ledger or an unusable
+        record shows in the status of opes_read_state, and while the status is not 0 every launch returns at once
+        (opes_clear_status)."""
+        d, cap = ledger["d"], ledger["capacity"]
+        if records.dtype != np.float64 or len(records.shape) != 2 or records.shape[1] != 2 * d + 2:
+            raise ValueError(f"records must be float64 with shape (n, {2 * d + 2}), got {records.shape} "
+                             f"{records.dtype}")
+        n = records.shape[0] if n_records is None else int(n_records)
+        if not 0 <= n <= records.shape[0]:
+            raise ValueError(f"n_records = {n} outside [0, {records.shape[0]}]")
+        ld = 0
+        if cv is not None:
+            if cv.dtype != np.float64 or len(cv.shape) != 2 or cv.shape[1] < d or cv.shape[0] < n:
+                raise ValueError(f"cv must be float64 with shape (>= {n}, >= {d}), got {cv.shape} {cv.dtype}")
+            ld = cv.shape[1]
+        par = np.ascontiguousarray(params, np.float64).reshape(-1)
+        if par.size != _lib.OPES_PARAMS:
+            raise ValueError(f"params must have {_lib.OPES_PARAMS} entries (Engine.opes_params)")
+        steps = int(max_steps) if int(max_steps) > 0 else max(n, 1)
+        if int(max_steps) < 0:
+            raise ValueError("max_steps must be >= 0 (0: one launch)")
+        launches = -(-n // steps)
+        for i in range(launches):
+            check(lib.msm_opes_deposit(self.handle, d, par.ctypes.data, ledger["state"].ptr, ledger["live"].ptr,
+                                       ledger["slot_version"].ptr, ledger["journal"].ptr, ledger["death"].ptr,
+                                       ledger["per_deposit"].ptr, cap, records.ptr, n,
+                                       cv.ptr if cv is not None else None, ld, steps, 1 if i == 0 else 0), self.handle)
+        return launches
+
+    def opes_bias(self, cv: DeviceArray, ledger: dict, params: np.ndarray, n_versions: int | None = None, *,
+                  counts: DeviceArray | None = None, live: bool = False, grad: bool = False, skip: bool = True,
+                  max_workgroups: int = 0, bias: DeviceArray | None = None, grad_out: DeviceArray | None = None):
+        """V at the frames cv f64 [n, ld >= d] (msm_opes_bias): `bias` f64 [n] and, with grad, dV/ds f64 [n, d], device
+        arrays.  Journal form: frame f sees the state after its first counts[f] deposits of the `n_versions` in the
+        journal (int32 [n]; None: all of them, the final bias).  live=True: one wave per frame against the live
+        kernels with the state read on the device, the MD step.  With preallocated `bias` / `grad_out` nothing is
+        allocated, uploaded or waited for."""
+        d = ledger["d"]
+        if cv.dtype != np.float64 or len(cv.shape) != 2 or cv.shape[1] < d or cv.shape[0] < 1:
+            raise ValueError(f"cv must be float64 with shape (n >= 1, >= {d}), got {cv.shape} {cv.dtype}")
+        n, ld = cv.shape
+        par = np.ascontiguousarray(params, np.float64).reshape(-1)
+        if par.size != _lib.OPES_PARAMS:
+            raise ValueError(f"params must have {_lib.OPES_PARAMS} entries (Engine.opes_params)")
+        if live:
+            if counts is not None or n_versions is not None:
+                raise ValueError("the live form takes neither counts nor n_versions")
+            T = ledger["capacity"]
+        else:
+            if n_versions is None:
+                raise ValueError("the journal form needs n_versions, the number of deposits made")
+            T = int(n_versions)
+            if not 0 <= T <= ledger["capacity"]:
+                raise ValueError(f"n_versions = {T} outside [0, {ledger['capacity']}]")
+        if counts is not None and (counts.dtype != np.int32 or counts.size != n):
+            raise ValueError(f"counts must be int32 of {n} entries")
+        bias = bias if bias is not None else self.empty((n,), np.float64)
+        if grad and grad_out is None:
+            grad_out = self.empty((n, d), np.float64)
+        if bias.dtype != np.float64 or bias.size != n:
+            raise ValueError(f"bias must be float64 of {n} entries")
+        if grad_out is not None and (grad_out.dtype != np.float64 or len(grad_out.shape) != 2
+                                     or grad_out.shape[0] != n or grad_out.shape[1] < d):
+            raise ValueError(f"grad_out must be float64 with shape ({n}, >= {d})")
+        check(lib.msm_opes_bias(self.handle, cv.ptr, n, ld, d, par.ctypes.data,
+                                (ledger["live"] if live else ledger["journal"]).ptr,
+                                None if live else ledger["death"].ptr, ledger["per_deposit"].ptr, T,
+                                counts.ptr if counts is not None else None, ledger["state"].ptr,
+                                0 if skip else _lib.OPES_NO_SKIP, int(max_workgroups), bias.ptr,
+                                grad_out.ptr if grad_out is not None else None,
+                                grad_out.shape[1] if grad_out is not None else 0), self.handle)
+        return (bias, grad_out) if grad_out is not None else bias
+
     def state_counts(self, labels: DeviceArray, k: int, out: DeviceArray | None = None) -> DeviceArray:
         out = out if out is not None else self.empty((k,), np.int64)
         check(lib.msm_state_counts(self.handle, labels.ptr, labels.size, int(k), out.ptr), self.handle)
