@@ -310,7 +310,7 @@ constexpr int kMTNarrow = 1024, kMTWide = 512;
 
 // Diagnostic build only (tools/probe/kmeans_stamp_probe.hip): per-phase cycle stamps of wave 0.
 #ifdef MSM_KM_STAMPS
-__device__ unsigned long long g_km_stamps[8];
+__device__ unsigned long long g_km_stamps[16];   // 0-7: phases of a unit; 8-12: the filter launch's prologue
 #define KSTAMP(i)                                                                          \
     do {                                                                                   \
         unsigned long long t__;                                                            \
@@ -319,8 +319,8 @@ __device__ unsigned long long g_km_stamps[8];
         klast__ = t__;                                                                     \
     } while (0)
 #define KSTAMP_VM(i) do { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); KSTAMP(i); } while (0)
-#define KSTAMP_INIT unsigned long long kacc__[8] = {0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long klast__; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(klast__)::"memory");
-#define KSTAMP_FLUSH if (threadIdx.x == 0) { for (int i__ = 0; i__ < 8; ++i__) atomicAdd(&g_km_stamps[i__], kacc__[i__]); }
+#define KSTAMP_INIT unsigned long long kacc__[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long klast__; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(klast__)::"memory");
+#define KSTAMP_FLUSH if (threadIdx.x == 0) { for (int i__ = 0; i__ < 16; ++i__) atomicAdd(&g_km_stamps[i__], kacc__[i__]); }
 #else
 #define KSTAMP(i)
 #define KSTAMP_VM(i)

@@ -52,6 +52,16 @@
 // room for the accumulation error of the slot itself.  Both slots are at least 2^-14.  Frames or centres with
 // |v| > 1e18, |v'| > 2^14, inf or NaN fail the guard: the frame (for a centre: every frame) takes step 4; so does
 // every frame when a centre's |C| would exceed 2^100.
+// Row sums.  The kappa slot of a centre holds any fp16 number >= kappa |c'_j| + 2 tiny_j, tiny_j the sum of what the
+// split left out of the row: step 1 asks for nothing more, so neither sum needs a fixed order.  The four lanes
+// (j, j + 16, j + 32, j + 48) of a row add |c'_jf|^2 and the left-out parts over features q, q + 4, q + 8 each and
+// combine them with the row swaps (filter_stage_build).  Every term is non-negative, so an fp64 sum of the ten in ANY
+// order is within 10 x 2^-53 relative of the exact sum; the square root, the product with kappa and the final sum add
+// a few 2^-53 more; the factor 1 + 2^-20 (kUp20d) in front of the round-up to fp16 covers all of it a hundred million
+// times over.  The order may therefore move the last bit of the slot (up or down one fp16 step on a row that sits within
+// 2^-20 of a step; the labels cannot change, only which frames near a tie take step 4).  What carries the bits of a
+// label or a distance keeps its order: h_j (the serial chain over ascending features, in lane j), C, the fp32 table,
+// the operand images.
 //
 // Schedule.  One workgroup of kFilterWaves waves per CU builds the centre tables in its LDS and then takes units of
 // 64 frames: tile loop (matrix pipe + top-two bookkeeping), the loads of the next unit's images and of this unit's
@@ -59,8 +69,8 @@
 // passes keep a frame's fp64 coordinates only until their fp32 copy for the pick is made: a certified frame that moves
 // its member sums (every frame in the first pass, under 10 % after two) reads its row again, L2-warm, all loads ahead
 // of the first atomic; step 4 reads the row of its frame wave-uniformly, next to the fp64 rows of the two best centres.
-// That, and fetching the first unit's images after the tables are built instead of across their staging, takes the fp64
-// no-whitening build from 132 VGPRs to 122: 16 waves without scratch memory (filter_waves).  (Step 4 as a scan of all
+// That takes the fp64 no-whitening build from 132 VGPRs to 122: 16 waves without scratch memory (filter_waves); the first
+// unit's images travel across the staging of the tables, which holds 24 registers (filter_stage_fetch).  (Step 4 as a scan of all
 // centres in fp64, rows from global memory, cost 25-30 us per pass for 0.2 % of the frames, in place or queued for the
 // end of the workgroup's units alike: ~10 us of a wave per frame, and the slowest workgroup has 20 of them.  Scoring
 // the eight candidates in fp64 before step 4, one lane and one row at a time, halves the frames that reach step 4 and
@@ -69,6 +79,7 @@
 // iteration) was balanced between the two; with one instruction per tile the VALU port bounds it.  Tried and dropped: scoring the candidates of unit i - 1 inside the tile
 // loop of unit i (same time: the port is the limit either way, and the state costs 12 of 16 waves).
 #pragma once
+#include "f16_split.h"
 
 typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
 typedef _Float16 v8h __attribute__((ext_vector_type(8)));
@@ -90,7 +101,6 @@ constexpr int kFilterCloseCH = 5;                                // prologue clo
 constexpr int kFilterRowQ = 3;                                   // uint4 per frame image (48 bytes)
 constexpr double kFilterHi = 1e18;                               // unscaled range guard (the fp32 pick)
 constexpr double kFilterScaledHi = 16384.0;                      // 2^14: scaled range guard (fp16 operands)
-constexpr double kF16MinNormal = 6.103515625e-05;                // 2^-14
 constexpr int kFilterScaleTop = 13;                              // a scale puts the largest |v| into [2^12, 2^13)
 constexpr double kFilterKappa = 52.0 * 5.9604644775390625e-08;   // 52 x 2^-24
 constexpr float kPickEps = 20.0f * 5.9604644775390625e-08f;      // 20 x 2^-24
@@ -107,42 +117,8 @@ __host__ __device__ inline int filter_scale_exp(double amax) {
     return e < -60 ? -60 : (e > 60 ? 60 : e);
 }
 
-// fp16 numbers of the normal range [2^-14, 65504] from fp64, without a detour through fp32 (two roundings):
-// v = m 2^q, m in [0.5, 1), keeps 11 significant bits, the last at 2^(q - 11)
-__device__ __forceinline__ double f16_round(double v) {
-    const int q = ilogb(v) + 1;
-    return ldexp(rint(ldexp(v, 11 - q)), q - 11);
-}
-__device__ __forceinline__ double f16_ceil(double v) {   // smallest fp16 >= v, v >= 2^-14
-    const int q = ilogb(v) + 1;
-    return ldexp(ceil(ldexp(v, 11 - q)), q - 11);
-}
-__device__ __forceinline__ unsigned short f16_bits(double v) {   // v is an fp16 number: exact
-    return __builtin_bit_cast(unsigned short, (_Float16)(float)v);
-}
-// two-term fp16 split of a scaled coordinate |v| <= 2^14: v = hi + lo + r with |r| <= 2^-22 |v|.  A part that would
-// be subnormal is left out (zero) and what it leaves behind is added to `tiny` (the bound pays for it, header "Range")
-__device__ __forceinline__ void f16_split2(double v, unsigned short& hi, unsigned short& lo, double& tiny) {
-    hi = lo = 0;
-    if (!(fabs(v) >= kF16MinNormal)) {
-        tiny += fabs(v);
-        return;
-    }
-    const double h = f16_round(v);
-    const double r = v - h;   // exact
-    hi = f16_bits(h);
-    if (!(fabs(r) >= kF16MinNormal)) {
-        tiny += fabs(r);
-        return;
-    }
-    lo = f16_bits(f16_round(r));
-}
-// smallest fp32 >= v, |v| < 2^127
-__device__ __forceinline__ float f32_up(double v) {
-    float f = (float)v;
-    if ((double)f < v) f = __uint_as_float(__float_as_uint(f) + (f >= 0.0f ? 1u : ~0u));
-    return f;
-}
+// f16_round, f16_ceil, f16_bits, f16_split2 (the two-term fp16 split of a scaled coordinate, with what it leaves out
+// added to `tiny`), f32_up and kF16MinNormal: f16_split.h, integer arithmetic on the bit pattern of the double
 
 // K slot of product term t (0 = ch xh, 1 = ch xl, 2 = cl xh), feature f.  Quarter q of the instruction (slots
 // 8 q .. 8 q + 7) reads piece filter_piece(q) of the 48-byte frame image
@@ -276,31 +252,56 @@ __host__ __device__ constexpr int filter_dp(int d) { return d <= 4 ? 4 : 10; }
 // them in flight before it builds the first (the build is ~300 instructions; one load round trip under load is as long):
 //   filter_stage_fetch: the tile's 16 x d coordinates, one coalesced load per 64 elements (element e = row e / d,
 //                       feature e % d), at most kStageRegs per lane;
-//   filter_stage_build: fp16 pairs into the A operands, fp32 coordinates into the table rows; the 16 row lanes then
-//                       fetch their row once more for h_j, C, the range guard and the kappa slot (the fp64 chain over
-//                       ascending features: the bits of every other h_j in the library).
+//                       and features q, q + 4, q + 8 of row lane & 15 (q = lane >> 4): the row side, kStageRowQ per lane;
+//   filter_stage_build: fp16 pairs into the A operands, fp32 coordinates into the table rows; then the row side.  Its
+//                       bound part (range guard, |c'_j|^2, what the split leaves out) is summed by the four lanes of a
+//                       row, each over its own features, and combined with the row swaps of wave.h; lane j of the first
+//                       sixteen collects the row's coordinates from the other three by the same swaps and runs the
+//                       fp64 chain over ascending features for h_j (the bits of every other h_j in the library), C,
+//                       the kappa slot and the table's last two columns.
 constexpr int kStageRegs = (16 * kFilterMaxD + 63) / 64;
-// i / d for 0 <= i < 256, 1 <= d <= 10 without the integer-division sequence: (i + 0.5) / d is at least 0.05 away from
-// every integer, far outside fp32 rounding
+// i / d for 0 <= i < 8192 (a tile's 160 elements; the close's kFilterCloseCH x 1024), 1 <= d <= 10 without the
+// integer-division sequence: (i + 0.5) / d is at least 0.05 away from every integer, fp32 rounding moves it by less
+// than 0.002
 __device__ __forceinline__ int stage_row(int i, int d) { return (int)(((float)i + 0.5f) * (1.0f / (float)d)); }
+// x of lane (j, qs) = j + 16 qs in lane j < 16 (the other lanes get some lane's x): v_permlane32_swap brings rows 2, 3
+// to rows 0, 1, v_permlane16_swap row 1 to row 0 (row_swap, wave.h)
+__device__ __forceinline__ double xrow_to_first(double x, int qs) {
+    const unsigned long long b = __builtin_bit_cast(unsigned long long, x);
+    unsigned lo = (unsigned)b, hi = (unsigned)(b >> 32);
+    if (qs & 2) {
+        lo = row_swap<1>(lo)[1];
+        hi = row_swap<1>(hi)[1];
+    }
+    if (qs & 1) {
+        lo = row_swap<0>(lo)[1];
+        hi = row_swap<0>(hi)[1];
+    }
+    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+template <int DP>
+constexpr int kStageRowQ = (DP + 3) / 4;   // features of a row per lane when its four lanes (j, j + 16, j + 32, j + 48) share them
 template <int DP>
 __device__ __forceinline__ void filter_stage_fetch(int tile, int lane, const double* __restrict__ centers, int k, int d,
-                                                   double (&c)[kStageRegs], double (&rc)[DP]) {
+                                                   double (&c)[kStageRegs], double (&rq)[kStageRowQ<DP>]) {
 #pragma unroll
     for (int u = 0; u < kStageRegs; ++u) {
         const int i = lane + 64 * u;
         const int r = stage_row(i, d), j = tile * 16 + r;
         c[u] = (i < 16 * d && j < k) ? centers[(size_t)tile * 16 * d + i] : 0.0;
     }
-    // the 16 row lanes: their own row once more, feature by feature (zeros beyond d leave every chain unchanged)
-    const int jr = tile * 16 + lane;
+    // the row side: features q, q + 4, q + 8 of row lane & 15 (zeros beyond d and k leave every chain and sum unchanged)
+    const int jq = tile * 16 + (lane & 15);
 #pragma unroll
-    for (int f = 0; f < DP; ++f) rc[f] = (lane < 16 && jr < k && f < d) ? centers[(size_t)jr * d + f] : 0.0;
+    for (int m = 0; m < kStageRowQ<DP>; ++m) {
+        const int f = (lane >> 4) + 4 * m;
+        rq[m] = (jq < k && f < d) ? centers[(size_t)jq * d + f] : 0.0;
+    }
 }
 // ec: the centres' scale exponent; exc = e_x + e_c (the scale of the C operand)
 template <int DP>
 __device__ __forceinline__ void filter_stage_build(int tile, int lane, unsigned short* simg, const double (&c)[kStageRegs],
-                                                   const double (&rc)[DP], int k, int d, int ec, int exc,
+                                                   const double (&rq)[kStageRowQ<DP>], int k, int d, int ec, int exc,
                                                    float* __restrict__ tab, float* __restrict__ cz, double* __restrict__ hs,
                                                    int* __restrict__ any_bad) {
     using S = FilterShape<DP>;
@@ -326,29 +327,39 @@ __device__ __forceinline__ void filter_stage_build(int tile, int lane, unsigned 
         }
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    // the bound side of row lane & 15, dealt over its four lanes by feature: the range guard, |c'_j|^2 and what
+    // f16_split2 leaves out of the row (header, "Row sums"); zeros beyond d and in padding rows add nothing
+    double aw = 0.0, tiny = 0.0;
+    int ok_q = 1;
+#pragma unroll
+    for (int m = 0; m < kStageRowQ<DP>; ++m) {
+        const double cf = rq[m];
+        const double w = ldexp(cf, ec);
+        if (!(fabs(cf) <= kFilterHi && fabs(w) <= kFilterScaledHi)) ok_q = 0;   // NaN fails
+        aw = fma(w, w, aw);
+        const bool whole = !(fabs(w) >= kF16MinNormal);
+        const double r = whole ? fabs(w) : fabs(w - f16_round(w));
+        if (whole || !(r >= kF16MinNormal)) tiny += r;
+    }
+    aw = xrow_reduce(aw, op_sum{});
+    tiny = xrow_reduce(tiny, op_sum{});
+    const bool ok_row = xrow_min_i32(ok_q) != 0;   // (a row that fails has garbage in aw and tiny: neither is used)
+    // |c_j|^2 in lane j < 16: the serial chain over ascending features, feature f from lane (j, f & 3)
+    double a = 0.0;
+#pragma unroll
+    for (int f = 0; f < DP; ++f) {
+        const double cf = xrow_to_first(rq[f >> 2], f & 3);
+        a = fma(cf, cf, a);
+    }
     int bad_row = 0;
     if (lane < 16) {
         const int j = tile * 16 + lane;
         float* row = tab + (size_t)j * S::RF;
         double h = __builtin_inf();
         if (j < k) {
-            double a = 0.0, aw = 0.0, tiny = 0.0;
-            bool ok = true;
-#pragma unroll
-            for (int f = 0; f < DP; ++f) {
-                const double cf = rc[f];   // zero beyond d
-                a = fma(cf, cf, a);
-                const double w = ldexp(cf, ec);
-                ok = ok && fabs(cf) <= kFilterHi && fabs(w) <= kFilterScaledHi;   // false for NaN
-                if (ok) {   // what f16_split2 leaves out of this coordinate
-                    aw = fma(w, w, aw);
-                    const double r = fabs(w) >= kF16MinNormal ? fabs(w - f16_round(w)) : fabs(w);
-                    if (!(r >= kF16MinNormal) || !(fabs(w) >= kF16MinNormal)) tiny += r;
-                }
-            }
             h = 0.5 * a;
             const double cval = ldexp(-(h - kFilterKappa * h), exc);
-            ok = ok && fabs(cval) <= 0x1p100;
+            const bool ok = ok_row && fabs(cval) <= 0x1p100;
             if (!ok) bad_row = 1;
             cz[j] = ok ? f32_up(cval) : 0.0f;
             if (ok)
@@ -574,6 +585,10 @@ __global__ __launch_bounds__(64 * filter_waves(DP, ACCUM, sizeof(T) == 8 && !WHI
     __shared__ int unit_ctr;
     __shared__ int any_bad;
     __shared__ unsigned long long cmax_bits;
+    // CLOSE: the high word of max |c| per wave, from the close (the scale needs the exponent alone; 1 stands for a
+    // subnormal maximum, which has the scale of any other number below 2^-47).  Words, not doubles: the static LDS of
+    // the kernel stays inside the 256 bytes filter_lds_bytes_close leaves for it
+    __shared__ int wave_cmax_hi[CLOSE ? 16 : 1];
     // (the wave number through readfirstlane: the compiler then knows that unit numbers are uniform and addresses the
     // image and coordinate loads as scalar base + lane offset + immediate, not with a 64-bit register pair per load)
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -595,6 +610,7 @@ __global__ __launch_bounds__(64 * filter_waves(DP, ACCUM, sizeof(T) == 8 && !WHI
         // arithmetic: one round trip (kFilterCloseCH x 1024 elements; the host sends larger tables elsewhere)
         __shared__ double red[16];
         constexpr int CH = kFilterCloseCH;
+        static_assert(CH * 1024 <= 8192, "stage_row");
         long long cnt[CH], sm[CH];
         double old[CH];
 #pragma unroll
@@ -606,13 +622,13 @@ __global__ __launch_bounds__(64 * filter_waves(DP, ACCUM, sizeof(T) == 8 && !WHI
             if (i < k * d) {
                 old[c] = centers[i];
                 if (cl.close_pending) {
-                    cnt[c] = (long long)cl.counts_in[i / d];
+                    cnt[c] = (long long)cl.counts_in[stage_row(i, d)];
                     sm[c] = (long long)cl.sums_in[i];
                 }
             }
         }
         const double inv_scale = st ? st->inv_scale : 0.0;   // (no state: an assign launch with nothing to close)
-        double acc = 0.0;
+        double acc = 0.0, cm = 0.0;   // cm: max |c| of the closed table, for the centres' scale below
 #pragma unroll
         for (int c = 0; c < CH; ++c) {
             const int i = tid + c * 1024;
@@ -625,11 +641,17 @@ __global__ __launch_bounds__(64 * filter_waves(DP, ACCUM, sizeof(T) == 8 && !WHI
                     cv = c_new;
                 }
                 cen[i] = cv;
+                cm = fmax(cm, fabs(cv));
                 if (closer && cl.centers_out != centers) cl.centers_out[i] = cv;
             }
         }
         for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-        if (lane == 0) red[wave] = acc;
+        cm = wave_max_f64(cm);
+        if (lane == 0) {
+            red[wave] = acc;
+            const int hw = (int)(__double_as_longlong(cm) >> 32);
+            wave_cmax_hi[wave] = hw == 0 && cm > 0.0 ? 1 : hw;
+        }
         __syncthreads();
         if (cl.close_pending) {
             double t = 0.0;
@@ -653,6 +675,7 @@ __global__ __launch_bounds__(64 * filter_waves(DP, ACCUM, sizeof(T) == 8 && !WHI
     } else {
         __syncthreads();
     }
+    KSTAMP_VM(8);   // stamps 8-12: the prologue (diagnostic builds only; they drain the loads each phase waits for)
     constexpr int kUnit = 16 * NF;   // 64 frames
     const int64_t n_units = (n + kUnit - 1) / kUnit;
     const int64_t units_per_block = (n_units + gridDim.x - 1) / gridDim.x;
@@ -672,38 +695,45 @@ __global__ __launch_bounds__(64 * filter_waves(DP, ACCUM, sizeof(T) == 8 && !WHI
 #pragma unroll
         for (int u = 0; u < NF; ++u) b[u] = __builtin_bit_cast(v8h, ub[voff + u * 16 * RQ]);
     };
-    // the first unit's images travel while the tables are built; kReloadZ: after that, their 16 registers across the
-    // staging of two tiles were what put the 16-wave build into scratch memory
-    if constexpr (!kReloadZ) {
-        if (unit < u_end) load_images(unit);
-    }
+    // the first unit's images travel while the tables are built (the staging of two tiles holds 24 registers since the
+    // row side takes its coordinates from the lanes of the row: the images' 16 fit beside them at 16 waves)
+    if (unit < u_end) load_images(unit);
 
     // ---- centre tables, built by every workgroup for itself: wave w stages tiles w, w + W, ... straight into the
     // LDS (a separate staging launch + 113 KB of copies per workgroup did the same for 4.7 us more per pass);
     // padding tiles too (their rows carry the -3e38 sentinel); two tiles per trip, both fetched before either is built.
     // The centres' scale 2^e_c comes first: max |c| over the table (non-negative doubles order like their bits; NaN
     // loses, an infinite coordinate fails the range guard anyway).  (Taking it from the fetched tiles instead kept
-    // their registers alive across the barrier: scratch memory.)
-    {
+    // their registers alive across the barrier: scratch memory.)  CLOSE: the close had every coordinate in a register and
+    // left the sixteen wave maxima behind its barrier: no second pass over the table, no barrier of its own.
+    double cmax;
+    if constexpr (CLOSE) {
+        const int hw = wave_reduce_valu<false>(wave_cmax_hi[lane & 15], [](int a, int b) { return max(a, b); });
+        cmax = __longlong_as_double((long long)hw << 32);
+    } else {
         double cm = 0.0;
         for (int i = tid; i < k * d; i += kMT) cm = fmax(cm, fabs(crows[i]));
         cm = wave_max_f64(cm);
         if (lane == 0 && cm > 0.0) atomicMax(&cmax_bits, (unsigned long long)__double_as_longlong(cm));
+        __syncthreads();
+        cmax = __longlong_as_double((long long)cmax_bits);
     }
-    __syncthreads();
     // (uniform values through readfirstlane: scalar registers, not VGPRs, for the rest of the kernel)
-    const int ec = __builtin_amdgcn_readfirstlane(filter_scale_exp(__longlong_as_double((long long)cmax_bits)));
+    const int ec = __builtin_amdgcn_readfirstlane(filter_scale_exp(cmax));
     const int exc = ex + ec;
+    KSTAMP_VM(9);
     for (int t = wave; t < n_tiles; t += 2 * kFilterWaves) {
         const int t2 = t + kFilterWaves;
-        double c0[kStageRegs], c1[kStageRegs], r0[DP], r1[DP];
-        filter_stage_fetch<DP>(t, lane, crows, k, d, c0, r0);
-        if (t2 < n_tiles) filter_stage_fetch<DP>(t2, lane, crows, k, d, c1, r1);
-        filter_stage_build<DP>(t, lane, reinterpret_cast<unsigned short*>(img + (size_t)t * 64), c0, r0, k, d, ec, exc, tab, cz,
-                               hs, &any_bad);
+        double c0[kStageRegs], c1[kStageRegs], q0[kStageRowQ<DP>], q1[kStageRowQ<DP>];
+        filter_stage_fetch<DP>(t, lane, crows, k, d, c0, q0);
+        if (t2 < n_tiles) filter_stage_fetch<DP>(t2, lane, crows, k, d, c1, q1);
+        KSTAMP_VM(10);
+        filter_stage_build<DP>(t, lane, reinterpret_cast<unsigned short*>(img + (size_t)t * 64), c0, q0, k, d, ec, exc, tab,
+                               cz, hs, &any_bad);
         if (t2 < n_tiles)
-            filter_stage_build<DP>(t2, lane, reinterpret_cast<unsigned short*>(img + (size_t)t2 * 64), c1, r1, k, d, ec, exc, tab,
-                                   cz, hs, &any_bad);
+            filter_stage_build<DP>(t2, lane, reinterpret_cast<unsigned short*>(img + (size_t)t2 * 64), c1, q1, k, d, ec, exc,
+                                   tab, cz, hs, &any_bad);
+        KSTAMP(11);
     }
     __syncthreads();
     // the upper bounds come out in units of 2^-(e_x + e_c): R goes back to the units of the fp32 scores with this
@@ -711,9 +741,7 @@ __global__ __launch_bounds__(64 * filter_waves(DP, ACCUM, sizeof(T) == 8 && !WHI
     const bool all_scan = __builtin_amdgcn_readfirstlane(any_bad) != 0;
     KSTAMP(0);
 
-    if constexpr (kReloadZ) {
-        if (unit < u_end) load_images(unit);
-    }
+    KSTAMP_VM(12);
     unsigned long long my_scans = 0;
     // 16-byte loads of a frame's coordinates: fp64 rows of exactly DP features on 16-byte boundaries
     const bool vec_rows = sizeof(T) == 8 && d == DP && ((ld * sizeof(T)) & 15) == 0 && (((uintptr_t)x) & 15) == 0;
